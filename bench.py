@@ -14,7 +14,11 @@ the bodies are range-partitioned over the ranks with one RCCL all-gather of posi
                                                   # game-thread model, OctreeSearch.cpp:21-34; RCCL grouped send/recv +
                                                   # in-place all-gather between the devices)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (the headline and the
+roofline figures of those same steps).  --full adds, after the timed region, what else the benchmark measures and checks: the
+fp64-sampled parity check of the timed pass, the distinct-mass row, the all-gather-only row (multi-GPU), the CPU baselines,
+BASELINE's other configs and the Barnes-Hut frames.  --dump-outputs DIR writes what the timed path computed in its last step
+(positions, velocities, accelerations of every body) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -93,6 +97,28 @@ def sampled_force_error(posm_all, acc_own, i_begin, bodies, G, eps):
         got = np.asarray(acc_own[i - i_begin, :3], np.float64)
         worst = max(worst, float(np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-300)))
     return worst
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 20261005
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one `directory/<name>.npy` per array (float32 or float64, one row per body).  When the arrays would
+    take more than DUMP_LIMIT_BYTES together, every one of them keeps the same rows: a fixed, seeded sample of bodies in
+    ascending order, so that two runs with the same arguments write the same bodies."""
+    import numpy as np
+    arrays = {k: np.asarray(a) for k, a in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"dump_outputs: {name} is {a.dtype}, not float32 or float64")
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.itemsize * (a.size // max(a.shape[0], 1)) for a in arrays.values())
+    keep = (DUMP_LIMIT_BYTES - 1024 * len(arrays)) // row_bytes
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False)) if n > keep else None
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows]))
 
 
 def cpu_baseline(posm, target_seconds):
@@ -676,17 +702,25 @@ def run_single_host(args):
         u_ms, u_n = e.kernel_time(nb.KERNEL_UPDATE)
         clk = clock_fields(e, f_ms / max(f_n, 1) * 1e-3, float(n // g) * float(n))
         equal_mass = e.equal_mass_form()
-        p_end = e.state(np.float64 if args.precision == "f64" else np.float32)[0]
-        finite = bool(np.isfinite(p_end).all())
-        e.compute_forces()                           # parity of the benched instantiation, after the timed region
-        acc = e.accelerations(np.float64 if args.precision == "f64" else np.float32)
+        dtype = np.float64 if args.precision == "f64" else np.float32
+        if args.dump_outputs or args.full:
+            p_end, v_end, a_end = e.state(dtype)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"positions": p_end[:, :3], "velocities": v_end[:, :3], "accelerations": a_end[:, :3]})
+        if args.full:
+            e.compute_forces()                       # parity of the benched instantiation, after the timed region
+            acc = e.accelerations(dtype)
     slice_n = n // g
-    bodies = sorted({b for k in range(g) for b in sample_bodies(k * slice_n, slice_n, cfg["super_tile"], cfg["i_per_thread"], seed=7 + k)})
-    err = sampled_force_error(p_end, acc, 0, bodies, 1.0e4, args.eps)
-    tol = {"f32": 2e-5, "f32_kahan": 2e-6 if args.eps > 0 else 2e-5, "f64": 1e-12}[args.precision]
-    if not (finite and err < tol):
-        raise SystemExit(f"bench.py: the benched force pass disagrees with the fp64 direct sum on sampled bodies: "
-                         f"max rel err {err:.3e} >= {tol:.1e} (finite={finite})")
+    checks = {}
+    if args.full:
+        finite = bool(np.isfinite(p_end).all())
+        bodies = sorted({b for k in range(g) for b in sample_bodies(k * slice_n, slice_n, cfg["super_tile"], cfg["i_per_thread"], seed=7 + k)})
+        err = sampled_force_error(p_end, acc, 0, bodies, 1.0e4, args.eps)
+        tol = {"f32": 2e-5, "f32_kahan": 2e-6 if args.eps > 0 else 2e-5, "f64": 1e-12}[args.precision]
+        if not (finite and err < tol):
+            raise SystemExit(f"bench.py: the benched force pass disagrees with the fp64 direct sum on sampled bodies: "
+                             f"max rel err {err:.3e} >= {tol:.1e} (finite={finite})")
+        checks = {"finite": finite, "max_rel_err_sampled": err, "bodies_sampled": len(bodies), "rel_err_tolerance": tol}
     pairs_per_step = float(n) * float(n)
     launch_pairs = float(slice_n) * float(n)
     avg_launch_s = f_ms / max(f_n, 1) * 1e-3
@@ -711,8 +745,7 @@ def run_single_host(args):
                    "algorithm": cfg["algorithm"], "zero_distance": args.zero_mode, "lds_tile_bodies": cfg["tile"],
                    "i_per_lane": cfg["i_per_thread"], "j_split": cfg["j_split"] if cfg["algorithm"] == "tiled" else None,
                    "super_tile_bodies": cfg["super_tile"] or None, "workgroups_per_device": cfg["blocks"],
-                   "accumulate": args.precision, "finite": finite, "equal_mass_form": equal_mass,
-                   "max_rel_err_sampled": err, "bodies_sampled": len(bodies), "rel_err_tolerance": tol},
+                   "accumulate": args.precision, "equal_mass_form": equal_mass, **checks},
         "roofline": {"bound": "valu_fp32" if args.precision != "f64" else "valu_fp64", "achieved": achieved, "peak": peak,
                      "unit": "TFLOP/s", "frac": achieved / peak,
                      "achieved_is": "algorithmic: N_i x N ordered interactions x 20 flop (SURVEY 8d) / the slowest device's launch time",
@@ -721,7 +754,7 @@ def run_single_host(args):
                      "avg_launch_ms": avg_launch_s * 1e3, "launches": f_n, "flop_per_pair": FLOP_PER_PAIR,
                      "pairs_per_launch": launch_pairs, "update_kernel_avg_ms": u_ms / max(u_n, 1)},
     }
-    if args.cpu_seconds > 0 and g == 1:
+    if args.full and args.cpu_seconds > 0 and g == 1:
         out["cpu_baseline"] = cpu_baseline(posm.astype(np.float32), args.cpu_seconds)
     print_result(out)
 
@@ -742,13 +775,20 @@ def main():
     ap.add_argument("--algorithm", default="auto", choices=["auto", "tiled", "symmetric"])
     ap.add_argument("--zero-mode", default="exact", choices=["exact", "floor"],
                     help="exact = the reference's d == 0 skip for every distance; floor = ~1e-20 eps^2 floor")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the fp64-sampled parity check of the timed pass, the distinct-mass row, "
+                         "the all-gather-only row (multi-GPU), the CPU baselines, BASELINE's other configs and the Barnes-Hut "
+                         "frames (one GPU, default workload); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the positions, velocities and accelerations of the last timed step as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of bodies above 64 MB)")
     ap.add_argument("--no-distinct-row", action="store_true",
-                    help="skip the second measurement of the same bodies with distinct masses (one GPU, equal-mass workloads)")
+                    help="with --full: skip the second measurement of the same bodies with distinct masses (one GPU, equal-mass workloads)")
     ap.add_argument("--no-tiled-row", action="store_true",
-                    help="multi-GPU: skip the extra timing of the one-sided kernel + all-gather-only step (config.all_gather_only_row)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length; 0 = skip")
+                    help="with --full, multi-GPU: skip the extra timing of the one-sided kernel + all-gather-only step (config.all_gather_only_row)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU baseline sample length; 0 = skip")
     ap.add_argument("--no-extra-rows", action="store_true",
-                    help="one GPU, default workload: skip BASELINE's other configs (N=65536 fp32, N=262144 fp64, N=2097152 Kahan) "
+                    help="with --full, one GPU, default workload: skip BASELINE's other configs (N=65536 fp32, N=262144 fp64, N=2097152 Kahan) "
                          "and the Barnes-Hut frames that follow the headline's timed region (`configs`, `bh` in the line)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="multi-GPU: every collective in the simulation's one stream order (default: the all-gather of a step's "
@@ -766,6 +806,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and args.host != "single" and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus, 2 * (args.child_timeout + 120.0)))
     if args.gpus > 1 and args.host != "single" and not args.worker:
@@ -889,30 +931,46 @@ def main():
     executed_tflops = (launch_pairs / 2 * flop_eval if cfg["algorithm"] == "symmetric"
                        else launch_pairs * FLOP_PER_PAIR) / avg_launch_s * 1e-12
     peak = PEAK_FP32_TFLOPS if args.precision != "f64" else PEAK_FP32_TFLOPS / 2
-    p_end, _ = sim.gather_state()
-    finite = bool(np.isfinite(p_end).all())
-    # parity of the benched instantiation at the benched size, after the timed region: one more force pass of the
-    # final state, sampled bodies against an fp64 direct sum (asserted: 2e-5 fp32, 2e-6 Kahan, 1e-12 fp64)
-    sim.compute_forces()
-    acc_own = sim.engine.accelerations(np.float64 if args.precision == "f64" else np.float32)
-    bodies = sample_bodies(sim.i_begin, sim.i_count, cfg["super_tile"], cfg["i_per_thread"])
-    err = sampled_force_error(p_end, acc_own, sim.i_begin, bodies, 1.0e4, args.eps)
-    n_sampled = len(bodies)
-    if world > 1:
-        t = torch.tensor([err, float(n_sampled)], dtype=torch.float64, device=f"cuda:{local_rank}")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        err = float(t[0])
-        n_sampled = int(t[1]) * world
-    tol = {"f32": 2e-5, "f32_kahan": 2e-6 if args.eps > 0 else 2e-5, "f64": 1e-12}[args.precision]
-    if not (finite and err < tol):
-        raise SystemExit(f"bench.py: the benched force pass disagrees with the fp64 direct sum on sampled bodies: "
-                         f"max rel err {err:.3e} >= {tol:.1e} (finite={finite})")
+    dtype = np.float64 if args.precision == "f64" else np.float32
+    if args.dump_outputs or args.full:
+        p_end, v_end = sim.gather_state()
+    if args.dump_outputs:
+        # the accelerations of the last step's force pass: every rank holds its own slice's
+        acc = sim.engine.state(dtype)[2]
+        if world > 1:
+            with sim._on_stream():
+                t = torch.from_numpy(np.ascontiguousarray(acc)).to(sim.device)
+                whole = torch.empty((n, 4), dtype=t.dtype, device=sim.device)
+                dist.all_gather_into_tensor(whole, t)
+                acc = whole.cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"positions": p_end[:, :3], "velocities": v_end[:, :3], "accelerations": acc[:, :3]})
+    checks = {}
+    if args.full:
+        finite = bool(np.isfinite(p_end).all())
+        # parity of the benched instantiation at the benched size, after the timed region: one more force pass of the
+        # final state, sampled bodies against an fp64 direct sum (asserted: 2e-5 fp32, 2e-6 Kahan, 1e-12 fp64)
+        sim.compute_forces()
+        acc_own = sim.engine.accelerations(dtype)
+        bodies = sample_bodies(sim.i_begin, sim.i_count, cfg["super_tile"], cfg["i_per_thread"])
+        err = sampled_force_error(p_end, acc_own, sim.i_begin, bodies, 1.0e4, args.eps)
+        n_sampled = len(bodies)
+        if world > 1:
+            t = torch.tensor([err, float(n_sampled)], dtype=torch.float64, device=f"cuda:{local_rank}")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            err = float(t[0])
+            n_sampled = int(t[1]) * world
+        tol = {"f32": 2e-5, "f32_kahan": 2e-6 if args.eps > 0 else 2e-5, "f64": 1e-12}[args.precision]
+        if not (finite and err < tol):
+            raise SystemExit(f"bench.py: the benched force pass disagrees with the fp64 direct sum on sampled bodies: "
+                             f"max rel err {err:.3e} >= {tol:.1e} (finite={finite})")
+        checks = {"finite": finite, "max_rel_err_sampled": err, "bodies_sampled": n_sampled, "rel_err_tolerance": tol}
 
     # The Plummer sphere's bodies all have one mass, and the symmetric kernel has a form for exactly that (no mass factor
     # inside the pair loop: nbody_equal_mass_form).  One GPU only: the same bodies with DISTINCT masses — the kernel's
     # general form — timed right after, same K steps, same parity check, so that both numbers stand in the one line.
     distinct = None
-    if world == 1 and equal_mass and not args.no_distinct_row:
+    if args.full and world == 1 and equal_mass and not args.no_distinct_row:
         posm2 = posm.copy()
         posm2[:, 3] *= np.random.default_rng(20261004).uniform(0.5, 1.5, n).astype(np.float32)
         sim2 = nb.ShardedSimulation(posm2, vel, rank=0, world_size=1, device=f"cuda:{local_rank}", engine_factory=factory,
@@ -946,7 +1004,7 @@ def main():
     # Multi-GPU only: north_star's literal step — one-sided kernel, per-step all-gather of positions, no other collective —
     # timed next to the default (symmetric + all-to-all) in the same job, same K steps, after the main measurement.
     tiled_row = None
-    if world > 1 and args.algorithm == "auto" and cfg["algorithm"] == "symmetric" and not args.no_tiled_row:
+    if args.full and world > 1 and args.algorithm == "auto" and cfg["algorithm"] == "symmetric" and not args.no_tiled_row:
         sim.close()
         sim = build("tiled")
         fence()
@@ -961,7 +1019,7 @@ def main():
     # One GPU, the default workload: BASELINE.json's other configs and the theta > 0 frames, each on a context of its own, after
     # everything of the headline has been measured (its engine released first: N = 2^21 Kahan wants its own pool).
     extra = None
-    if world == 1 and n == (1 << 20) and args.precision == "f32" and args.eps == 0.0 and args.algorithm == "auto" \
+    if args.full and world == 1 and n == (1 << 20) and args.precision == "f32" and args.eps == 0.0 and args.algorithm == "auto" \
             and not (args.tile or args.ipt or args.jsplit) and not args.no_extra_rows:
         sim.close()
         extra = extra_rows(args, nb)
@@ -984,10 +1042,10 @@ def main():
                        "lds_tile_bodies": cfg["tile"], "i_per_lane": cfg["i_per_thread"],
                        "j_split": cfg["j_split"] if cfg["algorithm"] == "tiled" else None,
                        "super_tile_bodies": cfg["super_tile"] or None,
-                       "workgroups": cfg["blocks"], "plan": cfg.get("plan"), "accumulate": args.precision, "finite": finite,
+                       "workgroups": cfg["blocks"], "plan": cfg.get("plan"), "accumulate": args.precision,
                        "equal_mass_form": equal_mass,
                        **({"distinct_masses": distinct} if distinct else {}),
-                       "max_rel_err_sampled": err, "bodies_sampled": n_sampled, "rel_err_tolerance": tol,
+                       **checks,
                        **({"fallback": fallback} if fallback else {}),
                        **({"all_gather_only_row": tiled_row} if tiled_row else {})},
             "roofline": {"bound": "valu_fp32" if args.precision != "f64" else "valu_fp64",
@@ -1007,7 +1065,7 @@ def main():
                          "flop_per_pair": FLOP_PER_PAIR, "pairs_per_launch": launch_pairs,
                          "update_kernel_avg_ms": u_ms / max(u_n, 1)},
         }
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(posm, args.cpu_seconds)
         if extra is not None:
             out["configs"], out["bh"], out["mid_sizes"] = extra

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--n", "65536", "--cpu-seconds", "0.5", "--settle-seconds", "0.05"],
+                          "--n", "65536", "--cpu-seconds", "0.5", "--settle-seconds", "0.05", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -53,6 +53,36 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert dm["max_rel_err_sampled"] < 2e-5 and 0.2 < dm["roofline_frac"] < rf["frac"] * 1.02
     assert dm["value"] == pytest.approx(65536.0 ** 2 * 3 / (dm["ms_per_step"] * 3e-3), rel=1e-6)
     assert 1.2 < dm["clock_ghz"] <= 2.45 and rf["cycles_per_interaction"] < dm["cycles_per_interaction"] < 36.0   # two more packed ops per register pair
+
+
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    # no --full: the headline and the roofline of the timed steps, nothing measured or checked after them; --dump-outputs writes
+    # what the last timed step computed, and with the same arguments two runs write the same bytes
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                              "--n", "65536", "--settle-seconds", "0.05", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        r = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                    "vs_baseline", "dtype", "data", "config", "roofline"):
+            assert key in r, key
+        assert r["steps"] == 4 and r["roofline"]["launches"] == 4 and r["dtype"] == "f32" and r["higher_is_better"] is True
+        assert r["value"] == pytest.approx(65536.0 ** 2 * 4 / (r["ms_per_step"] * 4e-3), rel=1e-6)
+        assert "cpu_baseline" not in r and "configs" not in r and "bh" not in r
+        assert "distinct_masses" not in r["config"] and "max_rel_err_sampled" not in r["config"]
+        arrays = {name: np.load(d / f"{name}.npy") for name in ("positions", "velocities", "accelerations")}
+        for name, a in arrays.items():
+            assert a.shape == (65536, 3) and a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert np.abs(arrays["accelerations"]).max() > 0.0
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert dumps[0][name].tobytes() == dumps[1][name].tobytes(), name
 
 
 def test_stdout_is_the_json_line_alone_when_rccl_prints_its_banner():

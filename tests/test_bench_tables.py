@@ -59,3 +59,27 @@ def test_result_line_has_stdout_to_itself():
     assert out.returncode == 0, out.stderr
     assert out.stdout == '{"value": 1.5}\n'
     assert "a library banner on fd 1" in out.stderr and "a python print" in out.stderr
+
+
+def test_dump_outputs_keeps_to_its_limit_with_the_same_rows_in_every_file(tmp_path, monkeypatch):
+    """--dump-outputs: below the limit every body is written as it is; above it every file keeps the same fixed, seeded sample of
+    rows (ascending body order), the same from run to run, and all files together stay within the limit."""
+    import numpy as np
+    b = _bench()
+    n = 5000
+    rows = np.arange(n, dtype=np.float64)
+    arrays = {"positions": np.stack([rows] * 3, 1).astype(np.float32), "accelerations": np.stack([rows] * 3, 1)}
+    b.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a), name
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 60000)
+    for run in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / run), arrays)
+        files = [tmp_path / run / f"{name}.npy" for name in arrays]
+        assert sum(os.path.getsize(f) for f in files) <= 60000
+    p1, a1 = (np.load(tmp_path / "s1" / f"{name}.npy") for name in ("positions", "accelerations"))
+    assert 0 < len(p1) < n and p1.dtype == np.float32 and a1.dtype == np.float64
+    assert np.array_equal(p1[:, 0], a1[:, 0]) and np.all(np.diff(a1[:, 0]) > 0)
+    for name in arrays:
+        assert (tmp_path / "s1" / f"{name}.npy").read_bytes() == (tmp_path / "s2" / f"{name}.npy").read_bytes()

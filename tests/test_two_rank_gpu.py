@@ -32,7 +32,7 @@ def _bench_two_ranks(extra_env, extra_args=(), launcher=True):
     line for N > 1 (torch.distributed.run around it); False: the bare `python bench.py --gpus 2`."""
     import json
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--bodies", "65536", "--settle-seconds", "0.02",
-            *extra_args]
+            "--full", *extra_args]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NBODY_DIST_BACKEND="gloo", **extra_env)
     if launcher:
@@ -51,11 +51,15 @@ def _bench_two_ranks(extra_env, extra_args=(), launcher=True):
     return r, out.stderr
 
 
-def test_bench_multi_rank_line_on_one_gpu():
+def test_bench_multi_rank_line_on_one_gpu(tmp_path):
     # bench.py's own multi-rank path (the one the driver launches on 8 GPUs), rehearsed with two ranks sharing this GPU over
     # gloo: symmetric kernel + all-to-all as the headline, the all-gather-only step (north_star's literal one) beside it,
-    # and the fp64-sampled parity check on every rank's slice
-    r, _ = _bench_two_ranks({})
+    # the fp64-sampled parity check on every rank's slice, and rank 0's dump of every body's last step
+    import numpy as np
+    r, _ = _bench_two_ranks({}, extra_args=["--dump-outputs", str(tmp_path)])
+    for name in ("positions", "velocities", "accelerations"):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.shape == (65536, 3) and a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0.0, name
     cf = r["config"]
     assert r["n_gpus"] == 2 and cf["algorithm"] == "symmetric" and "fallback" not in cf
     assert cf["max_rel_err_sampled"] < 2e-5 and cf["bodies_sampled"] >= 48
@@ -108,7 +112,7 @@ def test_bench_without_a_launcher_starts_its_own_ranks():
     # bench.py starts the launcher as a child process before touching the GPU and relays its line and exit code
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--bodies", "65536",
-           "--settle-seconds", "0.02", "--no-tiled-row"]
+           "--settle-seconds", "0.02", "--no-tiled-row", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["NBODY_DIST_BACKEND"] = "gloo"
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -128,7 +132,7 @@ def test_bench_single_host_line():
     # communicator, every collective still runs); the same contract line, cpu_baseline included at N = 1
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--host", "single", "--steps", "2", "--warmup", "1",
-           "--bodies", "65536", "--settle-seconds", "0.02", "--cpu-seconds", "0.5"]
+           "--bodies", "65536", "--settle-seconds", "0.02", "--cpu-seconds", "0.5", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 bash tools/profile_bench.sh "$OUT/bench" 16 > "$OUT/profile_bench.log" 2>&1
 echo "bench profile done"
-python3 bench.py --gpus 1 --host single --steps 5 --warmup 1 --cpu-seconds 0 > "$OUT/bench_line_single_host.json" 2> "$OUT/bench_single_host_stderr.txt"
+python3 bench.py --gpus 1 --host single --steps 5 --warmup 1 --full --cpu-seconds 0 > "$OUT/bench_line_single_host.json" 2> "$OUT/bench_single_host_stderr.txt"
 echo "single host line done"
 bash tools/profile_bh.sh "$OUT/bh" r03 > "$OUT/profile_bh.log" 2>&1
 echo "bh profile done"

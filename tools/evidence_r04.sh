@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/r04"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -o bench -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -o bench -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --full \
   > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.txt"
 f=$(find "$OUT/bench_stats" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/r04_bench_kernel_stats_symmetric.csv"
 echo "bench done"

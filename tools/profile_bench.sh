@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="${1:-$ROOT/gpurun_out/prof}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --full \
   > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.txt"
 tail -1 "$OUT/bench_line.json"
 # PMC passes over the dominant kernel of that line

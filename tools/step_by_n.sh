@@ -2,13 +2,13 @@
 # Whole-step rate (bench.py's `value`: force pass + row folds + update) with the library defaults, by N and precision.
 out=${1:-gpurun_out/step_by_n.txt}
 {
-echo "# python bench.py --bodies N --steps K --warmup 3 --cpu-seconds 0  (library defaults; K chosen for >= 0.15 s of steps)"
+echo "# python bench.py --bodies N --steps K --warmup 3 --full --cpu-seconds 0  (library defaults; K chosen for >= 0.15 s of steps)"
 echo "# Plummer sphere = equal masses: the fp32 rows run the equal-mass form; the same bodies with distinct masses (general form) follow in the same row"
 for prec in f32 f32_kahan f64; do
 for n in 32768 65536 131072 262144 524288 1048576; do
   k=$((200 * 65536 / n * 65536 / n)); [ $k -lt 4 ] && k=4; [ $k -gt 400 ] && k=400
   eps=0; [ $prec = f32_kahan ] && eps=0.5
-  python bench.py --bodies $n --precision $prec --eps $eps --steps $k --warmup 3 --cpu-seconds 0 --settle-seconds 0.3 2>/dev/null | python -c "
+  python bench.py --bodies $n --precision $prec --eps $eps --steps $k --warmup 3 --full --cpu-seconds 0 --settle-seconds 0.3 2>/dev/null | python -c "
 import sys,json
 r=json.loads(sys.stdin.read()); c=r['config']; f=r['roofline']
 d=c.get('distinct_masses')
