@@ -254,6 +254,17 @@ NBODY_AMD_API int nbody_exchange_write_recv(nbody_ctx *ctx, const void *host);
 NBODY_AMD_API int nbody_set_theta(nbody_ctx *ctx, float theta);
 /* The opening angle in force (nbody_params.theta, nbody_set_theta, or what nbody_load_checkpoint took over from a file). */
 NBODY_AMD_API int nbody_get_theta(nbody_ctx *ctx, float *theta);
+/*
+ * The deepest tree a theta > 0 frame may build, 42 <= levels <= 200 (root = level 0); default 42.  A frame is answered iff the
+ * reference's Octree::Add of that frame reaches depth <= levels; a frame that goes deeper is refused as before (NBODY_ERR_UNSUPPORTED,
+ * "Barnes-Hut tree deeper than N levels"): the state is left alone and the frames queued behind it do nothing.  Above 42, clusters of
+ * bodies that share a cell of level 42 are resolved on the device (at most 64 bodies per such cell; more are refused with a message
+ * of their own) in a frame that costs more than an ordinary one; frames without such a cluster run as at 42.  fp32 contexts only
+ * (NBODY_ERR_UNSUPPORTED otherwise); allowed at theta == 0, in force once theta > 0.  Every device of nbody_create_multi and every
+ * slice context takes it.  A setting, not state: checkpoints do not keep it.  Other values: NBODY_ERR_INVALID.
+ */
+NBODY_AMD_API int nbody_set_bh_max_depth(nbody_ctx *ctx, int32_t levels);
+NBODY_AMD_API int nbody_get_bh_max_depth(nbody_ctx *ctx, int32_t *levels);
 /* Nodes and levels of the last tree built, and its root CoM (= the next frame's root centre). */
 NBODY_AMD_API int nbody_bh_stats(nbody_ctx *ctx, int32_t *nodes, int32_t *levels, float root_com[3]);
 /* What DrawOctreeBoxes passes to DrawDebugBox when ShowOctree is set (OctreeSearch.cpp:39-40): for every body the box

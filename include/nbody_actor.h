@@ -44,6 +44,8 @@ NBODY_AMD_API void nbody_actor_set_ph_delta_time(nbody_actor *a, float dt);
 NBODY_AMD_API int32_t nbody_actor_get_show_octree(const nbody_actor *a);
 NBODY_AMD_API void nbody_actor_set_show_octree(nbody_actor *a, int32_t show);
 NBODY_AMD_API void nbody_actor_set_theta(nbody_actor *a, float theta);
+/* The deepest Barnes-Hut tree a frame may build (nbody_set_bh_max_depth), applied with the opening angle at every CreateOctree / Tick. */
+NBODY_AMD_API void nbody_actor_set_bh_max_depth(nbody_actor *a, int32_t levels);
 NBODY_AMD_API void nbody_actor_set_seed(nbody_actor *a, uint64_t seed);
 NBODY_AMD_API void nbody_actor_set_engine(nbody_actor *a, int32_t device, int32_t precision, double G, double eps);
 /* Share the bodies over several GPUs from the next CreateSpacePoints / SetParticles on (nbody_create_multi); n = 0: one GPU again. */

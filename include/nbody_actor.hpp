@@ -34,6 +34,7 @@ class OctreeSearchActor {
   // device list; other precisions report NBODY_ERR_UNSUPPORTED in LastStatus).  Set Theta = 0 for the theta -> 0
   // limit of that walk — exact O(N^2) all-pairs, the hot path this engine exists for (any precision, any device list).
   float Theta = 1.0f;
+  int32_t BhMaxDepth = 42;              // the deepest Barnes-Hut tree a frame may build (nbody_set_bh_max_depth; 42 .. 200)
   uint64_t Seed = 0x4E426F6479ull;      // CreateSpacePoints' generator seed (the reference is unseeded)
   float ActorLocation[3] = {0, 0, 0};   // GetActorLocation(), .cpp:64
   bool MirrorParticles = true;          // refresh `Particles` after every Tick, as the reference's TArray is live
@@ -139,6 +140,7 @@ class OctreeSearchActor {
   void CreateOctree() {
     if (!Initialized) return;
     LastStatus = nbody_set_theta(ctx_, Theta);
+    if (LastStatus == NBODY_OK) LastStatus = ApplyBhMaxDepth();
     if (LastStatus) return;
     LastStatus = nbody_compute_forces(ctx_);
     forces_fresh_ = LastStatus == NBODY_OK;
@@ -149,6 +151,7 @@ class OctreeSearchActor {
     if (OnFlushPersistentDebugLines) OnFlushPersistentDebugLines();            // .cpp:24
     if (PhDeltaTime > 0 && Initialized) {                                      // .cpp:25 (+ guards .cpp:49,76)
       LastStatus = nbody_set_theta(ctx_, Theta);
+      if (LastStatus == NBODY_OK) LastStatus = ApplyBhMaxDepth();
       if (LastStatus == NBODY_OK && MirrorParticles) {
         // .cpp:26-31 and the mirror DrawOctreeBoxes reads, in one call with one host synchronisation
         float s = Size;
@@ -252,6 +255,7 @@ class OctreeSearchActor {
     p.eps = Eps;
     LastStatus = Devices.empty() ? nbody_create(&p, &ctx_)
                                  : nbody_create_multi(&p, Devices.data(), (int32_t)Devices.size(), &ctx_);
+    bh_depth_applied_ = 42;             // (a new context starts at the default)
     if (LastStatus) return;
     LastStatus = nbody_set_particles(ctx_, data_, sizeof(FParticle), (int32_t)num_);
     if (LastStatus) return;
@@ -264,7 +268,17 @@ class OctreeSearchActor {
     dirty_ = false;
   }
 
+  // BhMaxDepth reaches the context whenever it differs from what was applied last (42: every new context's own; an fp64
+  // context that never asked for more is never asked)
+  int ApplyBhMaxDepth() {
+    if (BhMaxDepth == bh_depth_applied_) return NBODY_OK;
+    const int rc = nbody_set_bh_max_depth(ctx_, BhMaxDepth);
+    if (rc == NBODY_OK) bh_depth_applied_ = BhMaxDepth;
+    return rc;
+  }
+
   nbody_ctx *ctx_ = nullptr;
+  int32_t bh_depth_applied_ = 42;       // the limit the context holds (nbody_set_bh_max_depth)
   FParticle *data_ = nullptr;           // the records: Particles.data() or the host's array
   size_t num_ = 0;
   std::vector<float> boxes_;

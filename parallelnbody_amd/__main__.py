@@ -52,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--theta", type=float, default=None,
                     help="opening angle: 0 = exact all-pairs (default); 1.0 = the reference's shipped Barnes-Hut walk.  With "
                          "--resume: the file's own opening angle unless this option says otherwise (then it is announced)")
+    ap.add_argument("--bh-max-depth", type=int, default=None,
+                    help="the deepest Barnes-Hut tree a frame may build, 42 .. 200 (default 42: deeper frames are refused)")
     ap.add_argument("--sync-energy", action="store_true",
                     help="energy lines also carry the total with the staggered velocity pulled to the positions' time "
                          "(v_n = v_{n-1/2} + dt/2 a_n: one extra force pass per line.  Positions, velocities and — at theta > 0 — "
@@ -73,6 +75,8 @@ def main(argv=None):
             print(f"--resume: {a.resume} was written at theta = {e.theta():g}; continuing at --theta {a.theta:g} as asked "
                   "(not the trajectory the file belongs to)", file=sys.stderr)
             e.set_theta(a.theta)
+        if a.bh_max_depth is not None:
+            e.set_bh_max_depth(a.bh_max_depth)
         f64 = a.precision == "f64"
         if a.leapfrog_start and not a.resume and a.dt > 0:
             e.compute_forces()

@@ -107,6 +107,8 @@ def lib():
     sig("nbody_exchange_write_recv", c_int, vp, vp)
     sig("nbody_set_theta", c_int, vp, c_f)
     sig("nbody_get_theta", c_int, vp, ctypes.POINTER(c_f))
+    sig("nbody_set_bh_max_depth", c_int, vp, ctypes.c_int32)
+    sig("nbody_get_bh_max_depth", c_int, vp, ctypes.POINTER(ctypes.c_int32))
     sig("nbody_bh_stats", c_int, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), fp)
     sig("nbody_bh_leaf_boxes", c_int, vp, fp, sz)
     sig("nbody_bh_leaf_order", c_int, vp, ctypes.POINTER(c_i32))
@@ -169,6 +171,7 @@ def lib():
     sig("nbody_actor_get_show_octree", c_i32, vp)
     sig("nbody_actor_set_show_octree", None, vp, c_i32)
     sig("nbody_actor_set_theta", None, vp, c_f)
+    sig("nbody_actor_set_bh_max_depth", None, vp, ctypes.c_int32)
     sig("nbody_actor_set_seed", None, vp, ctypes.c_uint64)
     sig("nbody_actor_set_engine", None, vp, c_i32, c_i32, c_d, c_d)
     sig("nbody_actor_set_devices", None, vp, ctypes.POINTER(c_i32), c_i32)

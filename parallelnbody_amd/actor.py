@@ -63,6 +63,10 @@ class OctreeSearch:
     def set_theta(self, theta):
         self._L.nbody_actor_set_theta(self._h, theta)
 
+    def set_bh_max_depth(self, levels):
+        """The deepest Barnes-Hut tree a frame may build (42 .. 200), applied at the next CreateOctree / Tick."""
+        self._L.nbody_actor_set_bh_max_depth(self._h, int(levels))
+
     def set_devices(self, devices):
         """Share the bodies over several GPUs (nbody_create_multi) from the next CreateSpacePoints / SetParticles on."""
         devs = (ctypes.c_int32 * len(devices))(*devices) if devices else None

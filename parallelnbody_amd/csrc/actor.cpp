@@ -43,6 +43,7 @@ void nbody_actor_set_ph_delta_time(nbody_actor *a, float dt) { if (a) a->impl.Ph
 int32_t nbody_actor_get_show_octree(const nbody_actor *a) { return a && a->impl.ShowOctree ? 1 : 0; }
 void nbody_actor_set_show_octree(nbody_actor *a, int32_t show) { if (a) a->impl.ShowOctree = show != 0; }
 void nbody_actor_set_theta(nbody_actor *a, float theta) { if (a) a->impl.Theta = theta; }
+void nbody_actor_set_bh_max_depth(nbody_actor *a, int32_t levels) { if (a) a->impl.BhMaxDepth = levels; }
 void nbody_actor_set_seed(nbody_actor *a, uint64_t seed) { if (a) a->impl.Seed = seed; }
 void nbody_actor_set_engine(nbody_actor *a, int32_t device, int32_t precision, double G, double eps) {
   if (!a) return;

@@ -142,6 +142,8 @@ struct SmallTree {
                                 // them leave one of level l - 1 as well (bh_sweep_chunks_kernel counts, bh_sweep_top_kernel skips barriers by them)
   long long *clocks;            // build with -DNBODY_BH_PHASE_CLOCKS: wall_clock64 at the kernels' phase boundaries
   int cap;
+  int deep;                     // the context answers trees deeper than 42 levels (nbody_set_bh_max_depth): a frame with two bodies in one
+                                // cell of level 42 is handed back with kStatusDeep instead of refused, and built again by bh_deep_frame
 };
 
 // second key word of the body at sorted position i
@@ -373,6 +375,8 @@ constexpr int kWarmCap = 384;              // slots per bucket
 constexpr int kWarmWin = 64;               // boundaries a workgroup keeps in LDS
 constexpr int kStatusRetry = 3;            // header word 3: the frame was given up by the warm sort; queue it again with the cold one
 constexpr int kStatusUnsorted = 4;         // ... a COLD sort left keys out of order: an internal error, reported (never seen; bh_lcp_scan_kernel's guard)
+constexpr int kStatusDeep = kBhStatusDeep;            // ... a deep context's frame has bodies below level 42: built again with its deep clusters resolved (bh_deep_frame)
+constexpr int kStatusDeepRun = 6;          // ... a deep frame's cell of level 42 holds more bodies than kDeepRunMax (refused)
 constexpr int kBsP = 512;                  // the padded bucket at most
 
 struct RadixPass {
@@ -512,6 +516,18 @@ __global__ __launch_bounds__(kWalkT) void bh_walk_rows_kernel(SmallTree T, float
                                                               unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
                                                               WalkSlice S);
 __global__ __launch_bounds__(kB) void bh_small_leaf_boxes_kernel(SmallTree T, int n, float4 *__restrict__ out);
+// kernels_bh_deep.hip (deep contexts' frames with bodies below level 42)
+__global__ __launch_bounds__(kB) void bh_deep_thr_kernel(SmallTree T, float theta, int levels, float *__restrict__ thr);
+__global__ __launch_bounds__(kB) void bh_deep_runs_kernel(SmallTree T, const float4 *__restrict__ posm, int n, int levels,
+                                                          int *__restrict__ lcpD, unsigned long long *__restrict__ xkey);
+__global__ __launch_bounds__(1024) void bh_deep_scan_kernel(SmallTree T, int n, const int *__restrict__ lcpD, int *__restrict__ first);
+__global__ __launch_bounds__(kB) void bh_deep_nodes_kernel(SmallTree T, const float4 *__restrict__ posm, int n, const int *__restrict__ first,
+                                                           const int *__restrict__ lcpD, const float *__restrict__ thr);
+__global__ __launch_bounds__(kB) void bh_deep_sweep_level_kernel(SmallTree T, const float4 *__restrict__ posm, int n,
+                                                                 const int *__restrict__ first, const int *__restrict__ lcpD, int l,
+                                                                 int div_mode);
+__global__ __launch_bounds__(kB) void bh_deep_leaf_boxes_kernel(SmallTree T, int n, const unsigned long long *__restrict__ xkey,
+                                                                float4 *__restrict__ out);
 // kernels_bh_walk.hip (TWO: two steps to a turn of the loop, the two register sets changing places)
 template <bool TWO>
 __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,

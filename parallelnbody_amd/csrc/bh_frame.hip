@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "bh_common.h"
+#include "bh_deep_path.h"
 
 namespace nbody {
 
@@ -69,6 +70,15 @@ struct BhState {
   unsigned int *own = nullptr, *own_blk = nullptr;   // [i_count] sorted positions of the slice's bodies in key order; [blocks of kB] their counts (bh_own_*_kernel)
   bool warm_off = false;       // NBODY_BH_WARM_SORT=0 at creation: the cold sorts every frame (A/B measurements, tests)
   bool level_sweeps = false;   // ComputeMass with a launch per level at any size (NBODY_BH_LEVEL_SWEEPS=1 at creation; always above kChunkSweepMaxN)
+  // deep contexts (bh_set_max_depth > 42): a frame with bodies below level 42 is handed back (kStatusDeep) and built again by bh_deep_frame
+  int max_depth = kMaxLevels;
+  bool large_ready = false;    // the larger systems' sort buffers exist (always for them; a small system's deep context allocates them)
+  int *lcpD = nullptr;         // [n + 1] shared digits of neighbours, below level 42 included (bh_deep_runs_kernel)
+  unsigned long long *xkey = nullptr;   // [n][kDeepWords] the paths below level 42 of the bodies of deep clusters, by sorted position
+  float *thrD = nullptr;       // [kDeepMaxLevels + 2] acceptance thresholds by level
+  uint2 *deep_hop = nullptr;   // small systems: the hop words of a deep frame's tree (the lane walk reads them)
+  bool last_deep = false;      // the last frame built was a deep frame (bh_leaf_boxes)
+  SmallTree deep_T{};          // ... and the tree it was built with
 };
 
 #define BH_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
@@ -88,6 +98,7 @@ int bh_tile_size(int n) {
 }
 
 static hipError_t bh_create_state(BhState *b, int n, int i_begin, int i_count);
+static hipError_t bh_alloc_large(BhState *b);
 
 // The hipMemset calls of bh_create_state go to the NULL stream and return before they have run; the frames run on the context's
 // stream, which is non-blocking — it does not wait for the null stream.  This state is created by the first theta > 0 call, right
@@ -145,11 +156,20 @@ static hipError_t bh_create_state(BhState *b, int n, int i_begin, int i_count) {
   { const char *e = getenv("NBODY_BH_SMALL_GLOBAL_WALK_N"); b->small_global_walk_n = e && *e ? atoi(e) : kSmGlobalWalkN; }   // (tuning; read at every bh_create)
   if (b->small) return hipSuccess;
   BH_TRY(hipMalloc(&t.hop, sizeof(uint2) * (size_t)b->node_cap));   // (every word a walk reads is written by the frame's bh_nodes_kernel)
+  return bh_alloc_large(b);
+}
+
+// The larger systems' buffers for the keys' sorts, the node numbering and ComputeMass: every larger system's, and a small system's
+// once it is a deep context (its deep frames take the larger systems' sort).
+static hipError_t bh_alloc_large(BhState *b) {
+  const int n = b->n;
+  SmallTree &t = b->st;
+  b->large_ready = true;
   BH_TRY(hipMalloc(&b->size_words, 2 * kSizeSlots * sizeof(unsigned int)));
   BH_TRY(hipMemset(b->size_words, 0, 2 * kSizeSlots * sizeof(unsigned int)));
   BH_TRY(hipMalloc(&b->khi2, sizeof(unsigned long long) * n));
   BH_TRY(hipMalloc(&b->idx2, sizeof(unsigned int) * n));
-  t.klo_by_body = 1;           // the second key words stay where the key kernel put them (second_word())
+  if (!b->small) t.klo_by_body = 1;   // the second key words stay where the key kernel put them (second_word())
   b->radix = n > bh_merge_max_n();
   { const char *e = getenv("NBODY_BH_LEVEL_SWEEPS"); b->level_sweeps = e && e[0] == '1'; }
   { const char *e = getenv("NBODY_BH_WARM_SORT"); b->warm_off = e && e[0] == '0'; }
@@ -191,13 +211,14 @@ static hipError_t bh_create_state(BhState *b, int n, int i_begin, int i_count) {
     BH_TRY(hipMalloc(&b->kids, sizeof(int) * 8 * (size_t)(kMaxLevels + 1) * nchunks));
   }
   BH_TRY(hipEventCreateWithFlags(&b->ev, hipEventDisableTiming));
+  BH_TRY(hipStreamSynchronize(nullptr));                         // (its memsets: a small system's deep context makes these between frames)
   return hipSuccess;
 }
 
 void bh_destroy(BhState *b) {
   if (!b) return;
   void *ptrs[] = {b->khi, b->klo, b->khi2, b->idx, b->idx2, b->bound, b->pos_sorted, b->slot_hi, b->slot_lo, b->klo_sorted, b->slot_idx, b->gcount, b->size_words, b->part_hist, b->slice_hist, b->rx_desc, b->first, b->first_local, b->block_sum, b->lcpS, b->straddle, b->kids, b->own, b->own_blk,
-                  b->counters, b->root, b->prev_com, b->st.com, b->st.meta, b->st.hop, b->st.leaf_level, b->st.thr, b->st.lvl, b->st.clocks};
+                  b->lcpD, b->xkey, b->thrD, b->deep_hop, b->counters, b->root, b->prev_com, b->st.com, b->st.meta, b->st.hop, b->st.leaf_level, b->st.thr, b->st.lvl, b->st.clocks};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   if (b->h_counters) (void)hipHostFree(b->h_counters);
   if (b->h_verdict) (void)hipHostFree(b->h_verdict);
@@ -241,8 +262,11 @@ static WalkSlice bh_walk_slice(BhState *b, hipStream_t s) {
 
 // One CreateOctree (.cpp:74-89) + walk (+ update) of a larger system, queued on the stream.  Up to kChunkSweepMaxN bodies nothing
 // waits for the host; above, the level-by-level ComputeMass needs the deepest level there (one wait inside).
+static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root,
+                               float *stage, hipStream_t s);
+
 static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_v, float theta, double G, float dt, int keep_root,
-                                 float *stage, hipStream_t s) {
+                                 float *stage, hipStream_t s, bool deep = false) {
   float4 *posm = (float4 *)posm_v;
   const int n = b->n;
   const dim3 blk(kB), grd((n + kB - 1) / kB);
@@ -263,8 +287,8 @@ static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_
   // b->khi, the bodies in b->idx, and the second key words, still in body order, in b->klo.
   SmallTree &T = b->st;
   T.khi = b->khi; T.sidx = b->idx; T.klo = b->klo; T.klo_by_body = 1;
-  const bool warm_now = b->warm && !b->warm_off && b->cold_left == 0;
-  if (b->cold_left > 0) b->cold_left -= 1;                      // (the warm sort keeps giving frames up: cold for a while — BhState::giveups_in_row)
+  const bool warm_now = !deep && b->warm && !b->warm_off && b->cold_left == 0;   // (a deep frame: the cold sorts)
+  if (!deep && b->cold_left > 0) b->cold_left -= 1;                      // (the warm sort keeps giving frames up: cold for a while — BhState::giveups_in_row)
   if (warm_now) {
     // a frame that follows a frame: the previous order is almost this frame's (bh_keys_bucket_kernel)
     b->warm_since_collect += 1;
@@ -332,6 +356,8 @@ static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_
     }
   }
   if (T.klo_by_body) hipLaunchKernelGGL(bh_bound_kernel, dim3((b->nb + kB - 1) / kB), blk, 0, s, b->khi, b->idx, b->klo, b->nb, b->bound);   // (a cold frame)
+  if (deep) return bh_deep_tail(b, posm, vel, acc_v, theta, G, dt, keep_root, stage, s);
+  b->last_deep = false;
   const int block = kB * b->scan_bpt;
   hipLaunchKernelGGL(bh_lcp_scan_kernel, dim3((n + block - 1) / block), blk, 0, s, T, n, b->scan_bpt, b->lcpS, b->first_local, b->block_sum);
   hipLaunchKernelGGL(bh_nodes_kernel, grd, blk, sizeof(unsigned long long) * (size_t)(((n - 1) >> b->smp_shift) + 1), s, T, posm, n,
@@ -392,6 +418,8 @@ hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, d
                     hipStream_t s) {
   if (!b->small) return bh_large_frame(b, posm, vel, acc, theta, G, dt, keep_root, stage, s);
   const int n = b->n;
+  b->last_deep = false;
+  b->st.khi = b->khi; b->st.klo = b->klo; b->st.sidx = b->idx; b->st.klo_by_body = 0;   // (a deep frame before this one took the larger systems' sort)
   int P = 1;
   while (P < n) P <<= 1;
   hipLaunchKernelGGL(bh_small_build_kernel, dim3(1), dim3(kSmT), 0, s, b->st, (const float4 *)posm, n, P, b->div_mode, keep_root, theta);
@@ -432,6 +460,15 @@ hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames) {
     b->last_nodes = b->n >= 2 ? 1 + 8 * b->h_counters[1] : 1;   // the reference's count: every split makes eight children
     b->last_levels = b->h_counters[2];
   }
+  if (b->h_counters[3] == kStatusDeep) {                        // a deep context's frame with bodies below level 42: the caller builds it
+    b->warm_since_collect = 0;                                   // again (bh_deep_frame), then queues the ones behind it again
+    b->size_ready = false; b->pos_ready = false;
+    BH_TRY(hipMemsetAsync(b->counters + 3, 0, sizeof(int), s));
+    if (b->gcount) BH_TRY(hipMemsetAsync(b->gcount, 0, sizeof(unsigned int) * 2 * (size_t)b->nb, s));
+    b->warm = false;
+    *status = kStatusDeep;
+    return hipSuccess;
+  }
   if (!b->small && b->h_counters[3] == kStatusRetry) {
     b->retries += 1;
     b->warm_since_collect = 0;
@@ -466,11 +503,79 @@ hipError_t bh_reset_root(BhState *b, hipStream_t s) {
 // What DrawOctreeBoxes hands to DrawDebugBox: (Origin, Size) of the leaf holding each body, written at the body's index
 hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s) {
   if (b->last_levels <= 0 && b->last_nodes <= 0) return hipErrorInvalidValue;
+  if (b->last_deep) {
+    hipLaunchKernelGGL(bh_deep_leaf_boxes_kernel, dim3((b->n + kB - 1) / kB), dim3(kB), 0, s, b->deep_T, b->n, b->xkey, (float4 *)out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(bh_small_leaf_boxes_kernel, dim3((b->n + kB - 1) / kB), dim3(kB), 0, s, b->st, b->n, (float4 *)out);
   return hipGetLastError();
 }
 
 void bh_set_div_mode(BhState *b, int div_mode) { b->div_mode = div_mode ? 1 : 0; }
+
+// The deepest tree the context answers (42 .. kDeepMaxLevels; nbody_set_bh_max_depth).  Above 42 the deep frames' buffers are made
+// here, once: the extended shared digits, the continuations of deep clusters, the thresholds of every level, and for a small system
+// the larger systems' sort buffers and hop words.  (hipMalloc / hipMemset: the null stream, waited for as in bh_create.)
+hipError_t bh_set_max_depth(BhState *b, int levels) {
+  if (levels < kMaxLevels || levels > kDeepMaxLevels) return hipErrorInvalidValue;
+  if (levels > kMaxLevels && !b->lcpD) {
+    if (!b->large_ready) BH_TRY(bh_alloc_large(b));
+    BH_TRY(hipMalloc(&b->lcpD, sizeof(int) * ((size_t)b->n + 1)));
+    BH_TRY(hipMalloc(&b->xkey, sizeof(unsigned long long) * kDeepWords * (size_t)b->n));
+    BH_TRY(hipMalloc(&b->thrD, sizeof(float) * (kDeepMaxLevels + 2)));
+    if (!b->st.hop) BH_TRY(hipMalloc(&b->deep_hop, sizeof(uint2) * (size_t)b->node_cap));
+    BH_TRY(hipStreamSynchronize(nullptr));
+  }
+  b->max_depth = levels;
+  b->st.deep = levels > kMaxLevels ? 1 : 0;
+  return hipSuccess;
+}
+
+// One frame of a deep context built again after bh_collect handed it back (kStatusDeep): the cold sorts, then bh_deep_tail.  One wait
+// inside (ComputeMass a launch per level: the host needs the deepest level).
+// A deep frame always walks with the lane walk's shipped loop (bh_walk_lane_kernel<false>): NBODY_BH_WALK / NBODY_BH_ROWS_MAX_N /
+// NBODY_BH_WAVE_MAX_N choose among the walks of ordinary frames only.  The loop reads each node's threshold from its hop word; the A/B
+// builds NBODY_BH_LANE_NO_PIPELINE / NBODY_BH_LANE_META_WORD read it from a table of kMaxLevels + 2 levels by the node word's level,
+// which a deep node saturates at 63 — those builds refuse deep frames.
+hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
+                         hipStream_t s) {
+#if defined(NBODY_BH_LANE_NO_PIPELINE) || defined(NBODY_BH_LANE_META_WORD)
+  (void)b; (void)posm; (void)vel; (void)acc; (void)theta; (void)G; (void)dt; (void)keep_root; (void)stage; (void)s;
+  return hipErrorNotSupported;
+#endif
+  if (!b->lcpD) return hipErrorInvalidValue;
+  return bh_large_frame(b, posm, vel, acc, theta, G, dt, keep_root, stage, s, true);
+}
+
+// The tree of a deep frame from the sorted keys (kernels_bh_deep.hip), ComputeMass, and the lane walk with the Tick's update behind it.
+static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root,
+                               float *stage, hipStream_t s) {
+  const int n = b->n;
+  const dim3 blk(kB), grd((n + kB - 1) / kB);
+  SmallTree D = b->st;
+  if (!D.hop) D.hop = b->deep_hop;
+  hipLaunchKernelGGL(bh_deep_thr_kernel, dim3(1), blk, 0, s, D, theta, b->max_depth, b->thrD);
+  hipLaunchKernelGGL(bh_deep_runs_kernel, grd, blk, 0, s, D, (const float4 *)posm, n, b->max_depth, b->lcpD, b->xkey);
+  hipLaunchKernelGGL(bh_deep_scan_kernel, dim3(1), dim3(1024), 0, s, D, n, b->lcpD, b->first);
+  hipLaunchKernelGGL(bh_deep_nodes_kernel, grd, blk, 0, s, D, (const float4 *)posm, n, b->first, b->lcpD, b->thrD);
+  BH_TRY(hipMemcpyAsync(b->h_counters, b->counters, sizeof(int) * kHdrWords, hipMemcpyDeviceToHost, s));
+  BH_TRY(hipStreamSynchronize(s));
+  int maxl = -1;
+  if (b->h_counters[3] == 0)
+    for (int q = 0; q < kDeepSlots; ++q) maxl = std::max(maxl, b->h_counters[kHdrDeep + q]);
+  for (int l = maxl; l >= 0; --l)
+    hipLaunchKernelGGL(bh_deep_sweep_level_kernel, grd, blk, 0, s, D, (const float4 *)posm, n, b->first, b->lcpD, l, b->div_mode);
+  hipLaunchKernelGGL(bh_finish_kernel, dim3(1), dim3(1), 0, s, D, n, keep_root);
+  const WalkSlice S = bh_walk_slice(b, s);
+  const int nw = b->i_count;
+  hipLaunchKernelGGL(bh_walk_lane_kernel<false>, dim3((nw + kB - 1) / kB), blk, 0, s, D, posm, (float4 *)vel, (float4 *)acc, nw, G, dt,
+                     stage, (unsigned int *)nullptr, (float4 *)nullptr, S);
+  b->size_ready = false; b->pos_ready = false;                 // (the walk left neither the next Size nor the positions in key order)
+  b->warm = !b->small;                                          // b->khi / b->idx hold an order the next frame can start from
+  b->last_deep = true;
+  b->deep_T = D;
+  return hipGetLastError();
+}
 
 // The bodies in the order DrawOctreeBoxes meets their leaves (OctreeSearch.cpp:36-45: depth first, children 0..7): the
 // path keys are the octant digits root to leaf, so key order IS that order.

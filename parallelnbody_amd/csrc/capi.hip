@@ -89,6 +89,7 @@ struct nbody_ctx {
   // Barnes-Hut mode (bh_frame.hip, kernels_bh_*.hip)
   float theta = 0.0f;
   nbody::BhState *bh = nullptr;
+  int bh_max_depth = 42;       // the deepest tree a frame may build (nbody_set_bh_max_depth): a setting, not state (checkpoints do not keep it)
   void *bh_acc = nullptr;      // [i_count] float4: the walk's output, summed (j_split = 1) by update_kernel
   struct { float dt = 0.f; float *stage = nullptr; int queued = 0; bool timed = false; } bh_batch;   // what bh_enqueue queued since the last bh_finish
   KernelTimer timers[2];
@@ -520,14 +521,29 @@ int ensure_bh(nbody_ctx *c) {
     return fail(c, NBODY_ERR_HIP, "bh_create: %s", hipGetErrorString(e));
   }
   nbody::bh_set_div_mode(c->bh, c->p.bh_div_mode);
+  if (c->bh_max_depth != 42 && (e = nbody::bh_set_max_depth(c->bh, c->bh_max_depth)) != hipSuccess)
+    return fail(c, NBODY_ERR_HIP, "bh_set_max_depth: %s", hipGetErrorString(e));
   if (c->posm_escaped) nbody::bh_positions_external(c->bh);
   return NBODY_OK;
 }
 
 int bh_status_error(nbody_ctx *c, int status) {
-  if (status == 1) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut tree deeper than 42 levels: two bodies closer than Size/2^42 (the reference's Add would recurse without bound on coincident bodies)");
+  if (status == 1 && c->bh_max_depth == 42) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut tree deeper than 42 levels: two bodies closer than Size/2^42 (the reference's Add would recurse without bound on coincident bodies)");
+  if (status == 1) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut tree deeper than %d levels: two bodies closer than Size/2^%d (the reference's Add would recurse without bound on coincident bodies)", c->bh_max_depth, c->bh_max_depth);
+  if (status == 6) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut: more than 64 bodies share one cell of level 42 (a deep context orders at most 64 bodies below level 42)");
   if (status == 2) return fail(c, NBODY_ERR_NOMEM, "Barnes-Hut node pool exhausted");
   if (status == 4) return fail(c, NBODY_ERR_STATE, "Barnes-Hut: the sorted path keys are out of order (an internal error of this library; the frame was not built and the state is what it was)");
+  return NBODY_OK;
+}
+
+// a deep context: the frame bh_collect handed back (kStatusDeep), built again with its deep clusters resolved (one wait inside)
+int bh_enqueue_deep(nbody_ctx *c, float dt, float *stage) {
+  const bool timed = c->p.time_kernels != 0;
+  EventPair ev;
+  if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
+  HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, dt, 0, stage, c->stream));
+  if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
+  c->bh_batch.queued += 1;
   return NBODY_OK;
 }
 
@@ -566,6 +582,13 @@ int bh_finish(nbody_ctx *c) {
     c->steps_done += frames;
     const int left = c->bh_batch.queued - frames;
     c->bh_batch.queued = 0;
+    if (status == nbody::kBhStatusDeep) {
+      // a deep context's frame with bodies below level 42: built again with its deep clusters resolved, the ones behind it queued again
+      if (c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, left);
+      if (int rc = bh_enqueue_deep(c, c->bh_batch.dt, left == 1 ? c->bh_batch.stage : nullptr)) return rc;
+      if (int rc = bh_enqueue(c, c->bh_batch.dt, left - 1, c->bh_batch.stage)) return rc;
+      continue;
+    }
     if (status != 3) {
       if (c->bh_batch.timed && c->timers[NBODY_KERNEL_FORCES].pending.size() >= 1024) { int rc = timer_drain(c, NBODY_KERNEL_FORCES); if (rc) return rc; }
       return bh_status_error(c, status);
@@ -597,10 +620,20 @@ int part_bh_collect(nbody_ctx *c, int *status, int *built) {
   HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &st, &frames));
   *status = st; *built = frames;
   if (c->bh_batch.queued > 0) c->steps_done += frames;         // (whole frames, not a diagnostic force pass)
-  if (st == 3 && c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, c->bh_batch.queued - frames);
+  if ((st == 3 || st == kBhStatusDeep) && c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, c->bh_batch.queued - frames);
   c->bh_batch.queued = 0;
-  if (st == 1 || st == 2 || st == 4) return bh_status_error(c, st);
+  if (st == 1 || st == 2 || st == 4 || st == 6) return bh_status_error(c, st);
   return NBODY_OK;
+}
+// a deep context's frame handed back by part_bh_collect (status 5): built again on this device with its deep clusters resolved; the
+// caller collects it like any other frame
+int part_bh_queue_deep_frame(nbody_ctx *c, float dt, bool diagnostic) {
+  if (int rc = use_device(c)) return rc;
+  if (!(dt > 0.0f)) {
+    HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
+    return run_update(c, 0.0f);
+  }
+  return bh_enqueue_deep(c, dt, nullptr);
 }
 // the next tree's root centre (the previous tree's CoM, OctreeSearch.cpp:77-79) of a context that has built a tree: what a checkpoint keeps
 int part_bh_root(nbody_ctx *c, float out[3], int *has_root) {
@@ -632,6 +665,15 @@ int run_forces_bh(nbody_ctx *c, bool diagnostic) {
     { int rc = queue_forces_bh(c, diagnostic); if (rc) return rc; }
     int status = 0;
     HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, nullptr));
+    if (status == nbody::kBhStatusDeep) {                      // a deep context: once more, with its deep clusters resolved
+      const bool timed = c->p.time_kernels != 0;                // (the timed pass is the one that did the work, not the attempt handed back)
+      if (timed) timer_take_back(c, NBODY_KERNEL_FORCES, 1);
+      EventPair ev;
+      if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
+      HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
+      if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
+      HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, nullptr));
+    }
     if (status != 3) return bh_status_error(c, status);
     if (c->p.time_kernels) timer_take_back(c, NBODY_KERNEL_FORCES, 1);   // given up by the warm sort: once more, with the cold sorts
   }
@@ -1762,6 +1804,31 @@ int nbody_set_theta(nbody_ctx *c, float theta) {
   if (theta != c->theta) c->sym_posg_valid = false;   // the other force pass moves bodies without preparing the next all-pairs pass
   if (theta != c->theta && c->bh) nbody::bh_positions_changed(c->bh);   // ... nor leaving the next Barnes-Hut frame's Size
   c->theta = theta;
+  return NBODY_OK;
+}
+
+int nbody_set_bh_max_depth(nbody_ctx *c, int32_t levels) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (levels < 42 || levels > 200) return fail(c, NBODY_ERR_INVALID, "nbody_set_bh_max_depth: levels must be in [42, 200]");
+  if (c->multi) {
+    const int rc = multi_rc(c, nbody::multi_set_bh_max_depth(c->multi, levels));
+    if (!rc) c->bh_max_depth = levels;
+    return rc;
+  }
+  if (c->p.precision != NBODY_PREC_F32)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_set_bh_max_depth: Barnes-Hut needs an fp32 context");
+  if (int rc = use_device(c)) return rc;
+  if (c->bh) {
+    const hipError_t e = nbody::bh_set_max_depth(c->bh, levels);
+    if (e != hipSuccess) return fail(c, NBODY_ERR_HIP, "nbody_set_bh_max_depth: %s", hipGetErrorString(e));
+  }
+  c->bh_max_depth = levels;    // (a context without a tree yet takes it when its first theta > 0 frame creates one: ensure_bh)
+  return NBODY_OK;
+}
+
+int nbody_get_bh_max_depth(nbody_ctx *c, int32_t *levels) {
+  if (!c || !levels) return NBODY_ERR_INVALID;
+  *levels = c->bh_max_depth;
   return NBODY_OK;
 }
 

@@ -148,6 +148,10 @@ hipError_t bh_reset_root(BhState *b, hipStream_t s);          // previous CoM :=
 bool bh_is_small(const BhState *b);
 hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
                     hipStream_t s);
+constexpr int kBhStatusDeep = 5;                          // bh_collect: a deep context's frame to build again with bh_deep_frame
+hipError_t bh_set_max_depth(BhState *b, int levels);      // the deepest tree answered, 42 .. 200 (above 42: deep frames, bh_deep_frame)
+hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
+                         hipStream_t s);                   // the frame bh_collect handed back with *status 5, built with its deep clusters
 float bh_last_size(const BhState *b);                         // Size of the last frame bh_collect has seen
 hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames);   // *status 3: queue the frames that were not built again
 hipError_t bh_debug_clocks(BhState *b, long long out[16 + 3 * 512], hipStream_t s);   // tuning builds only (tools/bh_phases.py)

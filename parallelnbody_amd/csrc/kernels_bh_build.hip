@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kB) void bh_lcp_scan_kernel(SmallTree T, int n, int
       first_local[i] = c;                                      // the count for now; the scan below turns it into the prefix
       sum += c;
       if (i == n - 1) lcpS[n] = (signed char)-1;
-      if (ln == kMaxLevels) T.hdr[3] = 1;                      // the reference would recurse on: the frame is refused
+      if (ln == kMaxLevels) T.hdr[3] = T.deep ? kStatusDeep : 1;   // the reference would recurse on: the frame is refused (a deep context: built again)
       ties += ln >= kLevelsPerKey ? 1 : 0;                     // neighbours that agree in the whole first key word
       deep = max(deep, ln);
       lp = ln; h = hn;

@@ -441,7 +441,7 @@ __global__ __launch_bounds__(kSmT) void bh_small_build_kernel(SmallTree T, const
 #ifdef NBODY_BH_PHASE_CLOCKS
   if (t == 0) T.clocks[14] = s_bmax;                           // the fullest bucket of the sample sort
 #endif
-  if (s_err != 0) { if (t == 0) T.hdr[3] = 1; return; }
+  if (s_err != 0) { if (t == 0) T.hdr[3] = T.deep ? kStatusDeep : 1; return; }   // (a deep context: built again, bh_deep_frame)
   // ---- number the nodes: exclusive scan of (cells opened at body i) + 1, four bodies per thread.  The same pass writes the
   // leaves' words, counts the cells by level and notes which body opens each cell (numbered node - bodies before it).
   unsigned short *cowner = (unsigned short *)(lcpS + kSmBodies + 16);   // [cells]

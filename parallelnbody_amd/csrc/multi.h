@@ -41,6 +41,7 @@ int multi_load_checkpoint(Multi *m, const char *path, int64_t *steps_done);
 // replicated positions and walks + integrates its own slice; one in-place all-gather of the positions per frame.
 int multi_set_theta(Multi *m, float theta);
 int multi_bh_steps(Multi *m, float dt, int nsteps, int *built);   // whole frames; *built: how many were (a refused frame ends the call)
+int multi_set_bh_max_depth(Multi *m, int32_t levels);
 int multi_bh_stats(Multi *m, int32_t *nodes, int32_t *levels, float root_com[3]);
 int multi_bh_leaf_boxes(Multi *m, float *boxes, size_t stride);
 int multi_bh_leaf_order(Multi *m, int32_t *order);
@@ -50,6 +51,7 @@ int multi_bh_root(Multi *m, float root_com[3], int *has_root);
 // own slice, kick-drift; otherwise the accelerations alone — and, later, the one wait with the frames' verdict.
 int part_bh_queue_frame(nbody_ctx *c, float dt, bool diagnostic);
 int part_bh_collect(nbody_ctx *c, int *status, int *built);
+int part_bh_queue_deep_frame(nbody_ctx *c, float dt, bool diagnostic);   // after part_bh_collect's status 5
 int part_bh_root(nbody_ctx *c, float out[3], int *has_root);
 
 }  // namespace nbody

@@ -340,16 +340,20 @@ static int multi_bh_frames(Multi *m, float dt, int nframes, bool diagnostic, int
   while (todo > 0) {
     int left = todo < 64 ? todo : 64;                          // batches, as nbody_step has them: a given-up frame takes the ones queued behind it along
     todo -= left;
+    bool deep_next = false;                                    // the first frame of the next round is one a deep context handed back (status 5)
     while (left > 0) {
       for (int f = 0; f < left; ++f) {
-        for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, part_bh_queue_frame(m->part[(size_t)k], dt, diagnostic), "Barnes-Hut frame");
+        for (int k = 0; k < m->n_dev; ++k)
+          PART_TRY(m, k, (f == 0 && deep_next) ? part_bh_queue_deep_frame(m->part[(size_t)k], dt, diagnostic)
+                                               : part_bh_queue_frame(m->part[(size_t)k], dt, diagnostic), "Barnes-Hut frame");
         if (moves) { const int rc = gather_positions(m, true); if (rc) return rc; }
       }
+      deep_next = false;
       int status = 0, built = 0, refused_rc = NBODY_OK, refused_k = 0;
       for (int k = 0; k < m->n_dev; ++k) {                     // every device is collected (a refusal is cleared by that), then the verdicts compared
         int st = 0, b = 0;
         const int rc = part_bh_collect(m->part[(size_t)k], &st, &b);
-        if (rc && st != 1 && st != 2 && st != 4) return part_fail(m, k, rc, "Barnes-Hut frame");
+        if (rc && st != 1 && st != 2 && st != 4 && st != 6) return part_fail(m, k, rc, "Barnes-Hut frame");
         if (rc && !refused_rc) { refused_rc = rc; refused_k = k; }
         if (k == 0) { status = st; built = b; }
         else if (st != status || b != built)
@@ -360,6 +364,7 @@ static int multi_bh_frames(Multi *m, float dt, int nframes, bool diagnostic, int
       *built_out += built;
       left -= built;
       if (refused_rc) return part_fail(m, refused_k, refused_rc, "Barnes-Hut frame");   // the state is that of the frames built, on every device
+      if (status == 5) { deep_next = true; continue; }           // (5, kBhStatusDeep: built again with its deep clusters resolved, then the rest)
       if (status != 3) break;                                  // (3: the warm sort gave a frame up; `left` frames again)
     }
   }
@@ -367,6 +372,13 @@ static int multi_bh_frames(Multi *m, float dt, int nframes, bool diagnostic, int
 }
 
 int multi_bh_steps(Multi *m, float dt, int nsteps, int *built) { return multi_bh_frames(m, dt, nsteps, false, built); }
+
+int multi_set_bh_max_depth(Multi *m, int32_t levels) {
+  if (m->f64) return fail(m, NBODY_ERR_UNSUPPORTED, "nbody_set_bh_max_depth: Barnes-Hut needs an fp32 context");
+  { const int rc = wait_gather(m); if (rc) return rc; }
+  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_set_bh_max_depth(m->part[(size_t)k], levels), "nbody_set_bh_max_depth");
+  return NBODY_OK;
+}
 
 int multi_set_theta(Multi *m, float theta) {
   if (theta > 0.0f && m->f64) return fail(m, NBODY_ERR_UNSUPPORTED, "nbody_set_theta: Barnes-Hut needs an fp32 context");

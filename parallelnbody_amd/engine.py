@@ -234,6 +234,15 @@ class NBodyEngine:
         self._check(self._L.nbody_get_theta(self._h, ctypes.byref(v)))
         return v.value
 
+    def set_bh_max_depth(self, levels):
+        """The deepest Barnes-Hut tree a frame may build, 42 .. 200 (default 42); a deeper frame is refused (include/nbody.h)."""
+        self._check(self._L.nbody_set_bh_max_depth(self._h, int(levels)))
+
+    def bh_max_depth(self):
+        v = ctypes.c_int32()
+        self._check(self._L.nbody_get_bh_max_depth(self._h, ctypes.byref(v)))
+        return v.value
+
     def bh_stats(self):
         n, l = ctypes.c_int32(), ctypes.c_int32()
         com = np.zeros(3, np.float32)
