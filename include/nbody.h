@@ -101,12 +101,13 @@ typedef struct nbody_params {
   int32_t device;         /* HIP device ordinal */
   int32_t precision;      /* NBODY_PREC_* */
   double G;               /* gravitational constant; reference 1e4 */
-  double eps;             /* Plummer softening length; reference 0 (d == 0 pairs are skipped) */
+  double eps;             /* Plummer softening length; reference 0 (d == 0 pairs are skipped).  Applied at any theta: at theta > 0
+                             to the term of every node the walk accepts (see the Barnes-Hut paragraph below) */
   int32_t tile;           /* bodies per LDS tile: 64, 128, 256 (default), 512 */
   int32_t i_per_thread;   /* i-bodies per lane: 1, 2, 4 (8: fp32 symmetric kernels, 16: the plain one only); 0 = auto */
   int32_t j_split;        /* j-range chunks summed separately then combined in order; 0 = auto (a function of n_total only) */
   int32_t time_kernels;   /* nonzero: bracket kernels with HIP events for nbody_kernel_time */
-  int32_t zero_mode;      /* how d == 0 pairs are dropped when eps == 0 (NBODY_ZERO_*); 0 = default */
+  int32_t zero_mode;      /* how d == 0 pairs are dropped when eps == 0 (NBODY_ZERO_*); 0 = default.  No effect at theta > 0 */
   int32_t algorithm;      /* NBODY_ALGO_*; 0 = auto */
   float theta;            /* Barnes-Hut opening angle.  0 (default) = exact all-pairs, the hot path of this engine.  > 0 =
                              the reference's own tree walk (OctreeSearch.h:99-108; it ships 1.0, OctreeSearch.cpp:85) */
@@ -250,6 +251,9 @@ NBODY_AMD_API int nbody_exchange_write_recv(nbody_ctx *ctx, const void *host);
  * Systems of more than 4096 bodies sort a frame's path keys starting from the previous frame's order and take its Size out of the
  * previous frame's walk: a frame whose sort gives up (the records were replaced, the root box jumped) is queued again
  * by the library at the call's one wait; nothing of it shows but the time.
+ * Softening (eps > 0): the walk goes where the reference's goes, on the unsoftened d (Size/d < Theta, the leaf rule, d == 0 ends the
+ * subtree), and an accepted node adds float(G * M / ds^3) * (CoM - Pos) with ds = sqrtf(d^2 + eps2), eps2 = (float)(eps * eps), the
+ * one fp32 add not fused; an eps whose square rounds to 0 in fp32 gives the reference's frame, bit for bit.  zero_mode has no effect.
  */
 NBODY_AMD_API int nbody_set_theta(nbody_ctx *ctx, float theta);
 /* The opening angle in force (nbody_params.theta, nbody_set_theta, or what nbody_load_checkpoint took over from a file). */

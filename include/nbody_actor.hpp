@@ -44,7 +44,8 @@ class OctreeSearchActor {
                                         // device builds the whole tree and walks its slice — the frames equal one device's in every byte)
   int Precision = NBODY_PREC_F32;
   double G = 1.0e4;                     // .h:104
-  double Eps = 0.0;
+  double Eps = 0.0;                     // Plummer softening length (0: the reference's law); in force at any Theta — at Theta > 0 on
+                                        // the term of every node the walk accepts, the walk itself unsoftened (nbody.h, nbody_params.eps)
   int LastStatus = NBODY_OK;            // last C-ABI return code (the reference's methods are void)
 
   // Where the records live.  Unset: in `Particles` above.  Set: the host's own array — a UE4 adapter hands out its

@@ -5,6 +5,7 @@
     python -m parallelnbody_amd --plummer --n 65536 --eps 1 --steps 100 --energy-every 20
     python -m parallelnbody_amd --n 2000 --steps 300 --checkpoint run.ckpt ; python -m parallelnbody_amd --n 2000 --resume run.ckpt --steps 300
     python -m parallelnbody_amd --n 2000 --theta 1.0 --steps 600 --trajectory run.trj --trajectory-every 10   # as shipped: Barnes-Hut, theta = 1
+    python -m parallelnbody_amd --n 2000 --theta 1.0 --eps 5 --steps 600          # Barnes-Hut with every accepted node's term softened
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).

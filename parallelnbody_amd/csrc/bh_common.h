@@ -318,9 +318,13 @@ __device__ __forceinline__ unsigned long long descend_word(const float4 &p, floa
 // walks only its own bodies (a body's walk, OctreeSearch.cpp:83-86, reads the finished tree and writes that body alone).  own[j]: the
 // sorted position of the slice's j-th body in key order (neighbours in space share their windows' loads); null on a context that
 // owns all bodies (j is the sorted position itself).  vel / acc / stage hold the slice's bodies, posm all.
+// eps2: the Plummer softening every term of a softened walk (SOFT = true, force_term) adds to d^2 — the context's eps * eps rounded
+// once to fp32.  The unsoftened walks never read it: it sits in what was the struct's padding, so their arguments, and with them their
+// instructions, are those of the walks before softening.
 struct WalkSlice {
   const unsigned int *own;
   int off;
+  float eps2 = 0.f;
 };
 __device__ __forceinline__ int walk_place(const WalkSlice &S, int j) { return S.own != nullptr ? (int)S.own[j] : j; }
 
@@ -501,16 +505,21 @@ __global__ __launch_bounds__(kB) void bh_own_count_kernel(const unsigned int *__
 __global__ __launch_bounds__(kB) void bh_own_list_kernel(const unsigned int *__restrict__ sidx, int n, unsigned int lo, unsigned int cnt,
                                                          const int *__restrict__ status, const unsigned int *__restrict__ blk,
                                                          unsigned int *__restrict__ own);
+// (SOFT: every term softened by S.eps2 — force_term; false: the reference's term, S.eps2 unread)
+template <bool SOFT>
 __global__ __launch_bounds__(kWalkT) void bh_walk_compact_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                  float4 *__restrict__ acc, int n, float theta, double G, float dt,
                                                                  float *__restrict__ stage, WalkSlice S);
+template <bool SOFT>
 __global__ __launch_bounds__(kWvT) void bh_walk_wave_compact_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                     float4 *__restrict__ acc, int n, double G, float dt,
                                                                     float *__restrict__ stage, WalkSlice S);
+template <bool SOFT>
 __global__ __launch_bounds__(kWvGT) void bh_walk_wave_rows_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                   float4 *__restrict__ acc, int n, double G, float dt,
                                                                   float *__restrict__ stage, unsigned int *__restrict__ next_size,
                                                                   float4 *__restrict__ pos_sorted, WalkSlice S);
+template <bool SOFT>
 __global__ __launch_bounds__(kWalkT) void bh_walk_rows_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                               float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                               unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
@@ -528,8 +537,8 @@ __global__ __launch_bounds__(kB) void bh_deep_sweep_level_kernel(SmallTree T, co
                                                                  int div_mode);
 __global__ __launch_bounds__(kB) void bh_deep_leaf_boxes_kernel(SmallTree T, int n, const unsigned long long *__restrict__ xkey,
                                                                 float4 *__restrict__ out);
-// kernels_bh_walk.hip (TWO: two steps to a turn of the loop, the two register sets changing places)
-template <bool TWO>
+// kernels_bh_walk.hip (TWO: two steps to a turn of the loop, the two register sets changing places; SOFT: as above)
+template <bool TWO, bool SOFT>
 __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                           float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                           unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,

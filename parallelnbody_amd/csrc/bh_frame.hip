@@ -249,24 +249,24 @@ static bool bh_wave_walk() {
 }
 
 // The walk's view of the context's slice (WalkSlice): for a slice, the list of its bodies' sorted positions is made first —
-// behind the frame's sort, T.sidx final.
-static WalkSlice bh_walk_slice(BhState *b, hipStream_t s) {
-  if (!b->sliced) return WalkSlice{nullptr, 0};
+// behind the frame's sort, T.sidx final.  eps2: the softening the walk applies (> 0: the SOFT walks).
+static WalkSlice bh_walk_slice(BhState *b, hipStream_t s, float eps2) {
+  if (!b->sliced) return WalkSlice{nullptr, 0, eps2};
   const dim3 grd((b->n + kB - 1) / kB), blk(kB);
   hipLaunchKernelGGL(bh_own_count_kernel, grd, blk, 0, s, b->st.sidx, b->n, (unsigned int)b->i_begin, (unsigned int)b->i_count,
                      b->counters + 3, b->own_blk);
   hipLaunchKernelGGL(bh_own_list_kernel, grd, blk, 0, s, b->st.sidx, b->n, (unsigned int)b->i_begin, (unsigned int)b->i_count,
                      b->counters + 3, b->own_blk, b->own);
-  return WalkSlice{b->own, b->i_begin};
+  return WalkSlice{b->own, b->i_begin, eps2};
 }
 
 // One CreateOctree (.cpp:74-89) + walk (+ update) of a larger system, queued on the stream.  Up to kChunkSweepMaxN bodies nothing
 // waits for the host; above, the level-by-level ComputeMass needs the deepest level there (one wait inside).
-static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root,
-                               float *stage, hipStream_t s);
+static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float eps2, float dt,
+                               int keep_root, float *stage, hipStream_t s);
 
-static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_v, float theta, double G, float dt, int keep_root,
-                                 float *stage, hipStream_t s, bool deep = false) {
+static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_v, float theta, double G, float eps2, float dt,
+                                 int keep_root, float *stage, hipStream_t s, bool deep = false) {
   float4 *posm = (float4 *)posm_v;
   const int n = b->n;
   const dim3 blk(kB), grd((n + kB - 1) / kB);
@@ -356,7 +356,7 @@ static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_
     }
   }
   if (T.klo_by_body) hipLaunchKernelGGL(bh_bound_kernel, dim3((b->nb + kB - 1) / kB), blk, 0, s, b->khi, b->idx, b->klo, b->nb, b->bound);   // (a cold frame)
-  if (deep) return bh_deep_tail(b, posm, vel, acc_v, theta, G, dt, keep_root, stage, s);
+  if (deep) return bh_deep_tail(b, posm, vel, acc_v, theta, G, eps2, dt, keep_root, stage, s);
   b->last_deep = false;
   const int block = kB * b->scan_bpt;
   hipLaunchKernelGGL(bh_lcp_scan_kernel, dim3((n + block - 1) / block), blk, 0, s, T, n, b->scan_bpt, b->lcpS, b->first_local, b->block_sum);
@@ -388,22 +388,23 @@ static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_
   // below that, sixteen lanes per body (NBODY_BH_ROWS_MAX_N: tuning).  A slice walks its own bodies only — the count that
   // decides — and leaves neither the next frame's Size nor the positions in key order (they would be its own bodies' alone).
   const int rows_max_n = b->rows_max_n, wave_max_n = b->wave_max_n;   // (NBODY_BH_ROWS_MAX_N / NBODY_BH_WAVE_MAX_N as they stood at creation)
-  const WalkSlice S = bh_walk_slice(b, s);
+  const WalkSlice S = bh_walk_slice(b, s, eps2);
+  const bool soft = S.eps2 > 0.0f;
   const int nw = b->i_count;
   float4 *const pos_sorted = b->sliced ? nullptr : b->pos_sorted;
   if (b->sliced) next_size = nullptr;
   if (nw <= wave_max_n && nw <= rows_max_n && bh_wave_walk())
-    hipLaunchKernelGGL(bh_walk_wave_rows_kernel, dim3((nw + kWvGT / 64 - 1) / (kWvGT / 64)), dim3(kWvGT), 0, s, b->st, posm, (float4 *)vel,
-                       (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
+    hipLaunchKernelGGL(soft ? bh_walk_wave_rows_kernel<true> : bh_walk_wave_rows_kernel<false>, dim3((nw + kWvGT / 64 - 1) / (kWvGT / 64)),
+                       dim3(kWvGT), 0, s, b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
   else if (nw <= rows_max_n)
-    hipLaunchKernelGGL(bh_walk_rows_kernel, dim3((nw + kWalkT / kWalkG - 1) / (kWalkT / kWalkG)), dim3(kWalkT), 0, s, b->st, posm, (float4 *)vel,
-                       (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
+    hipLaunchKernelGGL(soft ? bh_walk_rows_kernel<true> : bh_walk_rows_kernel<false>, dim3((nw + kWalkT / kWalkG - 1) / (kWalkT / kWalkG)),
+                       dim3(kWalkT), 0, s, b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
   else if (nw >= kLaneTwoStepsMinN)
-    hipLaunchKernelGGL(bh_walk_lane_kernel<true>, dim3((nw + kB - 1) / kB), blk, 0, s, b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt,
-                       stage, next_size, pos_sorted, S);
+    hipLaunchKernelGGL((soft ? bh_walk_lane_kernel<true, true> : bh_walk_lane_kernel<true, false>), dim3((nw + kB - 1) / kB), blk, 0, s,
+                       b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
   else
-    hipLaunchKernelGGL(bh_walk_lane_kernel<false>, dim3((nw + kB - 1) / kB), blk, 0, s, b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt,
-                       stage, next_size, pos_sorted, S);
+    hipLaunchKernelGGL((soft ? bh_walk_lane_kernel<false, true> : bh_walk_lane_kernel<false, false>), dim3((nw + kB - 1) / kB), blk, 0, s,
+                       b->st, posm, (float4 *)vel, (float4 *)acc_v, nw, G, dt, stage, next_size, pos_sorted, S);
   b->pos_ready = !b->sliced;                                    // (every walk of all bodies writes them, moving or not)
   b->warm = true;                                               // b->khi / b->idx hold an order the next frame can start from
   return hipGetLastError();
@@ -414,9 +415,9 @@ static hipError_t bh_large_frame(BhState *b, void *posm_v, void *vel, void *acc_
 // bh_walk_compact_kernel); larger ones: bh_large_frame.
 // keep_root: the tree is a diagnostic's (nbody_compute_forces), the next frame's root centre stays what it was.
 // stage (optional): the walk also writes every body's FParticle record (10 floats, body order) there — the frame's mirror.
-hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
-                    hipStream_t s) {
-  if (!b->small) return bh_large_frame(b, posm, vel, acc, theta, G, dt, keep_root, stage, s);
+hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
+                    float *stage, hipStream_t s) {
+  if (!b->small) return bh_large_frame(b, posm, vel, acc, theta, G, eps2, dt, keep_root, stage, s);
   const int n = b->n;
   b->last_deep = false;
   b->st.khi = b->khi; b->st.klo = b->klo; b->st.sidx = b->idx; b->st.klo_by_body = 0;   // (a deep frame before this one took the larger systems' sort)
@@ -426,17 +427,19 @@ hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, d
   // from kSmGlobalWalkN bodies on the waves walk the tree in its global arrays (the larger systems' kernel): with a 146 KB copy of the
   // tree a CU holds one workgroup of eight bodies, and more bodies than that need second rounds (frames, LDS / global: N = 2000
   // 50.5 / 52.8 us, 3000 75.3 / 70.6, 4096 106.2 / 94.0).  (A slice walks its own bodies: their number decides.)
-  const WalkSlice S = bh_walk_slice(b, s);
+  const WalkSlice S = bh_walk_slice(b, s, eps2);
+  const bool soft = S.eps2 > 0.0f;
   const int nw = b->i_count;
   if (bh_wave_walk() && nw >= b->small_global_walk_n)
-    hipLaunchKernelGGL(bh_walk_wave_rows_kernel, dim3((nw + kWvGT / 64 - 1) / (kWvGT / 64)), dim3(kWvGT), 0, s, b->st, (float4 *)posm, (float4 *)vel,
-                       (float4 *)acc, nw, G, dt, stage, (unsigned int *)nullptr, (float4 *)nullptr, S);
+    hipLaunchKernelGGL(soft ? bh_walk_wave_rows_kernel<true> : bh_walk_wave_rows_kernel<false>, dim3((nw + kWvGT / 64 - 1) / (kWvGT / 64)),
+                       dim3(kWvGT), 0, s, b->st, (float4 *)posm, (float4 *)vel, (float4 *)acc, nw, G, dt, stage, (unsigned int *)nullptr,
+                       (float4 *)nullptr, S);
   else if (bh_wave_walk())
-    hipLaunchKernelGGL(bh_walk_wave_compact_kernel, dim3((nw + kWvT / 64 - 1) / (kWvT / 64)), dim3(kWvT), 0, s, b->st, (float4 *)posm,
-                       (float4 *)vel, (float4 *)acc, nw, G, dt, stage, S);
+    hipLaunchKernelGGL(soft ? bh_walk_wave_compact_kernel<true> : bh_walk_wave_compact_kernel<false>, dim3((nw + kWvT / 64 - 1) / (kWvT / 64)),
+                       dim3(kWvT), 0, s, b->st, (float4 *)posm, (float4 *)vel, (float4 *)acc, nw, G, dt, stage, S);
   else
-    hipLaunchKernelGGL(bh_walk_compact_kernel, dim3((nw + kWalkT / kWalkG - 1) / (kWalkT / kWalkG)), dim3(kWalkT), 0, s, b->st, (float4 *)posm,
-                       (float4 *)vel, (float4 *)acc, nw, theta, G, dt, stage, S);
+    hipLaunchKernelGGL(soft ? bh_walk_compact_kernel<true> : bh_walk_compact_kernel<false>, dim3((nw + kWalkT / kWalkG - 1) / (kWalkT / kWalkG)),
+                       dim3(kWalkT), 0, s, b->st, (float4 *)posm, (float4 *)vel, (float4 *)acc, nw, theta, G, dt, stage, S);
   return hipGetLastError();
 }
 
@@ -533,23 +536,23 @@ hipError_t bh_set_max_depth(BhState *b, int levels) {
 
 // One frame of a deep context built again after bh_collect handed it back (kStatusDeep): the cold sorts, then bh_deep_tail.  One wait
 // inside (ComputeMass a launch per level: the host needs the deepest level).
-// A deep frame always walks with the lane walk's shipped loop (bh_walk_lane_kernel<false>): NBODY_BH_WALK / NBODY_BH_ROWS_MAX_N /
+// A deep frame always walks with the lane walk's shipped loop (bh_walk_lane_kernel<false, SOFT>): NBODY_BH_WALK / NBODY_BH_ROWS_MAX_N /
 // NBODY_BH_WAVE_MAX_N choose among the walks of ordinary frames only.  The loop reads each node's threshold from its hop word; the A/B
 // builds NBODY_BH_LANE_NO_PIPELINE / NBODY_BH_LANE_META_WORD read it from a table of kMaxLevels + 2 levels by the node word's level,
 // which a deep node saturates at 63 — those builds refuse deep frames.
-hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
-                         hipStream_t s) {
+hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
+                         float *stage, hipStream_t s) {
 #if defined(NBODY_BH_LANE_NO_PIPELINE) || defined(NBODY_BH_LANE_META_WORD)
-  (void)b; (void)posm; (void)vel; (void)acc; (void)theta; (void)G; (void)dt; (void)keep_root; (void)stage; (void)s;
+  (void)b; (void)posm; (void)vel; (void)acc; (void)theta; (void)G; (void)eps2; (void)dt; (void)keep_root; (void)stage; (void)s;
   return hipErrorNotSupported;
 #endif
   if (!b->lcpD) return hipErrorInvalidValue;
-  return bh_large_frame(b, posm, vel, acc, theta, G, dt, keep_root, stage, s, true);
+  return bh_large_frame(b, posm, vel, acc, theta, G, eps2, dt, keep_root, stage, s, true);
 }
 
 // The tree of a deep frame from the sorted keys (kernels_bh_deep.hip), ComputeMass, and the lane walk with the Tick's update behind it.
-static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root,
-                               float *stage, hipStream_t s) {
+static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, float theta, double G, float eps2, float dt,
+                               int keep_root, float *stage, hipStream_t s) {
   const int n = b->n;
   const dim3 blk(kB), grd((n + kB - 1) / kB);
   SmallTree D = b->st;
@@ -566,10 +569,10 @@ static hipError_t bh_deep_tail(BhState *b, float4 *posm, void *vel, void *acc, f
   for (int l = maxl; l >= 0; --l)
     hipLaunchKernelGGL(bh_deep_sweep_level_kernel, grd, blk, 0, s, D, (const float4 *)posm, n, b->first, b->lcpD, l, b->div_mode);
   hipLaunchKernelGGL(bh_finish_kernel, dim3(1), dim3(1), 0, s, D, n, keep_root);
-  const WalkSlice S = bh_walk_slice(b, s);
+  const WalkSlice S = bh_walk_slice(b, s, eps2);
   const int nw = b->i_count;
-  hipLaunchKernelGGL(bh_walk_lane_kernel<false>, dim3((nw + kB - 1) / kB), blk, 0, s, D, posm, (float4 *)vel, (float4 *)acc, nw, G, dt,
-                     stage, (unsigned int *)nullptr, (float4 *)nullptr, S);
+  hipLaunchKernelGGL((S.eps2 > 0.0f ? bh_walk_lane_kernel<false, true> : bh_walk_lane_kernel<false, false>), dim3((nw + kB - 1) / kB), blk, 0,
+                     s, D, posm, (float4 *)vel, (float4 *)acc, nw, G, dt, stage, (unsigned int *)nullptr, (float4 *)nullptr, S);
   b->size_ready = false; b->pos_ready = false;                 // (the walk left neither the next Size nor the positions in key order)
   b->warm = !b->small;                                          // b->khi / b->idx hold an order the next frame can start from
   b->last_deep = true;

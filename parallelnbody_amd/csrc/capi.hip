@@ -536,12 +536,16 @@ int bh_status_error(nbody_ctx *c, int status) {
   return NBODY_OK;
 }
 
+// the Plummer softening of every theta > 0 walk: eps * eps in double, rounded once to fp32; 0 — eps == 0, or an eps whose square
+// rounds to 0 — walks with the reference's own term
+float bh_eps2(const nbody_ctx *c) { return (float)(c->p.eps * c->p.eps); }
+
 // a deep context: the frame bh_collect handed back (kStatusDeep), built again with its deep clusters resolved (one wait inside)
 int bh_enqueue_deep(nbody_ctx *c, float dt, float *stage) {
   const bool timed = c->p.time_kernels != 0;
   EventPair ev;
   if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-  HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, dt, 0, stage, c->stream));
+  HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, bh_eps2(c), dt, 0, stage, c->stream));
   if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
   c->bh_batch.queued += 1;
   return NBODY_OK;
@@ -553,7 +557,7 @@ int bh_enqueue(nbody_ctx *c, float dt, int nsteps, float *stage = nullptr) {
   for (int s = 0; s < nsteps; ++s) {
     EventPair ev;
     if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-    HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, dt, 0, s == nsteps - 1 ? stage : nullptr, c->stream));
+    HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, bh_eps2(c), dt, 0, s == nsteps - 1 ? stage : nullptr, c->stream));
     if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
     // (small systems queue a whole call's frames at once and give none up: bound the number of live events; the larger systems'
     // batches of 64 never get here, so the pairs of a given-up batch are still there to be taken back)
@@ -630,7 +634,7 @@ int part_bh_collect(nbody_ctx *c, int *status, int *built) {
 int part_bh_queue_deep_frame(nbody_ctx *c, float dt, bool diagnostic) {
   if (int rc = use_device(c)) return rc;
   if (!(dt > 0.0f)) {
-    HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
+    HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
     return run_update(c, 0.0f);
   }
   return bh_enqueue_deep(c, dt, nullptr);
@@ -656,7 +660,7 @@ int queue_forces_bh(nbody_ctx *c, bool diagnostic) {
   EventPair ev;
   const bool timed = c->p.time_kernels != 0;
   if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-  HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
+  HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
   if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
   return NBODY_OK;
 }
@@ -670,7 +674,7 @@ int run_forces_bh(nbody_ctx *c, bool diagnostic) {
       if (timed) timer_take_back(c, NBODY_KERNEL_FORCES, 1);
       EventPair ev;
       if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-      HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
+      HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
       if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
       HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, nullptr));
     }

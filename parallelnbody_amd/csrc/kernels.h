@@ -145,13 +145,15 @@ hipError_t bh_reset_root(BhState *b, hipStream_t s);          // previous CoM :=
 // *status 0 ok, 1 tree deeper than 42 levels, 2 node pool exhausted; a refused frame and everything queued behind it leave the
 // state untouched.  keep_root != 0: the next tree's root centre stays what it was (a diagnostic pass).
 // stage (optional): the walk also writes every body's FParticle record (10 floats, body order) there — the frame's mirror.
+// eps2: Plummer softening, (float)(eps * eps).  > 0: every accepted node's term is that of ds = sqrtf(d^2 + eps2) (the walks' SOFT
+// instantiations); where the walk goes is the reference's, on the unsoftened d.  0: the reference's term.
 bool bh_is_small(const BhState *b);
-hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
-                    hipStream_t s);
+hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
+                    float *stage, hipStream_t s);
 constexpr int kBhStatusDeep = 5;                          // bh_collect: a deep context's frame to build again with bh_deep_frame
 hipError_t bh_set_max_depth(BhState *b, int levels);      // the deepest tree answered, 42 .. 200 (above 42: deep frames, bh_deep_frame)
-hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float dt, int keep_root, float *stage,
-                         hipStream_t s);                   // the frame bh_collect handed back with *status 5, built with its deep clusters
+hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
+                         float *stage, hipStream_t s);    // the frame bh_collect handed back with *status 5, built with its deep clusters
 float bh_last_size(const BhState *b);                         // Size of the last frame bh_collect has seen
 hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames);   // *status 3: queue the frames that were not built again
 hipError_t bh_debug_clocks(BhState *b, long long out[16 + 3 * 512], hipStream_t s);   // tuning builds only (tools/bh_phases.py)

@@ -20,12 +20,17 @@ template <typename T> __device__ __forceinline__ T mul_add_sep(T a, T b, T c) {
 //    without its scaling for arguments below 2^-96 and its special cases, and the double-precision division likewise without its
 //    scaling and special cases: a wave with an argument below 2^-96, an infinite / NaN one or a mass that is not finite in any of
 //    its lanes takes sqrtf and the division themselves.
-__device__ __forceinline__ void force_term(float cx, float cy, float cz, float M, const float4 &p, double G, float &tx, float &ty,
-                                           float &tz) {
+// SOFT: Plummer softening — the same term of ds = sqrtf(d2 + eps2), one fp32 add (not fused) in front of the root; the fast path and
+// its guard look at ds2 the same way.  Where the walk goes (.h:102-103) is decided on the unsoftened d2 by the walk itself.  false:
+// eps2 is not read, and the term is the reference's, instruction for instruction.
+template <bool SOFT>
+__device__ __forceinline__ void force_term(float cx, float cy, float cz, float M, const float4 &p, double G, float eps2, float &tx,
+                                           float &ty, float &tz) {
 #pragma clang fp contract(off)
   const float ex = p.x - cx, ey = p.y - cy, ez = p.z - cz;
   float d2 = ex * ex + ey * ey;
   d2 = d2 + ez * ez;
+  if constexpr (SOFT) d2 = d2 + eps2;                          // ds2 (eps2 == 0 would leave every bit of d2: it is never -0)
   float d, s;                                                  // FVector::Dist, .h:101 (correctly rounded); the scale factor
   if (__any(!(d2 >= 0x1p-96f) || d2 == __builtin_inff() || !(fabsf(M) <= 0x1.fffffep127f))) {
     d = sqrtf(d2);
@@ -107,10 +112,11 @@ __device__ __forceinline__ int row_max(int v) {
 // The walk of one row (see the kernels below).  LDS_TREE: the nodes are the LDS arrays s_a / s_past / s_m; otherwise they
 // are read from the tree's global arrays (coalesced: a window is sixteen consecutive nodes) and the threshold comes from the
 // level.  list / term: the row's own LDS slices.  The row's first lane ends up with the acceleration.
-template <bool LDS_TREE, typename LIST_T>
+template <bool LDS_TREE, bool SOFT, typename LIST_T>
 __device__ __forceinline__ void walk_windows(const SmallTree &T, const float4 *s_a, const float *s_m, const unsigned short *s_past,
                                              const float *s_thr, LIST_T *list, float4 *term, int nodes, bool valid,
-                                             const float4 &p, double G, int g, int row_shift, float &ax, float &ay, float &az) {
+                                             const float4 &p, double G, float eps2, int g, int row_shift, float &ax, float &ay,
+                                             float &az) {
 #pragma clang fp contract(off)
   float sum = 0.f;                                             // lanes 0, 1, 2 of the row: the x, y, z sums (ZeroVector, .cpp:84)
   int w0 = valid ? 0 : nodes;                                  // first node of the window (the same in all lanes of the row)
@@ -159,8 +165,8 @@ __device__ __forceinline__ void walk_windows(const SmallTree &T, const float4 *s
     for (int e = g; e < cnt; e += kWalkG) {
       const int nd = (int)list[e];
       float tx, ty, tz;
-      if (LDS_TREE) { const float4 a = s_a[nd]; force_term(a.x, a.y, a.z, s_m[nd], p, G, tx, ty, tz); }
-      else { const float4 c = T.com[nd]; force_term(c.x, c.y, c.z, c.w, p, G, tx, ty, tz); }
+      if (LDS_TREE) { const float4 a = s_a[nd]; force_term<SOFT>(a.x, a.y, a.z, s_m[nd], p, G, eps2, tx, ty, tz); }
+      else { const float4 c = T.com[nd]; force_term<SOFT>(c.x, c.y, c.z, c.w, p, G, eps2, tx, ty, tz); }
       term[e] = make_float4(tx, ty, tz, 0.f);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -252,6 +258,7 @@ __device__ __forceinline__ void walk_lane_tail(bool valid, unsigned int body, co
   }
 }
 
+template <bool SOFT>
 __global__ __launch_bounds__(kWalkT) void bh_walk_compact_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                  float4 *__restrict__ acc, int n, float theta, double G, float dt,
                                                                  float *__restrict__ stage, WalkSlice S) {
@@ -295,9 +302,11 @@ __global__ __launch_bounds__(kWalkT) void bh_walk_compact_kernel(SmallTree T, fl
   BH_WALK_CLOCK(10);
   BH_WG_STAMP(1);
   if (in_lds)
-    walk_windows<true>(T, s_a, s_m, s_past, s_thr, s_list[group], s_term[group], nodes, valid, p, G, g, (t & 63) - g, ax, ay, az);
+    walk_windows<true, SOFT>(T, s_a, s_m, s_past, s_thr, s_list[group], s_term[group], nodes, valid, p, G, S.eps2, g, (t & 63) - g,
+                             ax, ay, az);
   else   // a tree too large for LDS (deep chains of single-child cells): the same windows on the global arrays
-    walk_windows<false>(T, s_a, s_m, s_past, s_thr, s_list[group], s_term[group], nodes, valid, p, G, g, (t & 63) - g, ax, ay, az);
+    walk_windows<false, SOFT>(T, s_a, s_m, s_past, s_thr, s_list[group], s_term[group], nodes, valid, p, G, S.eps2, g, (t & 63) - g,
+                              ax, ay, az);
   BH_WALK_CLOCK(11);
   BH_WG_STAMP(2);
 #ifdef NBODY_BH_PHASE_CLOCKS
@@ -330,10 +339,10 @@ __device__ __forceinline__ int wave_incl_max(int v) {             // inclusive m
 
 // K: nodes a body lists before their terms (.h:104) are worked out and added — in the walk's order, the reference's own order of
 // additions — by lanes 0, 1, 2 (x, y, z).  list / term: the wave's own LDS slices (term: 3 K floats, 16-byte aligned; K a multiple of 8).
-template <bool LDS_TREE, int K, typename LIST_T>
+template <bool LDS_TREE, int K, bool SOFT, typename LIST_T>
 __device__ __forceinline__ void walk_wave(const SmallTree &T, const float4 *s_a, const float *s_m, const unsigned short *s_past,
                                           const float *s_thr, LIST_T *list, float *term, int nodes, bool valid, const float4 &p,
-                                          double G, int lane, float &ax, float &ay, float &az) {
+                                          double G, float eps2, int lane, float &ax, float &ay, float &az) {
 #pragma clang fp contract(off)
   float sum = 0.f;                                             // lanes 0, 1, 2: the x, y, z sums (ZeroVector, .cpp:84)
   int w0 = valid ? 0 : nodes;                                  // first node of the window: the same in every lane
@@ -380,8 +389,8 @@ __device__ __forceinline__ void walk_wave(const SmallTree &T, const float4 *s_a,
       float tx = 0.f, ty = 0.f, tz = 0.f;
       if (e < cnt) {
         const int nd = (int)list[e];
-        if (LDS_TREE) { const float4 a = s_a[nd]; force_term(a.x, a.y, a.z, s_m[nd], p, G, tx, ty, tz); }
-        else { const float4 c = T.com[nd]; force_term(c.x, c.y, c.z, c.w, p, G, tx, ty, tz); }
+        if (LDS_TREE) { const float4 a = s_a[nd]; force_term<SOFT>(a.x, a.y, a.z, s_m[nd], p, G, eps2, tx, ty, tz); }
+        else { const float4 c = T.com[nd]; force_term<SOFT>(c.x, c.y, c.z, c.w, p, G, eps2, tx, ty, tz); }
       }
       term[e] = tx; term[K + e] = ty; term[2 * K + e] = tz;
     }
@@ -403,6 +412,7 @@ __device__ __forceinline__ void walk_wave(const SmallTree &T, const float4 *s_a,
   az = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sum), 2));
 }
 
+template <bool SOFT>
 __global__ __launch_bounds__(kWvT) void bh_walk_wave_compact_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                     float4 *__restrict__ acc, int n, double G, float dt,
                                                                     float *__restrict__ stage, WalkSlice S) {
@@ -466,9 +476,9 @@ __global__ __launch_bounds__(kWvT) void bh_walk_wave_compact_kernel(SmallTree T,
   float ax = 0.f, ay = 0.f, az = 0.f;                          // Acceleration = ZeroVector, .cpp:84
   BH_WG_STAMP(1);
   if (in_lds)
-    walk_wave<true, kWvK>(T, s_a, s_m, s_past, s_thr, s_list[wave], s_term[wave], nodes, valid, p, G, lane, ax, ay, az);
+    walk_wave<true, kWvK, SOFT>(T, s_a, s_m, s_past, s_thr, s_list[wave], s_term[wave], nodes, valid, p, G, S.eps2, lane, ax, ay, az);
   else   // a tree too large for LDS (deep chains of single-child cells): the same windows on the global arrays
-    walk_wave<false, kWvK>(T, s_a, s_m, s_past, s_thr, s_list[wave], s_term[wave], nodes, valid, p, G, lane, ax, ay, az);
+    walk_wave<false, kWvK, SOFT>(T, s_a, s_m, s_past, s_thr, s_list[wave], s_term[wave], nodes, valid, p, G, S.eps2, lane, ax, ay, az);
   BH_WG_STAMP(2);
 #ifdef NBODY_BH_PHASE_CLOCKS
   if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) {       // the shader clock under this load: s_sleep 127 = 127 * 64 cycles
@@ -481,6 +491,7 @@ __global__ __launch_bounds__(kWvT) void bh_walk_wave_compact_kernel(SmallTree T,
 }
 
 // ... and on the larger systems' tree in its global arrays: a window is sixty-four consecutive nodes — one coalesced 1 KB load
+template <bool SOFT>
 __global__ __launch_bounds__(kWvGT) void bh_walk_wave_rows_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                                   float4 *__restrict__ acc, int n, double G, float dt,
                                                                   float *__restrict__ stage, unsigned int *__restrict__ next_size,
@@ -505,13 +516,14 @@ __global__ __launch_bounds__(kWvGT) void bh_walk_wave_rows_kernel(SmallTree T, f
   __syncthreads();
   const float4 p = posm[body];
   float ax = 0.f, ay = 0.f, az = 0.f;
-  walk_wave<false, kWvGK>(T, (const float4 *)nullptr, (const float *)nullptr, (const unsigned short *)nullptr, s_thr, s_list[wave],
-                          s_term[wave], nodes, valid, p, G, lane, ax, ay, az);
+  walk_wave<false, kWvGK, SOFT>(T, (const float4 *)nullptr, (const float *)nullptr, (const unsigned short *)nullptr, s_thr,
+                                s_list[wave], s_term[wave], nodes, valid, p, G, S.eps2, lane, ax, ay, az);
   walk_row_tail(valid, lane, body, p, ax, ay, az, posm, vel, acc, dt, stage, s_term[wave], S.off, next_size, pos_sorted, place);
 }
 
 // The same walk for systems whose tree does not go into LDS but that have too few bodies to keep the chip busy with one lane
 // each (bh_walk_lane_kernel): rows of sixteen lanes on the global arrays, no tree copy.
+template <bool SOFT>
 __global__ __launch_bounds__(kWalkT) void bh_walk_rows_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                               float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                               unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
@@ -534,8 +546,8 @@ __global__ __launch_bounds__(kWalkT) void bh_walk_rows_kernel(SmallTree T, float
   __syncthreads();
   const float4 p = posm[body];
   float ax = 0.f, ay = 0.f, az = 0.f;
-  walk_windows<false>(T, (const float4 *)nullptr, (const float *)nullptr, (const unsigned short *)nullptr, s_thr, s_list[group],
-                      s_term[group], nodes, valid, p, G, g, (t & 63) - g, ax, ay, az);
+  walk_windows<false, SOFT>(T, (const float4 *)nullptr, (const float *)nullptr, (const unsigned short *)nullptr, s_thr,
+                            s_list[group], s_term[group], nodes, valid, p, G, S.eps2, g, (t & 63) - g, ax, ay, az);
   walk_row_tail(valid, g, body, p, ax, ay, az, posm, vel, acc, dt, stage, (float *)s_term[group], S.off, next_size, pos_sorted, place);
 }
 
@@ -567,7 +579,7 @@ __global__ __launch_bounds__(kB) void bh_small_leaf_boxes_kernel(SmallTree T, in
 // (Fetching the NEXT node of the preorder while a node is looked at — the walk goes there whenever it descends or the node is a
 // leaf, two steps in three — was tried in round 4: slower at every size, N = 32768 200 us a frame against 185, 65536 213 / 197,
 // 2^18 316 / 284, 2^20 843 / 710.)
-template <bool TWO>
+template <bool TWO, bool SOFT>
 __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *__restrict__ posm, float4 *__restrict__ vel,
                                                           float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                           unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
@@ -608,7 +620,7 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
     const bool take = leaf || d2 >= s_thr[(w >> kLevelShift) & 63u];
     if (take && d2 != 0.f) {
       float tx, ty, tz;
-      force_term(cm.x, cm.y, cm.z, cm.w, p, G, tx, ty, tz);
+      force_term<SOFT>(cm.x, cm.y, cm.z, cm.w, p, G, S.eps2, tx, ty, tz);
       ax = ax + tx; ay = ay + ty; az = az + tz;
     }
     node = (take || d2 == 0.f) ? past : node + 1;
@@ -630,7 +642,7 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
     const unsigned int w_next = T.meta[fetch];
     if (take && d2 != 0.f) {
       float tx, ty, tz;
-      force_term(cm.x, cm.y, cm.z, cm.w, p, G, tx, ty, tz);
+      force_term<SOFT>(cm.x, cm.y, cm.z, cm.w, p, G, S.eps2, tx, ty, tz);
       ax = ax + tx; ay = ay + ty; az = az + tz;
     }
     cm = cm_next; w = w_next; node = next;
@@ -664,7 +676,7 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
     HB = *(const uint2 *)((const char *)T.hop + (fetch << 3));                                                                        \
     if (take && d2 != 0.f) {                                                                                                           \
       float tx, ty, tz;                                                                                                                \
-      force_term(CA.x, CA.y, CA.z, CA.w, p, G, tx, ty, tz);                                                                            \
+      force_term<SOFT>(CA.x, CA.y, CA.z, CA.w, p, G, S.eps2, tx, ty, tz);                                                              \
       ax = ax + tx; ay = ay + ty; az = az + tz;                                                                                        \
     }                                                                                                                                  \
     node = next;                                                                                                                       \
@@ -691,8 +703,22 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
 }
 
 
-template __global__ void bh_walk_lane_kernel<false>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *, unsigned int *, float4 *, WalkSlice);
-template __global__ void bh_walk_lane_kernel<true>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *, unsigned int *, float4 *, WalkSlice);
+#define BH_WALK_KERNELS(SOFT)                                                                                                          \
+  template __global__ void bh_walk_compact_kernel<SOFT>(SmallTree, float4 *, float4 *, float4 *, int, float, double, float, float *,  \
+                                                        WalkSlice);                                                                  \
+  template __global__ void bh_walk_wave_compact_kernel<SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *,   \
+                                                             WalkSlice);                                                             \
+  template __global__ void bh_walk_wave_rows_kernel<SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *,      \
+                                                          unsigned int *, float4 *, WalkSlice);                                      \
+  template __global__ void bh_walk_rows_kernel<SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *,           \
+                                                     unsigned int *, float4 *, WalkSlice);                                           \
+  template __global__ void bh_walk_lane_kernel<false, SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *,    \
+                                                            unsigned int *, float4 *, WalkSlice);                                    \
+  template __global__ void bh_walk_lane_kernel<true, SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float *,     \
+                                                           unsigned int *, float4 *, WalkSlice);
+BH_WALK_KERNELS(false)
+BH_WALK_KERNELS(true)
+#undef BH_WALK_KERNELS
 
 }  // namespace bh
 }  // namespace nbody

@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Compare the instruction streams of the kernels two builds have in common, from the gfx950 code objects of their objects.
+
+A kernel of the NEW object whose last template argument is `false` is paired with the OLD kernel of the same name without that
+argument (bh_walk_rows_kernel<false> with bh_walk_rows_kernel, bh_walk_lane_kernel<true, false> with bh_walk_lane_kernel<true>), so
+that a kernel that has gained a compile-time switch can be checked to be, in its `false` form, the kernel it was.  Addresses,
+encodings, comments and the padding behind a function are dropped; branch offsets are relative, so identical code compares equal
+wherever it was placed.
+
+    python3 tools/isa_compare.py OLD.o NEW.o [--only SUBSTRING]     # exit code 1 if a pair differs or a kernel has no partner
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_hazards import LLVM, code_object   # noqa: E402
+
+
+def kernels(obj, workdir):
+    """{demangled function name: [instruction lines]} of the object's code object."""
+    co = code_object(obj, workdir)
+    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "-C", "--no-show-raw-insn", "--no-leading-addr", co], check=True,
+                         capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for ln in dis.splitlines():
+        m = re.match(r"^<(.+)>:$", ln.strip())
+        if m:
+            cur = m.group(1)
+            out[cur] = []
+            continue
+        code = ln.split("//")[0].strip()
+        if cur is not None and code:
+            out[cur].append(" ".join(code.split()))
+    for ins in out.values():                                     # the padding up to the next function's alignment
+        while ins and ins[-1] in ("s_nop 0", "..."):
+            ins.pop()
+    return out
+
+
+def base(name):
+    """(name without return type and parameters, template arguments or None)"""
+    name = name.split("(")[0]
+    name = name.split(" ")[-1] if not name.endswith(">") else name[name.rfind(" ", 0, name.find("<")) + 1:]
+    if name.endswith(">"):
+        i = name.find("<")
+        return name[:i], [a.strip() for a in name[i + 1:-1].split(",")]
+    return name, None
+
+
+def key_new(name):
+    b, args = base(name)
+    if args is None or args[-1] != "false":
+        return None
+    return b + ("<" + ", ".join(args[:-1]) + ">" if len(args) > 1 else "")
+
+
+def key_old(name):
+    b, args = base(name)
+    return b + ("<" + ", ".join(args) + ">" if args else "")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--only", default="", help="compare the kernels whose name holds this")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as t_old, tempfile.TemporaryDirectory() as t_new:
+        old = {key_old(k): v for k, v in kernels(a.old, t_old).items() if a.only in k}
+        new = {}
+        for k, v in kernels(a.new, t_new).items():
+            if a.only in k and key_new(k) is not None:
+                new[key_new(k)] = v
+            elif a.only in k and base(k)[1] is None:
+                new[key_old(k)] = v
+    bad = 0
+    for k in sorted(set(old) | set(new)):
+        if k not in old or k not in new:
+            print(f"{k}: only in the {'old' if k in old else 'new'} object")
+            bad += 1
+            continue
+        same = old[k] == new[k]
+        print(f"{k}: {len(old[k])} / {len(new[k])} instructions, {'identical' if same else 'DIFFERENT'}")
+        bad += not same
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
