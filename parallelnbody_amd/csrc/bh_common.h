@@ -377,10 +377,10 @@ constexpr int kWarmMu = 224;               // places of the previous order per b
                                            // wanders by a few dozen — almost always fit a padded bucket of 256 in the second kernel (512 otherwise)
 constexpr int kWarmCap = 384;              // slots per bucket
 constexpr int kWarmWin = 64;               // boundaries a workgroup keeps in LDS
-constexpr int kStatusRetry = 3;            // header word 3: the frame was given up by the warm sort; queue it again with the cold one
-constexpr int kStatusUnsorted = 4;         // ... a COLD sort left keys out of order: an internal error, reported (never seen; bh_lcp_scan_kernel's guard)
+constexpr int kStatusRetry = kBhStatusRetry;       // header word 3: the frame was given up by the warm sort; queue it again with the cold one
+constexpr int kStatusUnsorted = kBhStatusUnsorted; // ... a COLD sort left keys out of order: an internal error, reported (never seen; bh_lcp_scan_kernel's guard)
 constexpr int kStatusDeep = kBhStatusDeep;            // ... a deep context's frame has bodies below level 42: built again with its deep clusters resolved (bh_deep_frame)
-constexpr int kStatusDeepRun = 6;          // ... a deep frame's cell of level 42 holds more bodies than kDeepRunMax (refused)
+constexpr int kStatusDeepRun = kBhStatusDeepRun;   // ... a deep frame's cell of level 42 holds more bodies than kDeepRunMax (refused)
 constexpr int kBsP = 512;                  // the padded bucket at most
 
 struct RadixPass {

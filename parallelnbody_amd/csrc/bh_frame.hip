@@ -451,7 +451,7 @@ float bh_last_size(const BhState *b) { float f; unsigned int u = (unsigned int)b
 // behind it leave the state untouched).  A refusal is cleared here, so that the next call starts afresh.
 // *status = kStatusRetry (3): the sort from the previous order gave a frame up (a bucket ran over): that frame and the ones queued
 // behind it did nothing and are the caller's to queue again — it knows what they were, has their event pairs, and on several devices
-// the collectives that go between them (capi.hip bh_finish, multi.hip); the state is ready for the first of them to sort cold.
+// the collectives that go between them (bh_driver.h bh_drive: bh_driver.hip, multi.hip); the state is ready for the first of them to sort cold.
 hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames) {
   BH_TRY(hipStreamSynchronize(s));                              // (the frames' walks have left the verdict in page-locked memory: hand_verdict)
   memcpy(b->h_counters, b->h_verdict, sizeof(int) * 8);

@@ -1,118 +1,19 @@
 // C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches.  Host C++ over the
 // HIP runtime; no torch types, no exceptions across the boundary (the entry points that allocate host memory catch
 // std::bad_alloc), no CPU fallback.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
-#include <utility>
-#include <vector>
 
-#include "../../include/nbody.h"
-#include "kernels.h"
-#include "multi.h"
-#include "sym_plan.h"
+#include "bh_driver.h"
+#include "ctx.h"
 
 namespace {
 
-thread_local std::string g_create_error;
-
-struct EventPair { hipEvent_t a, b; bool counts = true; };   // counts: the interval is a whole pass (not the first go of two)
-
-struct KernelTimer {
-  std::vector<EventPair> pending;   // recorded, not yet read
-  std::vector<EventPair> pool;      // free
-  double total_ms = 0.0;
-  int64_t launches = 0;
-};
-
-}  // namespace
-
-struct nbody_ctx {
-  nbody::Multi *multi = nullptr;   // nbody_create_multi: this context is a front for one context per device (multi.h)
-  nbody_params p;
-  size_t elem;                 // bytes per float4/double4 element
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  void *posm = nullptr, *vel = nullptr, *acc = nullptr, *accp = nullptr;
-  void *posm_alt = nullptr;    // small systems: second position buffer of the one-launch step (swapped with posm)
-  bool own_posm = false, own_vel = false, own_acc = false;
-  void *d_stage = nullptr, *h_stage = nullptr;   // renderer hand-off staging (device repack target, pinned mirror)
-  size_t stage_bytes = 0;
-  void *scratch = nullptr;     // 64 B device scratch (bounds bits, energy sums)
-  void *h_scratch = nullptr;   // pinned mirror
-  void *energy_part = nullptr; // nbody_energy: one pair of doubles per workgroup, folded in a fixed order
-  int j_split = 1, j_chunk = 0, ipt = 1, tile = 256;
-  int sym_np = 1;                        // register pairs per lane of the symmetric kernel
-  std::vector<std::pair<char *, size_t>> pinned;   // caller memory page-locked by nbody_pin_host_buffer
-  int wave = 0;                // block kernel: register pairs of bodies per workgroup (0 = tile / symmetric kernels)
-  int bh_word = 0;             // larger Barnes-Hut systems: which of the two Size words (scratch + 40, + 44) the next frame uses
-  int tick_word = 0;           // nbody_tick on the one-launch step: which of the two Size words (scratch + 32, + 36) is cleared and next
-  bool have_state = false;
-  double floor_eps2 = -1.0;    // NBODY_ZERO_FLOOR: eps^2 floor for the current masses (< 0 = not yet computed)
-  // symmetric algorithm (kernels_sym.hip, kernels_sym64.hip; plan: sym_plan.h)
-  bool sym = false;
-  int sym_bi = 0, sym_pad = 0, sym_items_n = 0, sym_nsrc = 1, sym_slots = 0, sym_min_sub = 0;
-  int sym_n_local = 0;                   // items [0, sym_n_local): strips inside the own slice (sym_plan.h)
-  std::vector<int> sym_phase_item0;      // pool phases of the plan: phase p = items [p], [p + 1]) (one phase unless the pool had to be shared)
-  int sym_n_gran = 0;
-  double sym_k = 0.0;
-  bool sym_even = false;                 // the plan is an even-share plan (sym_plan.h)
-  size_t sym_pool_elems = 0;
-  nbody::SymPlan *plan = nullptr;                  // host copy, dropped once uploaded
-  void *sym_pool = nullptr, *sym_items = nullptr, *sym_iptr = nullptr, *sym_ioff = nullptr, *sym_jptr = nullptr,
-       *sym_joff = nullptr, *sym_posg = nullptr;
-  void *sym_send = nullptr, *sym_recv = nullptr;   // exchange buffers (recv == send when the context owns all bodies)
-  void *sym_dup_table = nullptr;                   // coincident-body detector (hash slots + flag)
-  int sym_dup_slots = 0;
-  // fused single-device fp32 stepping: the update prepares the next pass (posg + the OTHER detector table)
-  void *sym_dup_table2 = nullptr;
-  int sym_dup_cur = 0;                             // which of the two tables holds the verdict on the current positions
-  bool sym_posg_valid = false;                     // posg (and that table) describe the current positions
-  bool posm_escaped = false;                       // the caller holds / owns the position buffer: it may change behind our back
-  // equal-mass kernels: device word the preparation kernel (fp64: mass_check_kernel) raises when two masses differ (sticky; the host resets it
-  // with every state it uploads) and what the host itself saw in that state (1 all equal, 0 not, -1 never saw one)
-  void *sym_general = nullptr;
-  int masses_equal = -1;
-  bool own_send = false, own_recv = false;
-  bool step_open = false;      // nbody_step_begin done, nbody_step_end pending
-  bool step_local = false;     // nbody_step_begin_local done, nbody_step_begin_remote pending
-  int64_t steps_done = 0;      // updates applied since the state was set (saved in checkpoints)
-  // Barnes-Hut mode (bh_frame.hip, kernels_bh_*.hip)
-  float theta = 0.0f;
-  nbody::BhState *bh = nullptr;
-  int bh_max_depth = 42;       // the deepest tree a frame may build (nbody_set_bh_max_depth): a setting, not state (checkpoints do not keep it)
-  void *bh_acc = nullptr;      // [i_count] float4: the walk's output, summed (j_split = 1) by update_kernel
-  struct { float dt = 0.f; float *stage = nullptr; int queued = 0; bool timed = false; } bh_batch;   // what bh_enqueue queued since the last bh_finish
-  KernelTimer timers[2];
-  int clk_items = 0;                   // NBODY_SYM_ITEM_CLOCKS: work items with stamps of their own behind the eight clock words
-  unsigned long long *clk = nullptr;   // time_kernels: {shader-clock cycles, reference-clock ticks} summed over the force kernels' workgroups (pk_common.h)
-  int wall_khz = 0, cus = 0;           // hipDeviceAttributeWallClockRate, compute units
-  std::string err;
-};
-
-namespace {
-
-int fail(nbody_ctx *c, int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf; else g_create_error = buf;
-  return code;
-}
-
-int run_update(nbody_ctx *c, float dt);   // (defined below; part_bh_queue_frame comes first)
-int queue_forces_bh(nbody_ctx *c, bool diagnostic);
+using nbody::EventPair; using nbody::fail; using nbody::g_create_error; using nbody::timed_launch; using nbody::use_device;
 
 // A call on a multi-device context is answered by its Multi; its message becomes the context's.
 int multi_rc(nbody_ctx *c, int rc) {
@@ -121,20 +22,6 @@ int multi_rc(nbody_ctx *c, int rc) {
 }
 int multi_unsupported(nbody_ctx *c, const char *who) {
   return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not available on a multi-device context (nbody_create_multi); use one context per device", who);
-}
-
-#define HIP_TRY(c, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail((c), NBODY_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-// One caller thread may hold contexts on several devices (nbody_create_multi does): every entry point that allocates,
-// launches, copies or records makes its context's device the current one first.
-int use_device(nbody_ctx *c) {
-  if (c->multi) return NBODY_OK;
-  HIP_TRY(c, hipSetDevice(c->p.device));
-  return NBODY_OK;
 }
 
 // Up to N = 16384 a workgroup owns a few bodies and spreads the j range over its lanes (forces_block_pk_kernel,
@@ -455,41 +342,6 @@ nbody::ForceLaunch make_launch(const nbody_ctx *c) {
   return L;
 }
 
-int timer_begin(nbody_ctx *c, int which, EventPair *ev) {
-  KernelTimer &t = c->timers[which];
-  if (t.pool.empty()) {
-    EventPair e;
-    HIP_TRY(c, hipEventCreate(&e.a));
-    HIP_TRY(c, hipEventCreate(&e.b));
-    t.pool.push_back(e);
-  }
-  *ev = t.pool.back();
-  t.pool.pop_back();
-  HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-  return NBODY_OK;
-}
-
-int timer_end(nbody_ctx *c, int which, const EventPair &ev, bool counts = true) {
-  HIP_TRY(c, hipEventRecord(ev.b, c->stream));
-  c->timers[which].pending.push_back(ev);
-  c->timers[which].pending.back().counts = counts;
-  return NBODY_OK;
-}
-
-int timer_drain(nbody_ctx *c, int which) {
-  KernelTimer &t = c->timers[which];
-  for (const EventPair &e : t.pending) {
-    HIP_TRY(c, hipEventSynchronize(e.b));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
-    t.total_ms += ms;
-    t.launches += e.counts ? 1 : 0;
-    t.pool.push_back(e);
-  }
-  t.pending.clear();
-  return NBODY_OK;
-}
-
 // NBODY_ZERO_FLOOR: the smallest eps^2 for which G*m_max*(eps^2)^(-3/2) stays below FLT_MAX/8.
 int ensure_floor(nbody_ctx *c) {
   if (c->p.zero_mode != NBODY_ZERO_FLOOR || c->p.eps > 0.0 || c->floor_eps2 > 0.0) return NBODY_OK;
@@ -507,189 +359,8 @@ int ensure_floor(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-// Barnes-Hut state of a context, on first use.
-int ensure_bh(nbody_ctx *c) {
-  if (c->p.precision != NBODY_PREC_F32)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "theta > 0 (Barnes-Hut) needs an fp32 context");
-  if (c->bh) return NBODY_OK;
-  // a context that owns a slice builds the whole tree from the replicated positions and walks its own bodies (bh_common.h, WalkSlice)
-  hipError_t e = nbody::bh_create(&c->bh, c->p.n_total, c->p.i_begin, c->p.i_count);
-  if (e == hipSuccess) e = hipMalloc(&c->bh_acc, (size_t)c->p.i_count * 16);
-  if (e != hipSuccess) {
-    nbody::bh_destroy(c->bh); c->bh = nullptr;
-    if (c->bh_acc) { (void)hipFree(c->bh_acc); c->bh_acc = nullptr; }
-    return fail(c, NBODY_ERR_HIP, "bh_create: %s", hipGetErrorString(e));
-  }
-  nbody::bh_set_div_mode(c->bh, c->p.bh_div_mode);
-  if (c->bh_max_depth != 42 && (e = nbody::bh_set_max_depth(c->bh, c->bh_max_depth)) != hipSuccess)
-    return fail(c, NBODY_ERR_HIP, "bh_set_max_depth: %s", hipGetErrorString(e));
-  if (c->posm_escaped) nbody::bh_positions_external(c->bh);
-  return NBODY_OK;
-}
-
-int bh_status_error(nbody_ctx *c, int status) {
-  if (status == 1 && c->bh_max_depth == 42) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut tree deeper than 42 levels: two bodies closer than Size/2^42 (the reference's Add would recurse without bound on coincident bodies)");
-  if (status == 1) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut tree deeper than %d levels: two bodies closer than Size/2^%d (the reference's Add would recurse without bound on coincident bodies)", c->bh_max_depth, c->bh_max_depth);
-  if (status == 6) return fail(c, NBODY_ERR_UNSUPPORTED, "Barnes-Hut: more than 64 bodies share one cell of level 42 (a deep context orders at most 64 bodies below level 42)");
-  if (status == 2) return fail(c, NBODY_ERR_NOMEM, "Barnes-Hut node pool exhausted");
-  if (status == 4) return fail(c, NBODY_ERR_STATE, "Barnes-Hut: the sorted path keys are out of order (an internal error of this library; the frame was not built and the state is what it was)");
-  return NBODY_OK;
-}
-
-// the Plummer softening of every theta > 0 walk: eps * eps in double, rounded once to fp32; 0 — eps == 0, or an eps whose square
-// rounds to 0 — walks with the reference's own term
-float bh_eps2(const nbody_ctx *c) { return (float)(c->p.eps * c->p.eps); }
-
-// a deep context: the frame bh_collect handed back (kStatusDeep), built again with its deep clusters resolved (one wait inside)
-int bh_enqueue_deep(nbody_ctx *c, float dt, float *stage) {
-  const bool timed = c->p.time_kernels != 0;
-  EventPair ev;
-  if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-  HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, bh_eps2(c), dt, 0, stage, c->stream));
-  if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
-  c->bh_batch.queued += 1;
-  return NBODY_OK;
-}
-
-// theta > 0: queue `nsteps` whole frames (tree, walk, update), nothing waits.
-int bh_enqueue(nbody_ctx *c, float dt, int nsteps, float *stage = nullptr) {
-  const bool timed = c->p.time_kernels != 0;
-  for (int s = 0; s < nsteps; ++s) {
-    EventPair ev;
-    if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-    HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, c->vel, c->acc, c->theta, c->p.G, bh_eps2(c), dt, 0, s == nsteps - 1 ? stage : nullptr, c->stream));
-    if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
-    // (small systems queue a whole call's frames at once and give none up: bound the number of live events; the larger systems'
-    // batches of 64 never get here, so the pairs of a given-up batch are still there to be taken back)
-    if (timed && nbody::bh_is_small(c->bh) && c->timers[NBODY_KERNEL_FORCES].pending.size() >= 1024) { int rc = timer_drain(c, NBODY_KERNEL_FORCES); if (rc) return rc; }
-  }
-  c->bh_batch.dt = dt; c->bh_batch.stage = stage; c->bh_batch.queued += nsteps; c->bh_batch.timed = timed;
-  c->sym_posg_valid = false;     // bodies move without the fused all-pairs update's preparation of the next pass
-  return NBODY_OK;
-}
-
-// The event pairs of the last `k` frames queued belong to frames that did nothing (the warm sort gave one up and the rest were queued
-// behind it): they are taken back, so that nbody_kernel_time counts every frame once — with the events around the run that built it.
-void timer_take_back(nbody_ctx *c, int which, int k) {
-  KernelTimer &t = c->timers[which];
-  for (; k > 0 && !t.pending.empty(); --k) { t.pool.push_back(t.pending.back()); t.pending.pop_back(); }
-}
-
-// ... and the one wait: the frames that were built count as steps; a refused frame (and all queued behind it) left the
-// state where it was.  Frames the sort from the previous order gave up (kernels_bh_sort.hip: a bucket ran over — the records were
-// replaced, the root box jumped) did nothing, nor did the frames queued behind them: they are queued again here, the first of them
-// with the cold sorts, inside event pairs of their own.
-int bh_finish(nbody_ctx *c) {
-  for (;;) {
-    int status = 0, frames = 0;
-    HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, &frames));
-    c->steps_done += frames;
-    const int left = c->bh_batch.queued - frames;
-    c->bh_batch.queued = 0;
-    if (status == nbody::kBhStatusDeep) {
-      // a deep context's frame with bodies below level 42: built again with its deep clusters resolved, the ones behind it queued again
-      if (c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, left);
-      if (int rc = bh_enqueue_deep(c, c->bh_batch.dt, left == 1 ? c->bh_batch.stage : nullptr)) return rc;
-      if (int rc = bh_enqueue(c, c->bh_batch.dt, left - 1, c->bh_batch.stage)) return rc;
-      continue;
-    }
-    if (status != 3) {
-      if (c->bh_batch.timed && c->timers[NBODY_KERNEL_FORCES].pending.size() >= 1024) { int rc = timer_drain(c, NBODY_KERNEL_FORCES); if (rc) return rc; }
-      return bh_status_error(c, status);
-    }
-    if (c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, left);
-    if (int rc = bh_enqueue(c, c->bh_batch.dt, left, c->bh_batch.stage)) return rc;
-  }
-}
-
-}  // namespace
-
-// ---- for multi.hip (declared in multi.h, not part of the C-ABI): one device's share of a theta > 0 step, in two halves, so that one
-// caller thread can queue every device's frames — and the all-gathers between them — before it waits for any of them.
-namespace nbody {
-int part_bh_queue_frame(nbody_ctx *c, float dt, bool diagnostic) {
-  if (int rc = use_device(c)) return rc;
-  if (int rc = ensure_bh(c)) return rc;
-  if (!(dt > 0.0f)) {                                           // accelerations only (nbody_compute_forces): walk into bh_acc, then the row fold
-    if (int rc = queue_forces_bh(c, diagnostic)) return rc;
-    return run_update(c, 0.0f);
-  }
-  return bh_enqueue(c, dt, 1);
-}
-// status: 0 all frames built; 1 / 2 refused (the error text is the context's); 3 the warm sort gave a frame up — the frames from
-// number *built on did nothing on this device (nor, the build being the same everywhere, on any other) and are the caller's to queue again
-int part_bh_collect(nbody_ctx *c, int *status, int *built) {
-  if (int rc = use_device(c)) return rc;
-  int st = 0, frames = 0;
-  HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &st, &frames));
-  *status = st; *built = frames;
-  if (c->bh_batch.queued > 0) c->steps_done += frames;         // (whole frames, not a diagnostic force pass)
-  if ((st == 3 || st == kBhStatusDeep) && c->bh_batch.timed) timer_take_back(c, NBODY_KERNEL_FORCES, c->bh_batch.queued - frames);
-  c->bh_batch.queued = 0;
-  if (st == 1 || st == 2 || st == 4 || st == 6) return bh_status_error(c, st);
-  return NBODY_OK;
-}
-// a deep context's frame handed back by part_bh_collect (status 5): built again on this device with its deep clusters resolved; the
-// caller collects it like any other frame
-int part_bh_queue_deep_frame(nbody_ctx *c, float dt, bool diagnostic) {
-  if (int rc = use_device(c)) return rc;
-  if (!(dt > 0.0f)) {
-    HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
-    return run_update(c, 0.0f);
-  }
-  return bh_enqueue_deep(c, dt, nullptr);
-}
-// the next tree's root centre (the previous tree's CoM, OctreeSearch.cpp:77-79) of a context that has built a tree: what a checkpoint keeps
-int part_bh_root(nbody_ctx *c, float out[3], int *has_root) {
-  *has_root = 0;
-  if (!c->bh) return NBODY_OK;
-  if (int rc = use_device(c)) return rc;
-  HIP_TRY(c, nbody::bh_get_root_com(c->bh, out, c->stream));
-  *has_root = 1;
-  return NBODY_OK;
-}
-}  // namespace nbody
-
-namespace {
-
-// Barnes-Hut force pass alone: ComputeCubeSize -> CreateOctree -> the walk, accelerations into bh_acc (run_update adds them up
-// and, for nbody_step_end, moves the bodies).  diagnostic: the pass belongs to no frame (nbody_compute_forces) and leaves the
-// next tree's root centre alone.
-int queue_forces_bh(nbody_ctx *c, bool diagnostic) {
-  { int rc = ensure_bh(c); if (rc) return rc; }
-  EventPair ev;
-  const bool timed = c->p.time_kernels != 0;
-  if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-  HIP_TRY(c, nbody::bh_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
-  if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
-  return NBODY_OK;
-}
-int run_forces_bh(nbody_ctx *c, bool diagnostic) {
-  for (;;) {
-    { int rc = queue_forces_bh(c, diagnostic); if (rc) return rc; }
-    int status = 0;
-    HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, nullptr));
-    if (status == nbody::kBhStatusDeep) {                      // a deep context: once more, with its deep clusters resolved
-      const bool timed = c->p.time_kernels != 0;                // (the timed pass is the one that did the work, not the attempt handed back)
-      if (timed) timer_take_back(c, NBODY_KERNEL_FORCES, 1);
-      EventPair ev;
-      if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
-      HIP_TRY(c, nbody::bh_deep_frame(c->bh, c->posm, nullptr, c->bh_acc, c->theta, c->p.G, bh_eps2(c), 0.0f, diagnostic ? 1 : 0, nullptr, c->stream));
-      if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev); if (rc) return rc; }
-      HIP_TRY(c, nbody::bh_collect(c->bh, c->stream, &status, nullptr));
-    }
-    if (status != 3) return bh_status_error(c, status);
-    if (c->p.time_kernels) timer_take_back(c, NBODY_KERNEL_FORCES, 1);   // given up by the warm sort: once more, with the cold sorts
-  }
-}
-
-// phase (SymLaunch::phase): 0 the whole pass; 1 / 2 the two goes of a sharded fp32 symmetric context (sym_two_goes)
-int run_forces(nbody_ctx *c, bool diagnostic = false, int phase = 0) {
-  if (c->theta > 0.0f) return run_forces_bh(c, diagnostic);
-  { int rc = ensure_floor(c); if (rc) return rc; }
-  EventPair ev;
-  const bool timed = c->p.time_kernels != 0;
-  if (timed) { int rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev); if (rc) return rc; }
+// the all-pairs force pass, queued.  phase (SymLaunch::phase): 0 the whole pass; 1 / 2 the two goes of a sharded fp32 symmetric context (sym_two_goes)
+int queue_forces(nbody_ctx *c, int phase) {
   if (c->sym) {
     nbody::SymLaunch L = make_sym_launch(c);
     L.phase = phase;
@@ -728,33 +399,29 @@ int run_forces(nbody_ctx *c, bool diagnostic = false, int phase = 0) {
   } else {
     HIP_TRY(c, nbody::launch_forces(make_launch(c), c->stream));
   }
-  if (timed) { int rc = timer_end(c, NBODY_KERNEL_FORCES, ev, phase != 1); if (rc) return rc; }   // two goes are ONE pass
-  // bound the number of live events on long untimed-drain runs
-  if (timed && c->timers[NBODY_KERNEL_FORCES].pending.size() >= 1024) return timer_drain(c, NBODY_KERNEL_FORCES);
   return NBODY_OK;
 }
 
+// one force pass; theta > 0: the Barnes-Hut walk into bh_acc, waited for (bh_driver.h; diagnostic: nbody_compute_forces' pass, part of no frame)
+int run_forces(nbody_ctx *c, bool diagnostic = false, int phase = 0) {
+  if (c->theta > 0.0f) return nbody::bh_run_forces(c, diagnostic);
+  { int rc = ensure_floor(c); if (rc) return rc; }
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&] { return queue_forces(c, phase); }, phase != 1);   // two goes are ONE pass
+}
+
 int run_update(nbody_ctx *c, float dt) {
-  EventPair ev;
-  const bool timed = c->p.time_kernels != 0;
-  if (timed) { int rc = timer_begin(c, NBODY_KERNEL_UPDATE, &ev); if (rc) return rc; }
-  if (c->theta > 0.0f) {
-    HIP_TRY(c, nbody::launch_update(c->p.precision, c->posm, c->vel, c->acc, c->bh_acc, c->p.i_begin, c->p.i_count, 1, dt, c->stream));
-    // bodies moved without the fused update's preparation of the next all-pairs pass: posg and the detector table are
-    // those of older positions (the next theta == 0 pass runs the preparation kernel again)
-    if (dt > 0.0f) c->sym_posg_valid = false;
-    if (dt > 0.0f && c->bh) nbody::bh_positions_changed(c->bh);   // ... and the next Barnes-Hut frame looks at the positions for its Size
-  } else if (c->sym) {
-    const nbody::SymLaunch L = make_sym_launch(c);
-    HIP_TRY(c, nbody::launch_update_sym(L, c->posm, c->vel, c->acc, c->p.i_begin, c->p.i_count, dt, c->stream));
-    if (L.fused) { c->sym_posg_valid = true; c->sym_dup_cur ^= 1; }   // the update wrote posg and the other table
-  }
-  else
-    HIP_TRY(c, nbody::launch_update(c->p.precision, c->posm, c->vel, c->acc, c->accp, c->p.i_begin, c->p.i_count,
-                                    c->j_split, dt, c->stream));
-  if (timed) { int rc = timer_end(c, NBODY_KERNEL_UPDATE, ev); if (rc) return rc; }
-  if (timed && c->timers[NBODY_KERNEL_UPDATE].pending.size() >= 1024) return timer_drain(c, NBODY_KERNEL_UPDATE);
-  return NBODY_OK;
+  if (c->theta > 0.0f) return nbody::bh_queue_update(c, dt);
+  return timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+    if (c->sym) {
+      const nbody::SymLaunch L = make_sym_launch(c);
+      HIP_TRY(c, nbody::launch_update_sym(L, c->posm, c->vel, c->acc, c->p.i_begin, c->p.i_count, dt, c->stream));
+      if (L.fused) { c->sym_posg_valid = true; c->sym_dup_cur ^= 1; }   // the update wrote posg and the other table
+    } else {
+      HIP_TRY(c, nbody::launch_update(c->p.precision, c->posm, c->vel, c->acc, c->accp, c->p.i_begin, c->p.i_count,
+                                      c->j_split, dt, c->stream));
+    }
+    return NBODY_OK;
+  });
 }
 
 template <typename SRC, typename DST>
@@ -1112,7 +779,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->p.device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (KernelTimer &t : c->timers) {
+  for (nbody::KernelTimer &t : c->timers) {
     for (EventPair &e : t.pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (EventPair &e : t.pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   }
@@ -1398,12 +1065,11 @@ static int step_one_launch(nbody_ctx *c, float dt, void *stage, void *size_bits,
   int rc;
   if (!c->posm_alt) HIP_TRY(c, hipMalloc(&c->posm_alt, (size_t)c->p.n_total * c->elem));
   if ((rc = ensure_floor(c))) return rc;
-  EventPair ev;
-  const bool timed = c->p.time_kernels != 0;
-  if (timed && (rc = timer_begin(c, NBODY_KERNEL_FORCES, &ev))) return rc;
-  HIP_TRY(c, nbody::launch_step_small(make_launch(c), c->posm_alt, c->vel, c->acc, dt, c->stream, stage, size_bits, size_zero));
-  if (timed && (rc = timer_end(c, NBODY_KERNEL_FORCES, ev))) return rc;
-  if (timed && c->timers[NBODY_KERNEL_FORCES].pending.size() >= 1024 && (rc = timer_drain(c, NBODY_KERNEL_FORCES))) return rc;
+  rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    HIP_TRY(c, nbody::launch_step_small(make_launch(c), c->posm_alt, c->vel, c->acc, dt, c->stream, stage, size_bits, size_zero));
+    return NBODY_OK;
+  });
+  if (rc) return rc;
   std::swap(c->posm, c->posm_alt);
   return NBODY_OK;
 }
@@ -1431,14 +1097,12 @@ int nbody_step(nbody_ctx *c, float dt, int32_t nsteps) {
     return fail(c, NBODY_ERR_STATE, "nbody_step: a sharded context advances one step per call (all-gather NBODY_BUF_POSM in between)");
   HIP_TRY(c, hipSetDevice(c->p.device));
   if (c->theta > 0.0f) {
-    if ((rc = ensure_bh(c))) return rc;
+    if ((rc = nbody::ensure_bh(c))) return rc;
     // every frame queued, one wait per call — the larger systems' in batches of 64: a frame their warm sort gives up takes the
-    // frames queued behind it along (bh_collect queues them again), and that should not be hundreds
+    // frames queued behind it along (bh_drive queues them again), and that should not be hundreds
     const int batch = nbody::bh_is_small(c->bh) ? nsteps : 64;
-    for (int done = 0; done < nsteps; done += batch) {
-      if ((rc = bh_enqueue(c, dt, std::min(batch, nsteps - done)))) return rc;
-      if ((rc = bh_finish(c))) return rc;
-    }
+    for (int done = 0; done < nsteps; done += batch)
+      if ((rc = nbody::bh_run_frames(c, dt, std::min(batch, nsteps - done), nullptr))) return rc;
     return NBODY_OK;
   }
   const bool one_launch = one_launch_ok(c);
@@ -1571,7 +1235,7 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
   // here and its verdict collected by the frame's one wait
   bool bh_frame = false;
   if (live && c->theta > 0.0f) {
-    if ((rc = ensure_bh(c))) return rc;
+    if ((rc = nbody::ensure_bh(c))) return rc;
     bh_frame = true;
   }
   const size_t ic = (size_t)c->p.i_count, bytes = ic * sizeof(nbody_particle);
@@ -1599,15 +1263,15 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
     return NBODY_OK;
   }
   bool bh_direct = false;
+  void *bh_stage = nullptr;
   if (bh_frame) {                                                // the walk writes the frame's records itself, Size rides with the verdict
     // ... straight into page-locked host memory: the caller's mirror if it is pinned, the staging buffer otherwise
-    void *stage = nullptr;
     if (aos) {
       if ((rc = ensure_stage(c, bytes))) return rc;
       bh_direct = stride == sizeof(nbody_particle) && in_pinned(c, aos, bytes);
-      HIP_TRY(c, hipHostGetDevicePointer(&stage, bh_direct ? aos : c->h_stage, 0));
+      HIP_TRY(c, hipHostGetDevicePointer(&bh_stage, bh_direct ? aos : c->h_stage, 0));
     }
-    if ((rc = bh_enqueue(c, dt, 1, (float *)stage))) return rc;
+    if ((rc = nbody::bh_queue_frame(c, dt, false, false, (float *)bh_stage))) return rc;
   } else if (live && size) {                                     // .cpp:26, 47-56: bounds of the positions BEFORE the step
     HIP_TRY(c, hipMemsetAsync(c->scratch, 0, 4, c->stream));
     HIP_TRY(c, nbody::launch_bounds(c->p.precision, c->posm, c->p.i_begin, c->p.i_count, (unsigned int *)c->scratch, c->stream));
@@ -1624,7 +1288,7 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
     if (!bh_frame) HIP_TRY(c, hipMemcpyAsync(direct ? aos : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
   }
   int frame_rc = NBODY_OK;
-  if (bh_frame) frame_rc = bh_finish(c);                         // the frame's one wait
+  if (bh_frame) frame_rc = nbody::bh_run_frames(c, dt, 1, (float *)bh_stage, true);   // the frame's one wait (and, given up or handed back, once more)
   else HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (bh_frame && frame_rc != NBODY_OK && aos) {                 // a refused frame wrote no records: deliver the untouched state
     HIP_TRY(c, nbody::launch_pack_particles(c->p.precision, c->posm, c->vel, c->acc, (float *)c->d_stage, c->p.i_begin,
@@ -1783,7 +1447,7 @@ int nbody_load_checkpoint(nbody_ctx *c, const char *path, int64_t *steps_done) t
   if (c->p.precision == NBODY_PREC_F32) {
     c->theta = h.theta;
     if (h.has_root || c->bh) {
-      { const int rc2 = ensure_bh(c); if (rc2) return rc2; }
+      { const int rc2 = nbody::ensure_bh(c); if (rc2) return rc2; }
       const float zero[3] = {0.f, 0.f, 0.f};
       HIP_TRY(c, nbody::bh_set_root_com(c->bh, h.has_root ? h.root_com : zero, c->stream));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1826,7 +1490,7 @@ int nbody_set_bh_max_depth(nbody_ctx *c, int32_t levels) {
     const hipError_t e = nbody::bh_set_max_depth(c->bh, levels);
     if (e != hipSuccess) return fail(c, NBODY_ERR_HIP, "nbody_set_bh_max_depth: %s", hipGetErrorString(e));
   }
-  c->bh_max_depth = levels;    // (a context without a tree yet takes it when its first theta > 0 frame creates one: ensure_bh)
+  c->bh_max_depth = levels;    // (a context without a tree yet takes it when its first theta > 0 frame creates one: bh_driver.hip ensure_bh)
   return NBODY_OK;
 }
 
@@ -1930,7 +1594,7 @@ int nbody_kernel_time(nbody_ctx *c, int32_t which, double *total_ms, int64_t *la
   if (!c || which < 0 || which > 1) return NBODY_ERR_INVALID;
   if (c->multi) return multi_rc(c, nbody::multi_kernel_time(c->multi, which, total_ms, launches));
   if (int rc0 = use_device(c)) return rc0;
-  int rc = timer_drain(c, which);
+  int rc = nbody::timer_drain(c, which);
   if (rc) return rc;
   if (total_ms) *total_ms = c->timers[which].total_ms;
   if (launches) *launches = c->timers[which].launches;
@@ -1942,7 +1606,7 @@ int nbody_kernel_time_reset(nbody_ctx *c) {
   if (c->multi) return multi_rc(c, nbody::multi_kernel_time_reset(c->multi));
   if (int rc0 = use_device(c)) return rc0;
   for (int w = 0; w < 2; ++w) {
-    int rc = timer_drain(c, w);
+    int rc = nbody::timer_drain(c, w);
     if (rc) return rc;
     c->timers[w].total_ms = 0.0;
     c->timers[w].launches = 0;

@@ -1,0 +1,175 @@
+// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, bh_driver.hip) share: error
+// texts, the device made current, the kernel timers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/nbody.h"
+#include "kernels.h"
+#include "multi.h"
+#include "sym_plan.h"
+
+namespace nbody {
+
+struct EventPair { hipEvent_t a, b; bool counts = true; };   // counts: the interval is a whole pass (not the first go of two)
+
+struct KernelTimer {
+  std::vector<EventPair> pending;   // recorded, not yet read
+  std::vector<EventPair> pool;      // free
+  double total_ms = 0.0;
+  int64_t launches = 0;
+};
+
+}  // namespace nbody
+
+struct nbody_ctx {
+  nbody::Multi *multi = nullptr;   // nbody_create_multi: this context is a front for one context per device (multi.h)
+  nbody_params p;
+  size_t elem;                 // bytes per float4/double4 element
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  void *posm = nullptr, *vel = nullptr, *acc = nullptr, *accp = nullptr;
+  void *posm_alt = nullptr;    // small systems: second position buffer of the one-launch step (swapped with posm)
+  bool own_posm = false, own_vel = false, own_acc = false;
+  void *d_stage = nullptr, *h_stage = nullptr;   // renderer hand-off staging (device repack target, pinned mirror)
+  size_t stage_bytes = 0;
+  void *scratch = nullptr;     // 64 B device scratch (bounds bits, energy sums)
+  void *h_scratch = nullptr;   // pinned mirror
+  void *energy_part = nullptr; // nbody_energy: one pair of doubles per workgroup, folded in a fixed order
+  int j_split = 1, j_chunk = 0, ipt = 1, tile = 256;
+  int sym_np = 1;                        // register pairs per lane of the symmetric kernel
+  std::vector<std::pair<char *, size_t>> pinned;   // caller memory page-locked by nbody_pin_host_buffer
+  int wave = 0;                // block kernel: register pairs of bodies per workgroup (0 = tile / symmetric kernels)
+  int bh_word = 0;             // larger Barnes-Hut systems: which of the two Size words (scratch + 40, + 44) the next frame uses
+  int tick_word = 0;           // nbody_tick on the one-launch step: which of the two Size words (scratch + 32, + 36) is cleared and next
+  bool have_state = false;
+  double floor_eps2 = -1.0;    // NBODY_ZERO_FLOOR: eps^2 floor for the current masses (< 0 = not yet computed)
+  // symmetric algorithm (kernels_sym.hip, kernels_sym64.hip; plan: sym_plan.h)
+  bool sym = false;
+  int sym_bi = 0, sym_pad = 0, sym_items_n = 0, sym_nsrc = 1, sym_slots = 0, sym_min_sub = 0;
+  int sym_n_local = 0;                   // items [0, sym_n_local): strips inside the own slice (sym_plan.h)
+  std::vector<int> sym_phase_item0;      // pool phases of the plan: phase p = items [p], [p + 1]) (one phase unless the pool had to be shared)
+  int sym_n_gran = 0;
+  double sym_k = 0.0;
+  bool sym_even = false;                 // the plan is an even-share plan (sym_plan.h)
+  size_t sym_pool_elems = 0;
+  nbody::SymPlan *plan = nullptr;                  // host copy, dropped once uploaded
+  void *sym_pool = nullptr, *sym_items = nullptr, *sym_iptr = nullptr, *sym_ioff = nullptr, *sym_jptr = nullptr,
+       *sym_joff = nullptr, *sym_posg = nullptr;
+  void *sym_send = nullptr, *sym_recv = nullptr;   // exchange buffers (recv == send when the context owns all bodies)
+  void *sym_dup_table = nullptr;                   // coincident-body detector (hash slots + flag)
+  int sym_dup_slots = 0;
+  // fused single-device fp32 stepping: the update prepares the next pass (posg + the OTHER detector table)
+  void *sym_dup_table2 = nullptr;
+  int sym_dup_cur = 0;                             // which of the two tables holds the verdict on the current positions
+  bool sym_posg_valid = false;                     // posg (and that table) describe the current positions
+  bool posm_escaped = false;                       // the caller holds / owns the position buffer: it may change behind our back
+  // equal-mass kernels: device word the preparation kernel (fp64: mass_check_kernel) raises when two masses differ (sticky; the host resets it
+  // with every state it uploads) and what the host itself saw in that state (1 all equal, 0 not, -1 never saw one)
+  void *sym_general = nullptr;
+  int masses_equal = -1;
+  bool own_send = false, own_recv = false;
+  bool step_open = false;      // nbody_step_begin done, nbody_step_end pending
+  bool step_local = false;     // nbody_step_begin_local done, nbody_step_begin_remote pending
+  int64_t steps_done = 0;      // updates applied since the state was set (saved in checkpoints)
+  // Barnes-Hut mode (bh_frame.hip, kernels_bh_*.hip; driven by bh_driver.hip)
+  float theta = 0.0f;
+  nbody::BhState *bh = nullptr;
+  int bh_max_depth = 42;       // the deepest tree a frame may build (nbody_set_bh_max_depth): a setting, not state (checkpoints do not keep it)
+  void *bh_acc = nullptr;      // [i_count] float4: the walk's output, summed (j_split = 1) by update_kernel
+  struct { int queued = 0; bool whole = false; } bh_batch;   // what bh_queue_frame queued since the last bh_collect_frames (whole: frames, not a force-only pass)
+  nbody::KernelTimer timers[2];
+  int clk_items = 0;                   // NBODY_SYM_ITEM_CLOCKS: work items with stamps of their own behind the eight clock words
+  unsigned long long *clk = nullptr;   // time_kernels: {shader-clock cycles, reference-clock ticks} summed over the force kernels' workgroups (pk_common.h)
+  int wall_khz = 0, cus = 0;           // hipDeviceAttributeWallClockRate, compute units
+  std::string err;
+};
+
+namespace nbody {
+
+inline thread_local std::string g_create_error;   // what nbody_last_error(nullptr) reports: a failed creation has no context to keep it
+
+inline int fail(nbody_ctx *c, int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (c) c->err = buf; else g_create_error = buf;
+  return code;
+}
+
+#define HIP_TRY(c, expr)                                                                         \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return nbody::fail((c), NBODY_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// One caller thread may hold contexts on several devices (nbody_create_multi does): every entry point that allocates,
+// launches, copies or records makes its context's device the current one first.
+inline int use_device(nbody_ctx *c) {
+  if (c->multi) return NBODY_OK;
+  HIP_TRY(c, hipSetDevice(c->p.device));
+  return NBODY_OK;
+}
+
+// ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
+constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain
+
+inline int timer_drain(nbody_ctx *c, int which) {
+  KernelTimer &t = c->timers[which];
+  for (const EventPair &e : t.pending) {
+    HIP_TRY(c, hipEventSynchronize(e.b));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
+    t.total_ms += ms;
+    t.launches += e.counts ? 1 : 0;
+    t.pool.push_back(e);
+  }
+  t.pending.clear();
+  return NBODY_OK;
+}
+
+// bound the number of live events on long runs that never read the timer
+inline int timer_drain_at_cap(nbody_ctx *c, int which) {
+  return c->timers[which].pending.size() >= kTimerPendingCap ? timer_drain(c, which) : NBODY_OK;
+}
+
+// The event pairs of the last `k` passes queued belong to passes that did nothing (a Barnes-Hut frame given up or handed back, and
+// the ones queued behind it): they are taken back, so that nbody_kernel_time counts every pass once — with the events around the
+// run that did the work.
+inline void timer_take_back(nbody_ctx *c, int which, int k) {
+  KernelTimer &t = c->timers[which];
+  for (; k > 0 && !t.pending.empty(); --k) { t.pool.push_back(t.pending.back()); t.pending.pop_back(); }
+}
+
+// launch() — a callable that queues one pass on c->stream and returns an NBODY_ code — inside an event pair of timer `which` when the
+// context times its kernels, bare otherwise.  counts: the interval is a whole pass.  may_drain: the pending list may be read once it
+// reaches the cap; a caller whose passes may still be taken back (a Barnes-Hut batch in flight) defers that to its collect.
+template <typename Launch>
+int timed_launch(nbody_ctx *c, int which, Launch &&launch, bool counts = true, bool may_drain = true) {
+  if (!c->p.time_kernels) return launch();
+  KernelTimer &t = c->timers[which];
+  if (t.pool.empty()) {
+    EventPair e;
+    HIP_TRY(c, hipEventCreate(&e.a));
+    HIP_TRY(c, hipEventCreate(&e.b));
+    t.pool.push_back(e);
+  }
+  EventPair ev = t.pool.back();
+  t.pool.pop_back();
+  HIP_TRY(c, hipEventRecord(ev.a, c->stream));
+  if (int rc = launch()) return rc;
+  HIP_TRY(c, hipEventRecord(ev.b, c->stream));
+  ev.counts = counts;
+  t.pending.push_back(ev);
+  return may_drain ? timer_drain_at_cap(c, which) : NBODY_OK;
+}
+
+}  // namespace nbody

@@ -142,20 +142,32 @@ hipError_t bh_reset_root(BhState *b, hipStream_t s);          // previous CoM :=
 // Octree::ComputeForces(body, theta) of every body and — with dt > 0 — the Tick's update of (posm, vel) in place, QUEUED on the
 // stream: nothing waits for the host (small systems, bh_is_small: two launches; larger ones up to 2^20 bodies: nine; beyond, one
 // wait inside for the deepest level).  bh_collect waits for the stream and reports the frames queued since the last collect:
-// *status 0 ok, 1 tree deeper than 42 levels, 2 node pool exhausted; a refused frame and everything queued behind it leave the
-// state untouched.  keep_root != 0: the next tree's root centre stays what it was (a diagnostic pass).
+// *status is one of the kBhStatus verdicts below; a refused frame (bh_refused) and everything queued behind it leave the state
+// untouched, a frame given up (kBhStatusRetry) or handed back (kBhStatusDeep) and the ones behind it did nothing and are the
+// caller's to queue again (bh_driver.h).  keep_root != 0: the next tree's root centre stays what it was (a diagnostic pass).
 // stage (optional): the walk also writes every body's FParticle record (10 floats, body order) there — the frame's mirror.
 // eps2: Plummer softening, (float)(eps * eps).  > 0: every accepted node's term is that of ds = sqrtf(d^2 + eps2) (the walks' SOFT
 // instantiations); where the walk goes is the reference's, on the unsoftened d.  0: the reference's term.
 bool bh_is_small(const BhState *b);
 hipError_t bh_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
                     float *stage, hipStream_t s);
-constexpr int kBhStatusDeep = 5;                          // bh_collect: a deep context's frame to build again with bh_deep_frame
+// bh_collect's verdicts (the frames' header word 3; bh_common.h's kStatus names are these)
+constexpr int kBhStatusOk = 0;
+constexpr int kBhStatusTooDeep = 1;                       // refused: the tree would be deeper than the context's limit (42 levels unless raised)
+constexpr int kBhStatusNodePool = 2;                      // refused: node pool exhausted
+constexpr int kBhStatusRetry = 3;                         // given up by the warm sort: queue it and the frames behind it again (the first sorts cold)
+constexpr int kBhStatusUnsorted = 4;                      // refused: a COLD sort left keys out of order (an internal error, never seen)
+constexpr int kBhStatusDeep = 5;                          // a deep context's frame handed back: build it again with bh_deep_frame, then the rest
+constexpr int kBhStatusDeepRun = 6;                       // refused: a deep frame's cell of level 42 holds more bodies than kDeepRunMax
+// refused: the state is untouched and the context carries an error text (bh_status_error)
+inline bool bh_refused(int status) {
+  return status == kBhStatusTooDeep || status == kBhStatusNodePool || status == kBhStatusUnsorted || status == kBhStatusDeepRun;
+}
 hipError_t bh_set_max_depth(BhState *b, int levels);      // the deepest tree answered, 42 .. 200 (above 42: deep frames, bh_deep_frame)
 hipError_t bh_deep_frame(BhState *b, void *posm, void *vel, void *acc, float theta, double G, float eps2, float dt, int keep_root,
-                         float *stage, hipStream_t s);    // the frame bh_collect handed back with *status 5, built with its deep clusters
+                         float *stage, hipStream_t s);    // the frame bh_collect handed back (kBhStatusDeep), built with its deep clusters
 float bh_last_size(const BhState *b);                         // Size of the last frame bh_collect has seen
-hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames);   // *status 3: queue the frames that were not built again
+hipError_t bh_collect(BhState *b, hipStream_t s, int *status, int *frames);   // *frames: how many were built
 hipError_t bh_debug_clocks(BhState *b, long long out[16 + 3 * 512], hipStream_t s);   // tuning builds only (tools/bh_phases.py)
 hipError_t bh_debug_poison(BhState *b, int kind, hipStream_t s);   // tests: kind 1 = the warm sort's bucket counts := 3 each (a fill that never ran)
 void bh_debug_sort_counts(const BhState *b, long long *warm_frames, long long *retries);   // frames sorted from the previous order; times frames were queued again

@@ -46,12 +46,4 @@ int multi_bh_stats(Multi *m, int32_t *nodes, int32_t *levels, float root_com[3])
 int multi_bh_leaf_boxes(Multi *m, float *boxes, size_t stride);
 int multi_bh_leaf_order(Multi *m, int32_t *order);
 int multi_bh_root(Multi *m, float root_com[3], int *has_root);
-
-// One device's share of a theta > 0 step in two halves (capi.hip; not part of the C-ABI): queue a frame — dt > 0: tree, walk of the
-// own slice, kick-drift; otherwise the accelerations alone — and, later, the one wait with the frames' verdict.
-int part_bh_queue_frame(nbody_ctx *c, float dt, bool diagnostic);
-int part_bh_collect(nbody_ctx *c, int *status, int *built);
-int part_bh_queue_deep_frame(nbody_ctx *c, float dt, bool diagnostic);   // after part_bh_collect's status 5
-int part_bh_root(nbody_ctx *c, float out[3], int *has_root);
-
 }  // namespace nbody

@@ -1,6 +1,8 @@
 // Single-process multi-GPU engine (see multi.h): sub-contexts driven through the public C-ABI, RCCL over xGMI between them.
 #include "multi.h"
 
+#include "bh_driver.h"
+
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and enums only: the functions are resolved with dlsym
@@ -307,23 +309,6 @@ int multi_set_state_soa_f64(Multi *m, const double *posm4, const double *vel4, i
   return NBODY_OK;
 }
 
-// One Tick body over all devices (OctreeSearch.cpp:27-31): everything is queued on the devices' streams, nothing waits
-// for the host.
-static int multi_bh_frames(Multi *m, float dt, int nframes, bool diagnostic, int *built_out);
-
-int multi_forces(Multi *m, float dt) {
-  if (m->theta > 0.0f) { int built = 0; return multi_bh_frames(m, dt, 1, !(dt > 0.0f), &built); }
-  // the strips inside every device's own slice need no other device's positions: they run while the last step's
-  // all-gather is still in flight; the rest of the pass is ordered behind it (nbody_step_begin_local / _remote)
-  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_begin_local(m->part[(size_t)k]), "force pass (own slice)");
-  { const int rc = wait_gather(m); if (rc) return rc; }
-  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_begin_remote(m->part[(size_t)k]), "force pass");
-  { const int rc = exchange_sums(m); if (rc) return rc; }
-  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_end(m->part[(size_t)k], dt), "update");
-  if (dt > 0.0f) return gather_positions(m);
-  return NBODY_OK;
-}
-
 // ---- theta > 0 -----------------------------------------------------------------------------------------------------------------
 // The reference's frame (OctreeSearch.cpp:25-31 with CreateOctree, .cpp:74-89) over several devices: the tree is ONE tree (.cpp:79-81)
 // and each body's walk (.cpp:83-86) reads it and writes that body alone — so every device builds the whole tree from its copy of the
@@ -336,38 +321,50 @@ static int multi_bh_frames(Multi *m, float dt, int nframes, bool diagnostic, int
   *built_out = 0;
   { const int rc = wait_gather(m); if (rc) return rc; }
   const bool moves = dt > 0.0f;
-  int todo = nframes;
-  while (todo > 0) {
-    int left = todo < 64 ? todo : 64;                          // batches, as nbody_step has them: a given-up frame takes the ones queued behind it along
-    todo -= left;
-    bool deep_next = false;                                    // the first frame of the next round is one a deep context handed back (status 5)
-    while (left > 0) {
-      for (int f = 0; f < left; ++f) {
-        for (int k = 0; k < m->n_dev; ++k)
-          PART_TRY(m, k, (f == 0 && deep_next) ? part_bh_queue_deep_frame(m->part[(size_t)k], dt, diagnostic)
-                                               : part_bh_queue_frame(m->part[(size_t)k], dt, diagnostic), "Barnes-Hut frame");
-        if (moves) { const int rc = gather_positions(m, true); if (rc) return rc; }
-      }
-      deep_next = false;
-      int status = 0, built = 0, refused_rc = NBODY_OK, refused_k = 0;
-      for (int k = 0; k < m->n_dev; ++k) {                     // every device is collected (a refusal is cleared by that), then the verdicts compared
-        int st = 0, b = 0;
-        const int rc = part_bh_collect(m->part[(size_t)k], &st, &b);
-        if (rc && st != 1 && st != 2 && st != 4 && st != 6) return part_fail(m, k, rc, "Barnes-Hut frame");
-        if (rc && !refused_rc) { refused_rc = rc; refused_k = k; }
-        if (k == 0) { status = st; built = b; }
-        else if (st != status || b != built)
-          return fail(m, NBODY_ERR_STATE, "Barnes-Hut frames: device " + std::to_string(m->devices[(size_t)k]) + " built " + std::to_string(b) +
-                      " frames (status " + std::to_string(st) + "), device " + std::to_string(m->devices[0]) + " " + std::to_string(built) +
-                      " (status " + std::to_string(status) + "): the devices' trees differ");
-      }
-      *built_out += built;
-      left -= built;
-      if (refused_rc) return part_fail(m, refused_k, refused_rc, "Barnes-Hut frame");   // the state is that of the frames built, on every device
-      if (status == 5) { deep_next = true; continue; }           // (5, kBhStatusDeep: built again with its deep clusters resolved, then the rest)
-      if (status != 3) break;                                  // (3: the warm sort gave a frame up; `left` frames again)
+  // one frame on every device — a force-only pass with its row fold behind it — and the gather that brings the moved bodies to everyone
+  auto queue = [&](bool deep, bool) -> int {
+    for (int k = 0; k < m->n_dev; ++k) {
+      nbody_ctx *c = m->part[(size_t)k];
+      (void)hipSetDevice(m->devices[(size_t)k]);
+      PART_TRY(m, k, bh_queue_frame(c, dt, diagnostic, deep, nullptr), "Barnes-Hut frame");
+      if (!moves) PART_TRY(m, k, bh_queue_update(c, 0.0f), "Barnes-Hut frame");
     }
-  }
+    return moves ? gather_positions(m, true) : NBODY_OK;
+  };
+  // every device is collected (a refusal is cleared by that), then the verdicts compared
+  auto collect = [&](int *status, int *built) -> int {
+    int refused_rc = NBODY_OK, refused_k = 0;
+    for (int k = 0; k < m->n_dev; ++k) {
+      int st = kBhStatusOk, b = 0;
+      (void)hipSetDevice(m->devices[(size_t)k]);
+      const int rc = bh_collect_frames(m->part[(size_t)k], &st, &b);
+      if (rc && !bh_refused(st)) return part_fail(m, k, rc, "Barnes-Hut frame");
+      if (rc && !refused_rc) { refused_rc = rc; refused_k = k; }
+      if (k == 0) { *status = st; *built = b; }
+      else if (st != *status || b != *built)
+        return fail(m, NBODY_ERR_STATE, "Barnes-Hut frames: device " + std::to_string(m->devices[(size_t)k]) + " built " + std::to_string(b) +
+                    " frames (status " + std::to_string(st) + "), device " + std::to_string(m->devices[0]) + " " + std::to_string(*built) +
+                    " (status " + std::to_string(*status) + "): the devices' trees differ");
+    }
+    return refused_rc ? part_fail(m, refused_k, refused_rc, "Barnes-Hut frame") : NBODY_OK;   // the state is that of the frames built, on every device
+  };
+  for (int done = 0; done < nframes; done += 64)                 // batches, as nbody_step has them: a given-up frame takes the ones queued behind it along
+    if (const int rc = bh_drive(nframes - done < 64 ? nframes - done : 64, queue, collect, built_out)) return rc;
+  return NBODY_OK;
+}
+
+// One Tick body over all devices (OctreeSearch.cpp:27-31): everything is queued on the devices' streams, nothing waits
+// for the host.
+int multi_forces(Multi *m, float dt) {
+  if (m->theta > 0.0f) { int built = 0; return multi_bh_frames(m, dt, 1, !(dt > 0.0f), &built); }
+  // the strips inside every device's own slice need no other device's positions: they run while the last step's
+  // all-gather is still in flight; the rest of the pass is ordered behind it (nbody_step_begin_local / _remote)
+  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_begin_local(m->part[(size_t)k]), "force pass (own slice)");
+  { const int rc = wait_gather(m); if (rc) return rc; }
+  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_begin_remote(m->part[(size_t)k]), "force pass");
+  { const int rc = exchange_sums(m); if (rc) return rc; }
+  for (int k = 0; k < m->n_dev; ++k) PART_TRY(m, k, nbody_step_end(m->part[(size_t)k], dt), "update");
+  if (dt > 0.0f) return gather_positions(m);
   return NBODY_OK;
 }
 

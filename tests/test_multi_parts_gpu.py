@@ -319,6 +319,49 @@ def test_barnes_hut_over_parts_when_frames_are_given_up_and_refused(nb, oracle, 
         assert e.particles().tobytes() == q.tobytes()
 
 
+def test_a_given_up_diagnostic_pass_over_parts_is_timed_once(nb, parts_env):
+    # nbody_compute_forces right after the records were replaced by the unrelated scene of the test above: the force-only pass starts
+    # from the previous frames' order (nbody_push_particles keeps it), is given up on every device and queued again with the cold
+    # sorts.  nbody_kernel_time counts that pass once — the given-up attempt's event pair is taken back, on a multi-device context as
+    # on one device — and the accelerations are the one-device context's.  That the pass IS given up rests on the scene itself (no
+    # nbody_debug_bh_poison): the one-device twin, taken through the same calls, counts the retry (nbody_debug_bh_sort_counts does
+    # not reach a part of a multi-device context; every device builds the same tree from the same positions).
+    n, parts = 16384, 4
+    rng = np.random.default_rng(3)
+    posm, vel = nb.ic_reference_box(n, 1000.0, seed=2)
+    q = np.zeros(n, nb.PARTICLE_DTYPE)
+    q["Mass"] = posm[:, 3] * np.float32(1e-3); q["Position"] = posm[:, :3]; q["Velocity"] = vel[:, :3]
+    far = np.float32(0.7) * np.abs(q["Position"]).max()
+    clump = (rng.uniform(-30, 30, (n - 1, 3)) + far).astype(np.float32)
+    assert len(np.unique(clump, axis=0)) == n - 1
+    q2 = q.copy()
+    q2["Position"][1:] = clump
+
+    def sort_counts(e):
+        warm, retries = ctypes.c_longlong(), ctypes.c_longlong()
+        assert e._L.nbody_debug_bh_sort_counts(e._h, ctypes.byref(warm), ctypes.byref(retries)) == 0
+        return warm.value, retries.value
+
+    def run(e, twin):
+        e.set_particles(q)
+        e.step(0.01, 2)
+        e.push_particles(q2)
+        launches = e.kernel_time()[1]
+        before = sort_counts(e) if twin else None
+        e.compute_forces()
+        after = sort_counts(e) if twin else None
+        return e.kernel_time()[1] - launches, e.accelerations().copy(), before, after
+
+    with nb.NBodyEngine(n, theta=1.0, time_kernels=True) as one:
+        one_launches, one_acc, before, after = run(one, True)
+    assert after[0] == before[0] + 1 and after[1] == before[1] + 1      # the pass started warm and was queued again: a retry happened
+    assert one_launches == 1
+    with nb.NBodyEngine(n, theta=1.0, time_kernels=True, devices=[0] * parts) as e:
+        launches, acc, _, _ = run(e, False)
+    assert launches == 1
+    assert acc.tobytes() == one_acc.tobytes()
+
+
 def test_barnes_hut_checkpoints_and_the_opening_angle_over_parts(nb, parts_env, tmp_path):
     # the file a multi-device context writes at theta > 0 is the one-device context's (theta and the next tree's root centre
     # included); any partition resumes from it; nbody_set_theta switches a running multi-device context between the two force passes
