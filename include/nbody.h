@@ -278,6 +278,47 @@ NBODY_AMD_API int nbody_bh_leaf_boxes(nbody_ctx *ctx, float *boxes, size_t strid
  * children 0..7; order[k] = index of the body in the k-th occupied leaf.  n_total ints. */
 NBODY_AMD_API int nbody_bh_leaf_order(nbody_ctx *ctx, int32_t *order);
 
+/*
+ * The field at points that are not bodies (build-defined: the reference computes gravity at the bodies only).  Plain fp32 contexts
+ * (NBODY_PREC_F32) on one device that own all bodies; Kahan, fp64 and slice contexts (i_count < n_total) and nbody_create_multi
+ * contexts report NBODY_ERR_UNSUPPORTED.
+ *
+ * nbody_field_at: the acceleration the bodies exert on a massless point, for n caller-given points — xyz: 3 floats each, `stride`
+ * bytes apart (>= 12: &Particles[0].Position with stride 40 works); acc: 3 floats each, `acc_stride` bytes apart (>= 12).
+ *   theta == 0: acc[k] = sum over all n_total bodies, at their current positions, of the context's own pair law (G, eps, zero_mode;
+ *     NBODY_ZERO_SELECT contexts get the clamp form, which drops the same pairs); a point exactly on a body skips that pair when
+ *     eps == 0, as d == 0 does (OctreeSearch.h:102).  Every point's sum runs in a fixed order — the bodies in chunks that follow from
+ *     n_total alone, the chunks in order — so a point's result depends neither on the other points of the call, nor on n, nor on the
+ *     strides, nor on the device.
+ *   theta > 0: the walk of Octree::ComputeForces (OctreeSearch.h:99-108) from the point over THE LAST TREE BUILT — the tree nbody_bh_stats,
+ *     nbody_bh_leaf_boxes and nbody_bh_leaf_order describe —: the same opening rule on the unsoftened d, the same leaf rule, d == 0 ends the
+ *     subtree, the same term, softening included; at a body's own position it gives that body's own sum in every bit.  After nbody_step or
+ *     nbody_tick the last tree is that of the positions BEFORE that frame's update — the field the bodies just felt; for the field at the
+ *     current positions call nbody_compute_forces first.  Without a valid last tree — none built yet, the last frame refused, theta changed
+ *     since it was built — NBODY_ERR_STATE; a last tree built deeper than 42 levels (nbody_set_bh_max_depth) NBODY_ERR_UNSUPPORTED.
+ * n == 0 is a no-op; NULL pointers, n < 0 and strides < 12 are NBODY_ERR_INVALID.  The call synchronises and changes nothing a getter
+ * of the state shows: bodies, accelerations, steps done, root centre and tree stay what they were.  The one exception are the kernel
+ * timers of a time_kernels context: a query's device time is added to NBODY_KERNEL_FORCES and counts as one pass there
+ * (nbody_kernel_time), and at theta == 0 its workgroups enter nbody_kernel_clock's average.
+ *
+ * Tracers: massless bodies the engine advances along with the bodies.  nbody_set_tracers replaces any earlier set — pos4 / vel4: n x 4
+ * floats (the 4th ignored); vel4 NULL = at rest; n = 0 removes them.  In every step of nbody_step and nbody_tick with dt > 0 a tracer at
+ * y_n gets a = the field of the bodies at x_n — the positions that step's force pass uses (theta > 0: the walk of that frame's tree) —,
+ * then v += dt*a; y += dt*v, the bodies' own fp32 kick-drift (OctreeSearch.cpp:29-30).  nbody_compute_forces stores the tracers'
+ * accelerations as well and moves nothing; dt <= 0 leaves them alone, and nbody_step_begin / nbody_step_end touch neither their
+ * state nor their stored accelerations, at any theta.  Tracers never act on bodies or on each other: a context with tracers advances its bodies exactly as the same context without them, byte for byte.  A theta > 0
+ * frame that is refused leaves the tracers untouched like the bodies.  Their device time counts under NBODY_KERNEL_FORCES.
+ * Uploads (nbody_set_*, nbody_push_particles, nbody_load_checkpoint) keep the tracers.  Checkpoints do not store them (NBDYCKP2 is what
+ * it was): a host saves and restores them with nbody_get_tracers / nbody_set_tracers, which is bit-exact.
+ * Tracers and trees deeper than 42 levels exclude each other: whichever of nbody_set_tracers and nbody_set_bh_max_depth(> 42) comes second
+ * reports NBODY_ERR_UNSUPPORTED.
+ */
+NBODY_AMD_API int nbody_field_at(nbody_ctx *ctx, const float *xyz, size_t stride, int32_t n, float *acc, size_t acc_stride);
+NBODY_AMD_API int nbody_set_tracers(nbody_ctx *ctx, const float *pos4, const float *vel4, int32_t n);
+/* pos4 / vel4 / acc4: nbody_tracer_count x 4 floats each, any may be NULL.  Synchronises. */
+NBODY_AMD_API int nbody_get_tracers(nbody_ctx *ctx, float *pos4, float *vel4, float *acc4);
+NBODY_AMD_API int nbody_tracer_count(nbody_ctx *ctx, int32_t *n);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

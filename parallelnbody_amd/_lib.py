@@ -112,6 +112,10 @@ def lib():
     sig("nbody_bh_stats", c_int, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), fp)
     sig("nbody_bh_leaf_boxes", c_int, vp, fp, sz)
     sig("nbody_bh_leaf_order", c_int, vp, ctypes.POINTER(c_i32))
+    sig("nbody_field_at", c_int, vp, vp, sz, c_i32, vp, sz)
+    sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
+    sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
+    sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))
     sig("nbody_get_bounds", c_int, vp, fp)
     sig("nbody_get_positions", c_int, vp, fp, sz, c_i32, c_i32)
     sig("nbody_get_particles", c_int, vp, vp, sz)

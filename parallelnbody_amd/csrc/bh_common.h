@@ -543,6 +543,10 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
                                                           float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                           unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
                                                           WalkSlice S);
+// the walk of the last tree from points that are not bodies (HOP: on the hop words, where the tree has them)
+template <bool HOP, bool SOFT>
+__global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *__restrict__ pts, float4 *__restrict__ vel,
+                                                           float4 *__restrict__ acc, int m, double G, float eps2, float dt);
 
 }  // namespace bh
 }  // namespace nbody

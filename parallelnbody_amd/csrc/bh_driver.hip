@@ -45,6 +45,11 @@ int bh_queue_frame(nbody_ctx *c, float dt, bool diagnostic, bool deep, float *st
   auto launch = [&]() -> int {
     HIP_TRY(c, (deep ? bh_deep_frame : bh_frame)(c->bh, c->posm, whole ? c->vel : nullptr, whole ? c->acc : c->bh_acc, c->theta, c->p.G,
                                                  bh_eps2(c), whole ? dt : 0.0f, diagnostic ? 1 : 0, whole ? stage : nullptr, c->stream));
+    // the tracers' walk of this frame's tree, behind the frame's own walk and part of the frame: timed with it, queued again with it,
+    // and — looking at the frame's verdict itself — idle behind a frame that did nothing
+    // (whole frames and nbody_compute_forces' pass; not the force-only pass of nbody_step_begin, which leaves tracers alone at every angle)
+    if (c->tr_n > 0 && (whole || diagnostic))
+      HIP_TRY(c, bh_probe_walk(c->bh, c->tr_pos, c->tr_vel, c->tr_acc, c->tr_n, c->p.G, bh_eps2(c), whole ? dt : 0.0f, c->stream));
     return NBODY_OK;
   };
   // (small systems queue a whole call's frames at once and give none up: bound the number of live events; the larger systems'
@@ -63,6 +68,8 @@ int bh_collect_frames(nbody_ctx *c, int *status, int *built) {
   HIP_TRY(c, bh_collect(c->bh, c->stream, status, built));
   if (c->bh_batch.whole) c->steps_done += *built;
   const int undone = c->bh_batch.queued - *built;
+  // what nbody_field_at may walk: the arrays hold the tree of the last frame queued, if that frame was built
+  if (c->bh_batch.queued > 0) { c->bh_tree_valid = *status == kBhStatusOk && undone == 0; c->bh_tree_theta = c->theta; }
   c->bh_batch.queued = 0;
   if (*status == kBhStatusRetry || *status == kBhStatusDeep) {
     if (c->p.time_kernels) timer_take_back(c, NBODY_KERNEL_FORCES, undone);

@@ -514,6 +514,23 @@ hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s) {
   return hipGetLastError();
 }
 
+bool bh_last_deep(const BhState *b) { return b->last_deep; }
+
+// The walk of the last tree from m points that are not bodies (bh_probe_walk_kernel), queued on the stream behind the frame that
+// builds it — or behind nothing, for a query of the tree that is there.  b->st is the tree of every frame but a deep one.
+hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, double G, float eps2, float dt, hipStream_t s) {
+  if (m <= 0 || !pts || !acc || (dt > 0.0f && !vel) || b->last_deep) return hipErrorInvalidValue;
+  const dim3 grd((m + kB - 1) / kB), blk(kB);
+  const bool soft = eps2 > 0.0f;
+  if (b->st.hop != nullptr)
+    hipLaunchKernelGGL((soft ? bh_probe_walk_kernel<true, true> : bh_probe_walk_kernel<true, false>), grd, blk, 0, s, b->st, (float4 *)pts,
+                       (float4 *)vel, (float4 *)acc, m, G, eps2, dt);
+  else
+    hipLaunchKernelGGL((soft ? bh_probe_walk_kernel<false, true> : bh_probe_walk_kernel<false, false>), grd, blk, 0, s, b->st, (float4 *)pts,
+                       (float4 *)vel, (float4 *)acc, m, G, eps2, dt);
+  return hipGetLastError();
+}
+
 void bh_set_div_mode(BhState *b, int div_mode) { b->div_mode = div_mode ? 1 : 0; }
 
 // The deepest tree the context answers (42 .. kDeepMaxLevels; nbody_set_bh_max_depth).  Above 42 the deep frames' buffers are made

@@ -359,6 +359,40 @@ int ensure_floor(nbody_ctx *c) {
   return NBODY_OK;
 }
 
+// the partial rows of a slab of `m` points (kernels_probe.hip), grown on demand; freed at nbody_destroy
+int ensure_probe_part(nbody_ctx *c, int m) {
+  const size_t need = nbody::probe_part_elems(c->p.n_total, m);
+  if (need <= c->probe_part_elems) return NBODY_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                      // (a tracer pass may still be reading the old one)
+  if (c->probe_part) (void)hipFree(c->probe_part);
+  c->probe_part = nullptr; c->probe_part_elems = 0;
+  HIP_TRY(c, hipMalloc(&c->probe_part, need * 16));
+  c->probe_part_elems = need;
+  return NBODY_OK;
+}
+
+// theta == 0: the field of the bodies at their CURRENT positions at m points, queued (the context's own pair law: G, eps, zero_mode —
+// compare+select contexts get the clamp form, which drops the same pairs).  dt > 0: the points are the tracers and move.
+int queue_probe(nbody_ctx *c, void *pts, void *vel, void *acc, int m, float dt) {
+  nbody::ProbeLaunch L;
+  L.posm = c->posm; L.probe = pts; L.part = c->probe_part; L.acc = acc; L.pos_out = pts; L.vel = vel;
+  L.n_total = c->p.n_total; L.m = m;
+  L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+  if (L.eps2 == 0.0 && c->p.zero_mode == NBODY_ZERO_FLOOR && c->floor_eps2 > 0.0) L.eps2 = c->floor_eps2;
+  L.dt = dt;
+  L.clk = c->clk;
+  HIP_TRY(c, nbody::launch_probe(L, c->stream));
+  return NBODY_OK;
+}
+
+// The tracers' share of a theta == 0 step, queued IN FRONT of the bodies' force and update launches of that step: it reads the
+// positions the step's force pass uses, and the stream's order does the rest.  dt == 0: accelerations only.
+int queue_tracers(nbody_ctx *c, float dt) {
+  if (c->tr_n <= 0) return NBODY_OK;
+  if (int rc = ensure_probe_part(c, c->tr_n)) return rc;         // (the first theta == 0 pass with these tracers makes it: a theta > 0 context never does)
+  return queue_probe(c, c->tr_pos, c->tr_vel, c->tr_acc, c->tr_n, dt);
+}
+
 // the all-pairs force pass, queued.  phase (SymLaunch::phase): 0 the whole pass; 1 / 2 the two goes of a sharded fp32 symmetric context (sym_two_goes)
 int queue_forces(nbody_ctx *c, int phase) {
   if (c->sym) {
@@ -403,10 +437,14 @@ int queue_forces(nbody_ctx *c, int phase) {
 }
 
 // one force pass; theta > 0: the Barnes-Hut walk into bh_acc, waited for (bh_driver.h; diagnostic: nbody_compute_forces' pass, part of no frame)
-int run_forces(nbody_ctx *c, bool diagnostic = false, int phase = 0) {
+// tracer_dt >= 0 (nbody_step, nbody_compute_forces): the pass also carries the tracers, if any (theta > 0: the frame does, bh_driver.hip)
+int run_forces(nbody_ctx *c, bool diagnostic = false, int phase = 0, float tracer_dt = -1.0f) {
   if (c->theta > 0.0f) return nbody::bh_run_forces(c, diagnostic);
   { int rc = ensure_floor(c); if (rc) return rc; }
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&] { return queue_forces(c, phase); }, phase != 1);   // two goes are ONE pass
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&] {
+    if (c->tr_n > 0 && tracer_dt >= 0.0f) { if (int rc = queue_tracers(c, tracer_dt)) return rc; }
+    return queue_forces(c, phase);
+  }, phase != 1);   // two goes are ONE pass
 }
 
 int run_update(nbody_ctx *c, float dt) {
@@ -800,6 +838,9 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev})
+    if (q) (void)hipFree(q);
+  if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->clk) (void)hipFree(c->clk);
   if (c->energy_part) (void)hipFree(c->energy_part);
@@ -1048,7 +1089,7 @@ int nbody_compute_forces(nbody_ctx *c) {
   if (c->multi) return multi_rc(c, nbody::multi_forces(c->multi, 0.0f));
   if ((rc = needs_phases(c, "nbody_compute_forces"))) return rc;
   HIP_TRY(c, hipSetDevice(c->p.device));
-  if ((rc = run_forces(c, true))) return rc;
+  if ((rc = run_forces(c, true, 0, 0.0f))) return rc;
   if ((rc = run_update(c, 0.0f))) return rc;
   return NBODY_OK;
 }
@@ -1066,6 +1107,7 @@ static int step_one_launch(nbody_ctx *c, float dt, void *stage, void *size_bits,
   if (!c->posm_alt) HIP_TRY(c, hipMalloc(&c->posm_alt, (size_t)c->p.n_total * c->elem));
   if ((rc = ensure_floor(c))) return rc;
   rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    if (c->tr_n > 0) { if (int trc = queue_tracers(c, dt)) return trc; }   // (they read c->posm, which this launch only reads)
     HIP_TRY(c, nbody::launch_step_small(make_launch(c), c->posm_alt, c->vel, c->acc, dt, c->stream, stage, size_bits, size_zero));
     return NBODY_OK;
   });
@@ -1111,7 +1153,7 @@ int nbody_step(nbody_ctx *c, float dt, int32_t nsteps) {
       if ((rc = step_one_launch(c, dt, nullptr, nullptr, nullptr))) return rc;
       continue;
     }
-    if ((rc = run_forces(c))) return rc;
+    if ((rc = run_forces(c, false, 0, dt))) return rc;
     if ((rc = run_update(c, dt))) return rc;
   }
   c->steps_done += nsteps;
@@ -1471,6 +1513,7 @@ int nbody_set_theta(nbody_ctx *c, float theta) {
     return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_set_theta: Barnes-Hut needs an fp32 context");
   if (theta != c->theta) c->sym_posg_valid = false;   // the other force pass moves bodies without preparing the next all-pairs pass
   if (theta != c->theta && c->bh) nbody::bh_positions_changed(c->bh);   // ... nor leaving the next Barnes-Hut frame's Size
+  if (theta != c->theta) c->bh_tree_valid = false;    // the last tree's thresholds are the old angle's (nbody_field_at)
   c->theta = theta;
   return NBODY_OK;
 }
@@ -1485,6 +1528,9 @@ int nbody_set_bh_max_depth(nbody_ctx *c, int32_t levels) {
   }
   if (c->p.precision != NBODY_PREC_F32)
     return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_set_bh_max_depth: Barnes-Hut needs an fp32 context");
+  if (levels > 42 && c->tr_n > 0)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_set_bh_max_depth: trees deeper than 42 levels do not carry tracers (remove them with "
+                "nbody_set_tracers(ctx, NULL, NULL, 0) first)");
   if (int rc = use_device(c)) return rc;
   if (c->bh) {
     const hipError_t e = nbody::bh_set_max_depth(c->bh, levels);
@@ -1541,6 +1587,113 @@ int nbody_bh_leaf_order(nbody_ctx *c, int32_t *order) {
   if (!c->bh) return fail(c, NBODY_ERR_STATE, "nbody_bh_leaf_order: no tree has been built on this context (theta == 0?)");
   if (int rc = use_device(c)) return rc;
   HIP_TRY(c, nbody::bh_leaf_order(c->bh, order, c->stream));
+  return NBODY_OK;
+}
+
+// ---- the field at points that are not bodies: queries (nbody_field_at) and engine-stepped tracers ----
+namespace {
+// where they exist: plain fp32 contexts on one device that own all bodies
+int probes_supported(nbody_ctx *c, const char *who) {
+  if (c->p.precision != NBODY_PREC_F32)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: plain fp32 contexts only (NBODY_PREC_F32)", who);
+  if (c->p.i_count != c->p.n_total)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
+  return NBODY_OK;
+}
+}  // namespace
+
+int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *acc, size_t acc_stride) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_field_at");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_field_at"))) return rc;
+  if (n < 0 || !xyz || !acc || stride < 12 || acc_stride < 12)
+    return fail(c, NBODY_ERR_INVALID, "nbody_field_at: null buffer, n < 0 or a stride < 12");
+  if (n == 0) return NBODY_OK;
+  if (c->theta > 0.0f) {
+    if (!c->bh || !c->bh_tree_valid || c->bh_tree_theta != c->theta)
+      return fail(c, NBODY_ERR_STATE, "nbody_field_at: theta > 0 walks the last tree built, and there is none for this opening angle "
+                  "(none built yet, the last frame refused, or theta changed since): call nbody_compute_forces, nbody_step or nbody_tick first");
+    if (nbody::bh_last_deep(c->bh))
+      return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_field_at: the last tree was built deeper than 42 levels (nbody_set_bh_max_depth); "
+                  "such trees answer no field queries");
+  } else {
+    if ((rc = ensure_floor(c))) return rc;
+    if ((rc = ensure_probe_part(c, n))) return rc;
+  }
+  if ((size_t)n > c->probe_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->probe_dev) (void)hipFree(c->probe_dev);
+    if (c->probe_host) (void)hipHostFree(c->probe_host);
+    c->probe_dev = c->probe_host = nullptr; c->probe_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->probe_dev, (size_t)n * 32));
+    HIP_TRY(c, hipHostMalloc(&c->probe_host, (size_t)n * 32, hipHostMallocDefault));
+    c->probe_cap = (size_t)n;
+  }
+  float *h_pts = (float *)c->probe_host, *h_acc = h_pts + 4 * (size_t)n;
+  float *d_pts = (float *)c->probe_dev, *d_acc = d_pts + 4 * (size_t)n;
+  for (size_t k = 0; k < (size_t)n; ++k) {
+    memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
+    h_pts[4 * k + 3] = 0.0f;
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    if (c->theta > 0.0f) {
+      HIP_TRY(c, nbody::bh_probe_walk(c->bh, d_pts, nullptr, d_acc, n, c->p.G, (float)(c->p.eps * c->p.eps), 0.0f, c->stream));
+      return NBODY_OK;
+    }
+    return queue_probe(c, d_pts, nullptr, d_acc, n, 0.0f);
+  });                                                              // (a query's device time counts as a pass under NBODY_KERNEL_FORCES)
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h_acc, d_acc, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)acc + k * acc_stride, h_acc + 4 * k, 12);
+  return NBODY_OK;
+}
+
+int nbody_set_tracers(nbody_ctx *c, const float *pos4, const float *vel4, int32_t n) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_set_tracers");
+  if (!c) return NBODY_ERR_INVALID;
+  if (int rc = probes_supported(c, "nbody_set_tracers")) return rc;
+  if (n < 0 || (n > 0 && !pos4)) return fail(c, NBODY_ERR_INVALID, "nbody_set_tracers: n < 0 or null positions");
+  if (n > 0 && c->bh_max_depth > 42)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_set_tracers: this context builds trees deeper than 42 levels (nbody_set_bh_max_depth), "
+                "which do not carry tracers");
+  if (int rc = use_device(c)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (void **q : {&c->tr_pos, &c->tr_vel, &c->tr_acc}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+  c->tr_n = 0;
+  if (n == 0) return NBODY_OK;
+  const size_t bytes = (size_t)n * 16;
+  HIP_TRY(c, hipMalloc(&c->tr_pos, bytes));
+  HIP_TRY(c, hipMalloc(&c->tr_vel, bytes));
+  HIP_TRY(c, hipMalloc(&c->tr_acc, bytes));
+  HIP_TRY(c, hipMemcpyAsync(c->tr_pos, pos4, bytes, hipMemcpyHostToDevice, c->stream));
+  if (vel4) HIP_TRY(c, hipMemcpyAsync(c->tr_vel, vel4, bytes, hipMemcpyHostToDevice, c->stream));
+  else      HIP_TRY(c, hipMemsetAsync(c->tr_vel, 0, bytes, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->tr_acc, 0, bytes, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's arrays are its own again
+  c->tr_n = n;
+  return NBODY_OK;
+}
+
+int nbody_get_tracers(nbody_ctx *c, float *pos4, float *vel4, float *acc4) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_get_tracers");
+  if (!c) return NBODY_ERR_INVALID;
+  if (int rc = use_device(c)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t bytes = (size_t)c->tr_n * 16;
+  if (bytes == 0) return NBODY_OK;
+  if (pos4) HIP_TRY(c, hipMemcpy(pos4, c->tr_pos, bytes, hipMemcpyDeviceToHost));
+  if (vel4) HIP_TRY(c, hipMemcpy(vel4, c->tr_vel, bytes, hipMemcpyDeviceToHost));
+  if (acc4) HIP_TRY(c, hipMemcpy(acc4, c->tr_acc, bytes, hipMemcpyDeviceToHost));
+  return NBODY_OK;
+}
+
+int nbody_tracer_count(nbody_ctx *c, int32_t *n) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_tracer_count");
+  if (!c || !n) return NBODY_ERR_INVALID;
+  *n = c->tr_n;
   return NBODY_OK;
 }
 

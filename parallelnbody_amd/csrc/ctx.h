@@ -84,6 +84,16 @@ struct nbody_ctx {
   int bh_max_depth = 42;       // the deepest tree a frame may build (nbody_set_bh_max_depth): a setting, not state (checkpoints do not keep it)
   void *bh_acc = nullptr;      // [i_count] float4: the walk's output, summed (j_split = 1) by update_kernel
   struct { int queued = 0; bool whole = false; } bh_batch;   // what bh_queue_frame queued since the last bh_collect_frames (whole: frames, not a force-only pass)
+  // massless points in the bodies' field (kernels_probe.hip; theta > 0: bh_probe_walk): the tracers the steps carry along
+  // (nbody_set_tracers) and the staging of nbody_field_at, grown on demand
+  int tr_n = 0;
+  void *tr_pos = nullptr, *tr_vel = nullptr, *tr_acc = nullptr;   // [tr_n] float4 each
+  void *probe_part = nullptr;  // the j chunks' partial rows of one slab of points (theta == 0), shared by tracers and queries
+  size_t probe_part_elems = 0;
+  void *probe_dev = nullptr, *probe_host = nullptr;   // nbody_field_at: [2][probe_cap] float4 — the points, their accelerations — on the device, and its pinned mirror
+  size_t probe_cap = 0;
+  bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
+  float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
   int clk_items = 0;                   // NBODY_SYM_ITEM_CLOCKS: work items with stamps of their own behind the eight clock words
   unsigned long long *clk = nullptr;   // time_kernels: {shader-clock cycles, reference-clock ticks} summed over the force kernels' workgroups (pk_common.h)

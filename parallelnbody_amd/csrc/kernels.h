@@ -72,6 +72,32 @@ hipError_t launch_block(const BlockLaunch &L, hipStream_t s);
 hipError_t launch_update(int precision, void *posm, void *vel, void *acc, const void *accp, int i_begin,
                          int i_count, int j_split, float dt, hipStream_t s);
 
+// The bodies' field at `m` massless points, theta = 0 — kernels_probe.hip: acc[k] = sum over all n_total bodies of the pair law at
+// probe[k], partial rows per j chunk added in chunk order.  The chunks follow from n_total alone (probe_geometry), so a point's bits
+// do not depend on the other points, on m or on the device.  dt > 0: the points are tracers — v += dt*a; x += dt*v on (pos_out, vel)
+// behind the sums, as the bodies get it (pos_out may be `probe` itself: a slab's positions are read before they are written).
+constexpr size_t kProbePartBytes = 256u << 20;   // the partial rows' staging area at most: larger queries go in slabs of points
+struct ProbeLaunch {
+  const void *posm = nullptr;   // [n_total] float4: x, y, z, m
+  const void *probe = nullptr;  // [m] float4: x, y, z, unused
+  void *part = nullptr;         // [probe_part_elems(n_total, m)] float4: partial rows of one slab
+  void *acc = nullptr;          // [m] float4
+  void *pos_out = nullptr, *vel = nullptr;   // dt > 0: [m] float4 each
+  int n_total = 0, m = 0;
+  double G = 0.0, eps2 = 0.0;   // eps2 > 0 softened (also the floor mode); == 0 exact d == 0 skip (clamp form)
+  float dt = 0.f;
+  void *clk = nullptr;          // two device uint64 the workgroups add their clock intervals to (pk_common.h)
+};
+void probe_geometry(int n_total, int *j_split, int *j_chunk);
+size_t probe_slab_points(int n_total);                        // points whose partial rows fit kProbePartBytes (a multiple of 1024)
+inline size_t probe_part_elems(int n_total, int m) {            // float4 elements `part` must hold for a launch of m points
+  int js, jc;
+  probe_geometry(n_total, &js, &jc);
+  const size_t slab = probe_slab_points(n_total);
+  return (size_t)js * ((size_t)m < slab ? (size_t)m : slab);
+}
+hipError_t launch_probe(const ProbeLaunch &L, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {
@@ -179,6 +205,12 @@ hipError_t bh_leaf_order(BhState *b, int *out_host, hipStream_t s);
 hipError_t bh_stats(BhState *b, hipStream_t s, int *nodes, int *levels);   // waits for the stream when the last tree's counts are still on their way
 // out[body] = (ox, oy, oz, Size) of the leaf holding the body, for the last tree built
 hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s);
+// Octree::ComputeForces (OctreeSearch.h:99-108) from m points that are not bodies (pts: float4 x, y, z, unused), over the tree the
+// frame queued last on `s` has built — the body walks' step test and term, one lane per point in the caller's order.  The kernel looks at
+// the frame's verdict and does nothing behind a frame refused or given up; it writes neither the verdict nor the tree.  dt > 0: the points
+// are tracers and get the bodies' kick-drift on (pts, vel) behind their walk.  Not for the tree of a deep frame (bh_last_deep).
+hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, double G, float eps2, float dt, hipStream_t s);
+bool bh_last_deep(const BhState *b);                          // the last frame queued was built by the deep path
 hipError_t bh_get_root_com(BhState *b, float out[3], hipStream_t s);
 hipError_t bh_set_root_com(BhState *b, const float in[3], hipStream_t s);
 

@@ -1,6 +1,7 @@
 // Octree::ComputeForces (OctreeSearch.h:99-108) on the compact tree, and the Tick's update behind every walk (OctreeSearch.cpp:28-31)
 // — see bh_common.h.
 #include "bh_common.h"
+#include "tracer_update.h"
 
 namespace nbody {
 namespace bh {
@@ -662,7 +663,7 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
   // One step: the node in (CA, HA) is looked at, the node the walk goes to is asked for into (CB, HB).  Two steps to a turn of the
   // loop with the two register sets changing places, so that no step ends with the moves of "next becomes current" (two 64-bit moves
   // behind the loads' arrival, 4 % of the walk's instructions where the waves queue for the VALU).
-#define BH_LANE_STEP(CA, HA, CB, HB)                                                                                                   \
+#define BH_LANE_STEP(CA, HA, CB, HB, EPS2)                                                                                             \
   {                                                                                                                                    \
     const float ex = p.x - CA.x, ey = p.y - CA.y, ez = p.z - CA.z;                                                                     \
     float d2 = ex * ex + ey * ey;                                                                                                      \
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
     HB = *(const uint2 *)((const char *)T.hop + (fetch << 3));                                                                        \
     if (take && d2 != 0.f) {                                                                                                           \
       float tx, ty, tz;                                                                                                                \
-      force_term<SOFT>(CA.x, CA.y, CA.z, CA.w, p, G, S.eps2, tx, ty, tz);                                                              \
+      force_term<SOFT>(CA.x, CA.y, CA.z, CA.w, p, G, EPS2, tx, ty, tz);                                                                \
       ax = ax + tx; ay = ay + ty; az = az + tz;                                                                                        \
     }                                                                                                                                  \
     node = next;                                                                                                                       \
@@ -686,21 +687,85 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
   if constexpr (!TWO) {
     while (node < nodes) {
       float4 cm2; uint2 h2;
-      BH_LANE_STEP(cm, h, cm2, h2)
+      BH_LANE_STEP(cm, h, cm2, h2, S.eps2)
       cm = cm2; h = h2;
     }
   } else {
     float4 cm2 = cm;
     uint2 h2 = h;
     while (node < nodes) {
-      BH_LANE_STEP(cm, h, cm2, h2)
-      if (node < nodes) BH_LANE_STEP(cm2, h2, cm, h)
+      BH_LANE_STEP(cm, h, cm2, h2, S.eps2)
+      if (node < nodes) BH_LANE_STEP(cm2, h2, cm, h, S.eps2)
     }
   }
-#undef BH_LANE_STEP
-#endif
+#endif   // (BH_LANE_STEP stays defined for bh_probe_walk_kernel below)
   walk_lane_tail(valid, body, p, ax, ay, az, posm, vel, acc, dt, stage, S.off, next_size, pos_sorted, place);
 }
+
+// Octree::ComputeForces (.h:99-108) from a point that is NOT a body — nbody_field_at's points, the tracers of nbody_set_tracers —, one
+// lane per point in the caller's order, over the tree the last frame left in its global arrays: a leaf's CoM is its body's position and
+// mass, so this is the loop of bh_walk_lane_kernel with the position taken from `pts`, and at a body's own position it gives that body's
+// own sum in every bit (the body meets its own leaf at d == 0, which adds nothing).  HOP: the tree carries hop words (the larger
+// systems') and a step is the lane walk's own, BH_LANE_STEP; otherwise the plain loop on the node words and the levels' thresholds.
+// The same step test, the same force_term.  The kernel reads the frame's verdict and does nothing unless it is 0 — a frame refused,
+// given up or handed back, and every frame queued behind one, leaves tracers where they were —; it neither writes the verdict nor
+// touches the tree.  dt > 0: the point is a tracer and gets the bodies' update behind its walk (.cpp:29-30, multiply and add apart).
+template <bool HOP, bool SOFT>
+__global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *__restrict__ pts, float4 *__restrict__ vel,
+                                                           float4 *__restrict__ acc, int m, double G, float eps2, float dt) {
+#pragma clang fp contract(off)
+  const int k = blockIdx.x * kB + threadIdx.x;
+  const bool valid = k < m;
+  const int status = T.hdr[3], nodes_all = T.hdr[0];
+  if (status != 0) return;
+  const int nodes = valid ? nodes_all : 0;
+  const float4 p = pts[valid ? k : 0];
+  float ax = 0.f, ay = 0.f, az = 0.f;                          // Acceleration = ZeroVector, .cpp:84
+  int node = 0;
+#ifdef BH_LANE_STEP
+  if constexpr (HOP) {
+    float4 cm = T.com[0];
+    uint2 h = T.hop[0];
+    while (node < nodes) {
+      float4 cm2; uint2 h2;
+      BH_LANE_STEP(cm, h, cm2, h2, eps2)
+      cm = cm2; h = h2;
+    }
+  } else
+#endif
+  {
+    __shared__ float s_thr[kMaxLevels + 2];
+    if (threadIdx.x <= kMaxLevels) s_thr[threadIdx.x] = T.thr[threadIdx.x];
+    __syncthreads();
+    while (node < nodes) {
+      const float4 cm = T.com[node];
+      const unsigned int w = T.meta[node];
+      const bool leaf = (w & kLeafBit) != 0u;
+      const int past = leaf ? node + 1 : (int)(w & kLinkMask);
+      const float ex = p.x - cm.x, ey = p.y - cm.y, ez = p.z - cm.z;
+      float d2 = ex * ex + ey * ey;
+      d2 = d2 + ez * ez;
+      const bool take = leaf || d2 >= s_thr[(w >> kLevelShift) & 63u];   // .h:103
+      if (take && d2 != 0.f) {
+        float tx, ty, tz;
+        force_term<SOFT>(cm.x, cm.y, cm.z, cm.w, p, G, eps2, tx, ty, tz);
+        ax = ax + tx; ay = ay + ty; az = az + tz;
+      }
+      node = (take || d2 == 0.f) ? past : node + 1;           // .h:102: d == 0 ends the subtree
+    }
+  }
+  if (!valid) return;
+  acc[k] = make_float4(ax, ay, az, 0.f);
+  if (dt > 0.f) {
+    float4 v = vel[k], x = p;
+    tracer_kick_drift(dt, ax, ay, az, v, x);
+    vel[k] = v;
+    pts[k] = x;
+  }
+}
+#ifdef BH_LANE_STEP
+#undef BH_LANE_STEP
+#endif
 
 
 #define BH_WALK_KERNELS(SOFT)                                                                                                          \
@@ -719,6 +784,10 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
 BH_WALK_KERNELS(false)
 BH_WALK_KERNELS(true)
 #undef BH_WALK_KERNELS
+template __global__ void bh_probe_walk_kernel<false, false>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
+template __global__ void bh_probe_walk_kernel<false, true>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
+template __global__ void bh_probe_walk_kernel<true, false>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
+template __global__ void bh_probe_walk_kernel<true, true>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
 
 }  // namespace bh
 }  // namespace nbody

@@ -262,6 +262,52 @@ class NBodyEngine:
         self._check(self._L.nbody_bh_leaf_order(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return out
 
+    # -- the field at points that are not bodies --
+    def field_at(self, points):
+        """Acceleration the bodies exert on a massless point, for every row of `points` (nbody_field_at): [n,3] float32.  points: an
+        [n,3] (or [n,>=3]) float32 array with any row stride — e.g. the Position field of a PARTICLE_DTYPE array, read in place —
+        or anything np.asarray turns into one.  theta > 0: the walk of the last tree built (include/nbody.h)."""
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] < 3:
+            raise ValueError("field_at: points must be [n, >= 3]")
+        p = p[:, :3]
+        if p.dtype != np.float32 or p.shape[0] < 2 or p.strides[1] != 4 or p.strides[0] < 12:
+            p = np.ascontiguousarray(p, np.float32)
+        out = np.empty((p.shape[0], 3), np.float32)
+        self._check(self._L.nbody_field_at(self._h, p.ctypes.data, max(p.strides[0], 12), p.shape[0], out.ctypes.data, 12))
+        return out
+
+    def set_tracers(self, pos, vel=None):
+        """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
+        ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
+        def four(a):
+            a = np.asarray(a, np.float32)
+            a = a.reshape(-1, a.shape[-1] if a.ndim == 2 else 3)
+            if a.shape[1] not in (3, 4):
+                raise ValueError("set_tracers: [n,3] or [n,4]")
+            b = np.zeros((a.shape[0], 4), np.float32)
+            b[:, :a.shape[1]] = a
+            return b
+        p = four(pos)
+        v = None if vel is None else four(vel)
+        if v is not None and v.shape != p.shape:
+            raise ValueError("set_tracers: pos and vel must have the same number of rows")
+        self._check(self._L.nbody_set_tracers(self._h, _fp(p), None if v is None else _fp(v), p.shape[0]))
+
+    @property
+    def tracer_count(self):
+        n = ctypes.c_int32()
+        self._check(self._L.nbody_tracer_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def tracers(self):
+        """(pos, vel, acc) of the tracers, [n,4] float32 each (nbody_get_tracers; synchronises).  Feeding pos and vel back to
+        set_tracers restores them bit for bit."""
+        n = self.tracer_count
+        p, v, a = (np.zeros((n, 4), np.float32) for _ in range(3))
+        self._check(self._L.nbody_get_tracers(self._h, _fp(p), _fp(v), _fp(a)))
+        return p, v, a
+
     def synchronize(self):
         self._check(self._L.nbody_synchronize(self._h))
 
