@@ -319,6 +319,44 @@ NBODY_AMD_API int nbody_set_tracers(nbody_ctx *ctx, const float *pos4, const flo
 NBODY_AMD_API int nbody_get_tracers(nbody_ctx *ctx, float *pos4, float *vel4, float *acc4);
 NBODY_AMD_API int nbody_tracer_count(nbody_ctx *ctx, int32_t *n);
 
+/*
+ * The gravitational potential (build-defined: the reference computes none), on the contexts that answer nbody_field_at: plain fp32, one
+ * device, owning all bodies; Kahan, fp64, slice and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED.
+ *
+ * nbody_potential_at: phi at n caller-given points — xyz: 3 floats each, `stride` bytes apart (>= 12); phi: one float each, `phi_stride`
+ * bytes apart (>= 4).
+ *   theta == 0: phi(x) = -sum_j G m_j / sqrt(|x - x_j|^2 + eps^2) over all n_total bodies at their current positions.  With eps == 0 a pair
+ *     at distance exactly 0 contributes nothing, whatever zero_mode the context has (NBODY_ZERO_FLOOR's eps floor is NOT applied: it would
+ *     add G m / 1e-10); with eps > 0 a point exactly on a body does feel that body's -G m / eps, the Plummer potential at its centre.  The
+ *     pair term is fp32 (a 1-ulp reciprocal square root); a chunk's sum is one chain of fused multiply-adds in body order, the chunks —
+ *     those of nbody_field_at, a function of n_total alone — are added in chunk order in fp64, and the sum is negated and rounded once.  A
+ *     point's bits depend neither on the other points of the call, nor on n, nor on the strides, nor on the device.
+ *   theta > 0: the walk of Octree::ComputeForces (OctreeSearch.h:99-108) over THE LAST TREE BUILT, with nbody_field_at's rules: the same
+ *     opening test on the unsoftened d, the same leaf rule, d == 0 ends the subtree.  An accepted node adds, in fp64,
+ *     G * (double)M / (double)ds, ds = sqrtf(d^2 + eps^2) correctly rounded in fp32 (the eps^2 add one fp32 add, not fused), the division
+ *     correctly rounded; the fp64 sum runs in walk order and the result is (float)(-sum) — reproducible in plain C with contraction off.
+ *     Consequences of the reference's rule: a point exactly on the root's CoM gets 0, a point far outside the single root term.  Without a
+ *     valid last tree NBODY_ERR_STATE, after a tree deeper than 42 levels NBODY_ERR_UNSUPPORTED, as nbody_field_at reports them.
+ *   n == 0 is a no-op; NULL pointers, n < 0, stride < 12 and phi_stride < 4 are NBODY_ERR_INVALID.  The call synchronises and changes
+ *   nothing a getter of the state shows; its device time counts as one pass under NBODY_KERNEL_FORCES, as a field query's does.
+ *
+ * nbody_get_potentials: every body's potential from all OTHER bodies at the CURRENT positions — n_total floats, `stride` bytes apart (>= 4).
+ *   theta == 0: the sum above with the body itself left out BY INDEX (not by subtracting G m_i / eps afterwards); other bodies on the same
+ *     point are skipped when eps == 0, as nbody_energy skips them.  Changes nothing a getter shows.
+ *   theta > 0: the call first runs exactly what nbody_compute_forces runs — the tree of the current positions is built, the next frame's
+ *     root centre stays, the stored accelerations (the tracers' too) become those of the current positions — and then walks that tree
+ *     from every body, which meets its own leaf at d == 0.  Side effects: as after nbody_compute_forces.  A refused frame returns that
+ *     frame's error and no potentials.
+ *
+ * nbody_energy_fast: ke = 1/2 sum m_i v_i^2 in fp64, as nbody_energy computes it; pe = 1/2 sum m_i phi_i with phi_i the UNROUNDED fp64
+ *   per-body potentials of nbody_get_potentials (the fp64 fold at theta == 0, the fp64 walk sum at theta > 0), reduced in fp64 in a fixed
+ *   order without atomics: the same bits every run.  At theta > 0 it costs about one force pass where nbody_energy evaluates all pairs; its
+ *   potential is that of the opening rule's monopoles.  Synchronises; side effects as nbody_get_potentials.  Either output may be NULL.
+ */
+NBODY_AMD_API int nbody_potential_at(nbody_ctx *ctx, const float *xyz, size_t stride, int32_t n, float *phi, size_t phi_stride);
+NBODY_AMD_API int nbody_get_potentials(nbody_ctx *ctx, float *phi, size_t stride);
+NBODY_AMD_API int nbody_energy_fast(nbody_ctx *ctx, double *ke, double *pe);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -47,6 +47,10 @@ def main(argv=None):
     ap.add_argument("--precision", default="f32", choices=["f32", "f32_kahan", "f64"])
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--energy-every", type=int, default=0, help="print kinetic/potential energy every K frames")
+    ap.add_argument("--fast-energy", action="store_true",
+                    help="energy lines come from energy_fast(): the potential energy from the per-body potentials — at theta > 0 the "
+                         "walk of the tree of the current positions, about one force pass instead of all pairs (plain f32 only; at "
+                         "theta > 0 the stored accelerations become those of the current positions, the trajectory is unchanged)")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -86,7 +90,7 @@ def main(argv=None):
             e.set_state(p0, v0)
 
         def energies():
-            ke, pe = e.energy()
+            ke, pe = e.energy_fast() if a.fast_energy else e.energy()
             out = {"kinetic": ke, "potential": pe, "total": ke + pe}
             if a.sync_energy:
                 e.compute_forces()                               # a(x_n); positions and velocities are not touched

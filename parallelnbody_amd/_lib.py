@@ -113,6 +113,9 @@ def lib():
     sig("nbody_bh_leaf_boxes", c_int, vp, fp, sz)
     sig("nbody_bh_leaf_order", c_int, vp, ctypes.POINTER(c_i32))
     sig("nbody_field_at", c_int, vp, vp, sz, c_i32, vp, sz)
+    sig("nbody_potential_at", c_int, vp, vp, sz, c_i32, vp, sz)
+    sig("nbody_get_potentials", c_int, vp, vp, sz)
+    sig("nbody_energy_fast", c_int, vp, dp, dp)
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

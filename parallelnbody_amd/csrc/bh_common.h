@@ -547,6 +547,10 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
 template <bool HOP, bool SOFT>
 __global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *__restrict__ pts, float4 *__restrict__ vel,
                                                            float4 *__restrict__ acc, int m, double G, float eps2, float dt);
+// kernels_bh_pot.hip: the potential from the same walk (BODY: from every body, in key order, pts = posm)
+template <bool HOP, bool SOFT, bool BODY>
+__global__ __launch_bounds__(kB) void bh_pot_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ phi64,
+                                                         float *__restrict__ phif, int m, double G, float eps2);
 
 }  // namespace bh
 }  // namespace nbody

@@ -531,6 +531,26 @@ hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, dou
   return hipGetLastError();
 }
 
+// The potential from the walk of the last tree (bh_pot_walk_kernel): from m points, or — pts == nullptr — from the b->n bodies themselves.
+template <bool BODY>
+static void launch_pot_walk(BhState *b, const float4 *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s) {
+  const dim3 grd((m + kB - 1) / kB), blk(kB);
+  const bool soft = eps2 > 0.0f;
+  if (b->st.hop != nullptr)
+    hipLaunchKernelGGL((soft ? bh_pot_walk_kernel<true, true, BODY> : bh_pot_walk_kernel<true, false, BODY>), grd, blk, 0, s, b->st, pts,
+                       phi64, phif, m, G, eps2);
+  else
+    hipLaunchKernelGGL((soft ? bh_pot_walk_kernel<false, true, BODY> : bh_pot_walk_kernel<false, false, BODY>), grd, blk, 0, s, b->st, pts,
+                       phi64, phif, m, G, eps2);
+}
+hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s) {
+  if (m <= 0 || !posm || (!phi64 && !phif) || b->last_deep) return hipErrorInvalidValue;
+  if (pts != nullptr) launch_pot_walk<false>(b, (const float4 *)pts, phi64, phif, m, G, eps2, s);
+  else if (m != b->n) return hipErrorInvalidValue;
+  else launch_pot_walk<true>(b, (const float4 *)posm, phi64, phif, m, G, eps2, s);
+  return hipGetLastError();
+}
+
 void bh_set_div_mode(BhState *b, int div_mode) { b->div_mode = div_mode ? 1 : 0; }
 
 // The deepest tree the context answers (42 .. kDeepMaxLevels; nbody_set_bh_max_depth).  Above 42 the deep frames' buffers are made

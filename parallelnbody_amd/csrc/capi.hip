@@ -838,7 +838,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1600,6 +1600,55 @@ int probes_supported(nbody_ctx *c, const char *who) {
     return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
   return NBODY_OK;
 }
+
+// the queries' staging: [2][probe_cap] float4 on the device and its pinned mirror, grown on demand
+int ensure_probe_staging(nbody_ctx *c, int n) {
+  if ((size_t)n <= c->probe_cap) return NBODY_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->probe_dev) (void)hipFree(c->probe_dev);
+  if (c->probe_host) (void)hipHostFree(c->probe_host);
+  c->probe_dev = c->probe_host = nullptr; c->probe_cap = 0;
+  HIP_TRY(c, hipMalloc(&c->probe_dev, (size_t)n * 32));
+  HIP_TRY(c, hipHostMalloc(&c->probe_host, (size_t)n * 32, hipHostMallocDefault));
+  c->probe_cap = (size_t)n;
+  return NBODY_OK;
+}
+
+// theta > 0: is there a tree a query may walk?  (nbody_field_at's rules and messages)
+int probe_tree_ready(nbody_ctx *c, const char *who, const char *what) {
+  if (!c->bh || !c->bh_tree_valid || c->bh_tree_theta != c->theta)
+    return fail(c, NBODY_ERR_STATE, "%s: theta > 0 walks the last tree built, and there is none for this opening angle "
+                "(none built yet, the last frame refused, or theta changed since): call nbody_compute_forces, nbody_step or nbody_tick first", who);
+  if (nbody::bh_last_deep(c->bh))
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: the last tree was built deeper than 42 levels (nbody_set_bh_max_depth); "
+                "such trees answer no %s queries", who, what);
+  return NBODY_OK;
+}
+
+// The bodies' potentials at their CURRENT positions, queued on the stream as one pass under NBODY_KERNEL_FORCES: phi64 ([n_total] double,
+// device) and / or phif ([n_total] float, device).  theta > 0: first exactly what nbody_compute_forces runs (the tree of the current
+// positions, the stored accelerations, the tracers'), then the walk of that tree from every body.
+int queue_body_potentials(nbody_ctx *c, const char *who, double *phi64, float *phif) {
+  int rc;
+  const int n = c->p.n_total;
+  if (c->theta > 0.0f) {
+    if ((rc = run_forces(c, true, 0, 0.0f))) return rc;            // (a refused frame: its error, no potentials)
+    if ((rc = run_update(c, 0.0f))) return rc;
+    if ((rc = probe_tree_ready(c, who, "potential"))) return rc;
+    return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+      HIP_TRY(c, nbody::bh_pot_walk(c->bh, c->posm, nullptr, phi64, phif, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
+      return NBODY_OK;
+    });
+  }
+  if ((rc = ensure_probe_part(c, n))) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::PotLaunch L;
+    L.posm = c->posm; L.probe = nullptr; L.part = c->probe_part; L.phi64 = phi64; L.phif = phif;
+    L.n_total = n; L.m = n; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
+    HIP_TRY(c, nbody::launch_pot(L, c->stream));
+    return NBODY_OK;
+  });
+}
 }  // namespace
 
 int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *acc, size_t acc_stride) {
@@ -1621,15 +1670,7 @@ int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, flo
     if ((rc = ensure_floor(c))) return rc;
     if ((rc = ensure_probe_part(c, n))) return rc;
   }
-  if ((size_t)n > c->probe_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->probe_dev) (void)hipFree(c->probe_dev);
-    if (c->probe_host) (void)hipHostFree(c->probe_host);
-    c->probe_dev = c->probe_host = nullptr; c->probe_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->probe_dev, (size_t)n * 32));
-    HIP_TRY(c, hipHostMalloc(&c->probe_host, (size_t)n * 32, hipHostMallocDefault));
-    c->probe_cap = (size_t)n;
-  }
+  if ((rc = ensure_probe_staging(c, n))) return rc;
   float *h_pts = (float *)c->probe_host, *h_acc = h_pts + 4 * (size_t)n;
   float *d_pts = (float *)c->probe_dev, *d_acc = d_pts + 4 * (size_t)n;
   for (size_t k = 0; k < (size_t)n; ++k) {
@@ -1648,6 +1689,80 @@ int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, flo
   HIP_TRY(c, hipMemcpyAsync(h_acc, d_acc, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)acc + k * acc_stride, h_acc + 4 * k, 12);
+  return NBODY_OK;
+}
+
+int nbody_potential_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *phi, size_t phi_stride) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_potential_at");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_potential_at"))) return rc;
+  if (n < 0 || !xyz || !phi || stride < 12 || phi_stride < 4)
+    return fail(c, NBODY_ERR_INVALID, "nbody_potential_at: null buffer, n < 0, a point stride < 12 or a potential stride < 4");
+  if (n == 0) return NBODY_OK;
+  if (c->theta > 0.0f) {
+    if ((rc = probe_tree_ready(c, "nbody_potential_at", "potential"))) return rc;
+  } else {
+    if ((rc = ensure_probe_part(c, n))) return rc;
+  }
+  if ((rc = ensure_probe_staging(c, n))) return rc;
+  float *h_pts = (float *)c->probe_host, *h_phi = h_pts + 4 * (size_t)n;
+  float *d_pts = (float *)c->probe_dev, *d_phi = d_pts + 4 * (size_t)n;
+  for (size_t k = 0; k < (size_t)n; ++k) {
+    memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
+    h_pts[4 * k + 3] = 0.0f;
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    if (c->theta > 0.0f) {
+      HIP_TRY(c, nbody::bh_pot_walk(c->bh, c->posm, d_pts, nullptr, d_phi, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
+      return NBODY_OK;
+    }
+    nbody::PotLaunch L;
+    L.posm = c->posm; L.probe = d_pts; L.part = c->probe_part; L.phif = d_phi;
+    L.n_total = c->p.n_total; L.m = n; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
+    HIP_TRY(c, nbody::launch_pot(L, c->stream));
+    return NBODY_OK;
+  });                                                              // (a query's device time counts as a pass under NBODY_KERNEL_FORCES)
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h_phi, d_phi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)phi + k * phi_stride, h_phi + k, 4);
+  return NBODY_OK;
+}
+
+int nbody_get_potentials(nbody_ctx *c, float *phi, size_t stride) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_get_potentials");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_get_potentials"))) return rc;
+  if (!phi || stride < 4) return fail(c, NBODY_ERR_INVALID, "nbody_get_potentials: null buffer or stride < 4");
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * 4))) return rc;
+  if ((rc = queue_body_potentials(c, "nbody_get_potentials", nullptr, (float *)c->d_stage))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (stride == 4) memcpy(phi, c->h_stage, n * 4);
+  else for (size_t k = 0; k < n; ++k) memcpy((char *)phi + k * stride, (const char *)c->h_stage + k * 4, 4);
+  return NBODY_OK;
+}
+
+int nbody_energy_fast(nbody_ctx *c, double *ke, double *pe) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_energy_fast");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_energy_fast"))) return rc;
+  const int n = c->p.n_total;
+  if (!c->pot64) HIP_TRY(c, hipMalloc(&c->pot64, ((size_t)n + 2 * (size_t)nbody::energy_fast_slots(n)) * sizeof(double)));
+  double *phi64 = (double *)c->pot64, *partials = phi64 + n;
+  if ((rc = queue_body_potentials(c, "nbody_energy_fast", phi64, nullptr))) return rc;
+  HIP_TRY(c, nbody::launch_energy_fast(c->posm, c->vel, phi64, n, partials, (double *)c->scratch, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  double v[2];
+  memcpy(v, c->h_scratch, 16);
+  if (ke) *ke = v[0];
+  if (pe) *pe = v[1];
   return NBODY_OK;
 }
 

@@ -92,6 +92,7 @@ struct nbody_ctx {
   size_t probe_part_elems = 0;
   void *probe_dev = nullptr, *probe_host = nullptr;   // nbody_field_at: [2][probe_cap] float4 — the points, their accelerations — on the device, and its pinned mirror
   size_t probe_cap = 0;
+  void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];

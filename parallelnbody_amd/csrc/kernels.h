@@ -98,6 +98,27 @@ inline size_t probe_part_elems(int n_total, int m) {            // float4 elemen
 }
 hipError_t launch_probe(const ProbeLaunch &L, hipStream_t s);
 
+// The bodies' potential at theta = 0 — kernels_pot.hip: phi[k] = -sum_j G m_j / sqrt(|probe[k] - x_j|^2 + eps2) over all n_total bodies:
+// fp32 terms, one fused chain per chunk of probe_geometry in body order, the chunks' rows added in chunk order in fp64, negated.  With
+// eps2 == 0 a pair at distance 0 adds nothing.  probe == nullptr: the points are the bodies themselves (m == n_total) and every body
+// leaves itself out by index.  phi64 gets the fp64 value, phif the value rounded once; either may be null.
+struct PotLaunch {
+  const void *posm = nullptr;   // [n_total] float4: x, y, z, m
+  const void *probe = nullptr;  // [m] float4: x, y, z, unused; nullptr: posm
+  void *part = nullptr;         // the staging area of ProbeLaunch::part (one float per point and chunk of a slab: a quarter of it)
+  double *phi64 = nullptr;      // [m]
+  float *phif = nullptr;        // [m]
+  int n_total = 0, m = 0;
+  double G = 0.0, eps2 = 0.0;
+  void *clk = nullptr;
+};
+hipError_t launch_pot(const PotLaunch &L, hipStream_t s);
+// out[0] = sum_i 1/2 m_i v_i^2, out[1] = sum_i 1/2 m_i phi64[i] over n bodies (fp32 posm / vel), in a fixed order: per-workgroup pairs
+// into `partials` (2 * energy_fast_slots(n) doubles), then one workgroup folds them — no atomics, reproducible bits.
+constexpr int kEnergyFastSlots = 1024;
+int energy_fast_slots(int n);
+hipError_t launch_energy_fast(const void *posm, const void *vel, const double *phi64, int n, double *partials, double *out, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {
@@ -210,6 +231,10 @@ hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s);
 // the frame's verdict and does nothing behind a frame refused or given up; it writes neither the verdict nor the tree.  dt > 0: the points
 // are tracers and get the bodies' kick-drift on (pts, vel) behind their walk.  Not for the tree of a deep frame (bh_last_deep).
 hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, double G, float eps2, float dt, hipStream_t s);
+// The potential from the same walk (kernels_bh_pot.hip): an accepted node adds G * M / ds in fp64, ds = sqrtf(d2 + eps2) correctly rounded;
+// phi = -(the fp64 sum in walk order) to phi64 and, rounded, to phif (either may be null).  pts == nullptr: the points are the bodies
+// (posm, n of them), walked in key order and written at the body's index — a body meets its own leaf at d == 0, which adds nothing.
+hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s);
 bool bh_last_deep(const BhState *b);                          // the last frame queued was built by the deep path
 hipError_t bh_get_root_com(BhState *b, float out[3], hipStream_t s);
 hipError_t bh_set_root_com(BhState *b, const float in[3], hipStream_t s);

@@ -277,6 +277,34 @@ class NBodyEngine:
         self._check(self._L.nbody_field_at(self._h, p.ctypes.data, max(p.strides[0], 12), p.shape[0], out.ctypes.data, 12))
         return out
 
+    # -- the potential --
+    def potential_at(self, points):
+        """The bodies' gravitational potential at every row of `points` (nbody_potential_at): [n] float32.  points: as for field_at.
+        theta > 0: the walk of the last tree built (include/nbody.h)."""
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] < 3:
+            raise ValueError("potential_at: points must be [n, >= 3]")
+        p = p[:, :3]
+        if p.dtype != np.float32 or p.shape[0] < 2 or p.strides[1] != 4 or p.strides[0] < 12:
+            p = np.ascontiguousarray(p, np.float32)
+        out = np.empty(p.shape[0], np.float32)
+        self._check(self._L.nbody_potential_at(self._h, p.ctypes.data, max(p.strides[0], 12), p.shape[0], out.ctypes.data, 4))
+        return out
+
+    def potentials(self):
+        """Every body's potential from all other bodies at the current positions (nbody_get_potentials): [n_total] float32.
+        theta > 0: builds the tree of the current positions first — side effects as after compute_forces()."""
+        out = np.empty(self.n_total, np.float32)
+        self._check(self._L.nbody_get_potentials(self._h, out.ctypes.data, 4))
+        return out
+
+    def energy_fast(self):
+        """(ke, pe) from the per-body potentials (nbody_energy_fast): at theta > 0 about one force pass instead of all pairs.
+        Side effects as potentials()."""
+        ke, pe = ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.nbody_energy_fast(self._h, ctypes.byref(ke), ctypes.byref(pe)))
+        return ke.value, pe.value
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
