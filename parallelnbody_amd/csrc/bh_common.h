@@ -4,6 +4,7 @@
 //   kernels_bh_sort.hip    the larger systems' path keys and their order: the sort from the previous frame's order, the cold sorts
 //   kernels_bh_build.hip   shared digits + node numbering, node words and leaves, ComputeMass (chunks + top, or a launch per level)
 //   kernels_bh_walk.hip    Octree::ComputeForces: the walks (wave / sixteen lanes / one lane per body), the Tick's update behind them
+//   kernels_bh_pot.hip     the walk of the last tree from a point, written once: the field (bh_probe_walk_kernel), the potential
 //   bh_frame.hip           the host side: BhState, one frame queued on the stream (bh_frame), the verdict (bh_collect)
 // Here: the constants and the compact tree (SmallTree) the kernels and the host agree on, the device helpers more than one file
 // uses — each a restatement of a line of the reference, cited where it stands — and the kernels' declarations.
@@ -543,11 +544,11 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
                                                           float4 *__restrict__ acc, int n, double G, float dt, float *__restrict__ stage,
                                                           unsigned int *__restrict__ next_size, float4 *__restrict__ pos_sorted,
                                                           WalkSlice S);
-// the walk of the last tree from points that are not bodies (HOP: on the hop words, where the tree has them)
+// kernels_bh_pot.hip: the walk of the last tree from points that are not bodies (HOP: on the hop words, where the tree has them)
 template <bool HOP, bool SOFT>
 __global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *__restrict__ pts, float4 *__restrict__ vel,
                                                            float4 *__restrict__ acc, int m, double G, float eps2, float dt);
-// kernels_bh_pot.hip: the potential from the same walk (BODY: from every body, in key order, pts = posm)
+// the potential from the same walk (BODY: from every body, in key order, pts = posm)
 template <bool HOP, bool SOFT, bool BODY>
 __global__ __launch_bounds__(kB) void bh_pot_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ phi64,
                                                          float *__restrict__ phif, int m, double G, float eps2);

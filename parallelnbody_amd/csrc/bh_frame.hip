@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "bh_common.h"
 #include "bh_deep_path.h"
@@ -516,38 +517,36 @@ hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s) {
 
 bool bh_last_deep(const BhState *b) { return b->last_deep; }
 
+// The walks of the last tree from points (kernels_bh_pot.hip), one lane per point: pick(hop, soft) names the kernel's instantiation for a
+// tree with hop words (the larger systems') and for eps2 > 0; args follow the tree in the kernel's parameters.
+template <class Pick, class... Args>
+static void launch_point_walk(BhState *b, int m, float eps2, hipStream_t s, Pick pick, Args... args) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  const bool hop = b->st.hop != nullptr, soft = eps2 > 0.0f;
+  const auto kernel = hop ? (soft ? pick(yes, yes) : pick(yes, no)) : (soft ? pick(no, yes) : pick(no, no));
+  hipLaunchKernelGGL(kernel, dim3((m + kB - 1) / kB), dim3(kB), 0, s, b->st, args...);
+}
+
 // The walk of the last tree from m points that are not bodies (bh_probe_walk_kernel), queued on the stream behind the frame that
 // builds it — or behind nothing, for a query of the tree that is there.  b->st is the tree of every frame but a deep one.
 hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, double G, float eps2, float dt, hipStream_t s) {
   if (m <= 0 || !pts || !acc || (dt > 0.0f && !vel) || b->last_deep) return hipErrorInvalidValue;
-  const dim3 grd((m + kB - 1) / kB), blk(kB);
-  const bool soft = eps2 > 0.0f;
-  if (b->st.hop != nullptr)
-    hipLaunchKernelGGL((soft ? bh_probe_walk_kernel<true, true> : bh_probe_walk_kernel<true, false>), grd, blk, 0, s, b->st, (float4 *)pts,
-                       (float4 *)vel, (float4 *)acc, m, G, eps2, dt);
-  else
-    hipLaunchKernelGGL((soft ? bh_probe_walk_kernel<false, true> : bh_probe_walk_kernel<false, false>), grd, blk, 0, s, b->st, (float4 *)pts,
-                       (float4 *)vel, (float4 *)acc, m, G, eps2, dt);
+  launch_point_walk(b, m, eps2, s, [](auto hop, auto soft) { return bh_probe_walk_kernel<decltype(hop)::value, decltype(soft)::value>; },
+                    (float4 *)pts, (float4 *)vel, (float4 *)acc, m, G, eps2, dt);
   return hipGetLastError();
 }
 
 // The potential from the walk of the last tree (bh_pot_walk_kernel): from m points, or — pts == nullptr — from the b->n bodies themselves.
-template <bool BODY>
-static void launch_pot_walk(BhState *b, const float4 *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s) {
-  const dim3 grd((m + kB - 1) / kB), blk(kB);
-  const bool soft = eps2 > 0.0f;
-  if (b->st.hop != nullptr)
-    hipLaunchKernelGGL((soft ? bh_pot_walk_kernel<true, true, BODY> : bh_pot_walk_kernel<true, false, BODY>), grd, blk, 0, s, b->st, pts,
-                       phi64, phif, m, G, eps2);
-  else
-    hipLaunchKernelGGL((soft ? bh_pot_walk_kernel<false, true, BODY> : bh_pot_walk_kernel<false, false, BODY>), grd, blk, 0, s, b->st, pts,
-                       phi64, phif, m, G, eps2);
-}
 hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s) {
   if (m <= 0 || !posm || (!phi64 && !phif) || b->last_deep) return hipErrorInvalidValue;
-  if (pts != nullptr) launch_pot_walk<false>(b, (const float4 *)pts, phi64, phif, m, G, eps2, s);
-  else if (m != b->n) return hipErrorInvalidValue;
-  else launch_pot_walk<true>(b, (const float4 *)posm, phi64, phif, m, G, eps2, s);
+  if (pts == nullptr && m != b->n) return hipErrorInvalidValue;
+  if (pts != nullptr)
+    launch_point_walk(b, m, eps2, s, [](auto hop, auto soft) { return bh_pot_walk_kernel<decltype(hop)::value, decltype(soft)::value, false>; },
+                      (const float4 *)pts, phi64, phif, m, G, eps2);
+  else
+    launch_point_walk(b, m, eps2, s, [](auto hop, auto soft) { return bh_pot_walk_kernel<decltype(hop)::value, decltype(soft)::value, true>; },
+                      (const float4 *)posm, phi64, phif, m, G, eps2);
   return hipGetLastError();
 }
 

@@ -1590,6 +1590,8 @@ int nbody_bh_leaf_order(nbody_ctx *c, int32_t *order) {
   return NBODY_OK;
 }
 
+}  // extern "C"
+
 // ---- the field at points that are not bodies: queries (nbody_field_at) and engine-stepped tracers ----
 namespace {
 // where they exist: plain fp32 contexts on one device that own all bodies
@@ -1614,7 +1616,7 @@ int ensure_probe_staging(nbody_ctx *c, int n) {
   return NBODY_OK;
 }
 
-// theta > 0: is there a tree a query may walk?  (nbody_field_at's rules and messages)
+// theta > 0: is there a tree a query may walk?  (`what`: "field", "potential")
 int probe_tree_ready(nbody_ctx *c, const char *who, const char *what) {
   if (!c->bh || !c->bh_tree_valid || c->bh_tree_theta != c->theta)
     return fail(c, NBODY_ERR_STATE, "%s: theta > 0 walks the last tree built, and there is none for this opening angle "
@@ -1622,6 +1624,16 @@ int probe_tree_ready(nbody_ctx *c, const char *who, const char *what) {
   if (nbody::bh_last_deep(c->bh))
     return fail(c, NBODY_ERR_UNSUPPORTED, "%s: the last tree was built deeper than 42 levels (nbody_set_bh_max_depth); "
                 "such trees answer no %s queries", who, what);
+  return NBODY_OK;
+}
+
+// theta == 0: the potential of the bodies at their CURRENT positions at m points, queued (G and eps the context's; eps == 0: the exact
+// d == 0 rule whatever its zero_mode is).  probe == nullptr: at the bodies themselves (m == n_total).
+int queue_pot(nbody_ctx *c, const void *probe, int m, double *phi64, float *phif) {
+  nbody::PotLaunch L;
+  L.posm = c->posm; L.probe = probe; L.part = c->probe_part; L.phi64 = phi64; L.phif = phif;
+  L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
+  HIP_TRY(c, nbody::launch_pot(L, c->stream));
   return NBODY_OK;
 }
 
@@ -1641,94 +1653,64 @@ int queue_body_potentials(nbody_ctx *c, const char *who, double *phi64, float *p
     });
   }
   if ((rc = ensure_probe_part(c, n))) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::PotLaunch L;
-    L.posm = c->posm; L.probe = nullptr; L.part = c->probe_part; L.phi64 = phi64; L.phif = phif;
-    L.n_total = n; L.m = n; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
-    HIP_TRY(c, nbody::launch_pot(L, c->stream));
-    return NBODY_OK;
-  });
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return queue_pot(c, nullptr, n, phi64, phif); });
+}
+
+// One query at points that are not bodies: n points from (xyz, stride) in, `width` floats each out to (out, out_stride) — the
+// arguments' checks (`bad_args`: the message of a bad one), the tree or the partial rows the launch needs, the points as float4
+// through the pinned staging, launch(d_pts, d_out) timed as a pass under NBODY_KERNEL_FORCES, the values back (d_out: a float4 per
+// point for width 3, a float for width 1).  floor: the query follows the context's NBODY_ZERO_FLOOR.
+template <class Launch>
+int query_points(nbody_ctx *c, const char *who, const char *what, const char *bad_args, bool floor, const float *xyz, size_t stride,
+                 int32_t n, float *out, size_t out_stride, int width, Launch launch) {
+  if (c && c->multi) return multi_unsupported(c, who);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, who))) return rc;
+  if (n < 0 || !xyz || !out || stride < 12 || out_stride < 4 * (size_t)width) return fail(c, NBODY_ERR_INVALID, "%s: %s", who, bad_args);
+  if (n == 0) return NBODY_OK;
+  if (c->theta > 0.0f) {
+    if ((rc = probe_tree_ready(c, who, what))) return rc;
+  } else {
+    if (floor && (rc = ensure_floor(c))) return rc;
+    if ((rc = ensure_probe_part(c, n))) return rc;
+  }
+  if ((rc = ensure_probe_staging(c, n))) return rc;
+  const size_t out_floats = width == 3 ? 4 : 1;
+  float *h_pts = (float *)c->probe_host, *h_out = h_pts + 4 * (size_t)n;
+  float *d_pts = (float *)c->probe_dev, *d_out = d_pts + 4 * (size_t)n;
+  for (size_t k = 0; k < (size_t)n; ++k) {
+    memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
+    h_pts[4 * k + 3] = 0.0f;
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return launch(d_pts, d_out); }))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h_out, d_out, (size_t)n * out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)out + k * out_stride, h_out + out_floats * k, 4 * (size_t)width);
+  return NBODY_OK;
 }
 }  // namespace
 
+extern "C" {
+
 int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *acc, size_t acc_stride) {
-  if (c && c->multi) return multi_unsupported(c, "nbody_field_at");
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if ((rc = probes_supported(c, "nbody_field_at"))) return rc;
-  if (n < 0 || !xyz || !acc || stride < 12 || acc_stride < 12)
-    return fail(c, NBODY_ERR_INVALID, "nbody_field_at: null buffer, n < 0 or a stride < 12");
-  if (n == 0) return NBODY_OK;
-  if (c->theta > 0.0f) {
-    if (!c->bh || !c->bh_tree_valid || c->bh_tree_theta != c->theta)
-      return fail(c, NBODY_ERR_STATE, "nbody_field_at: theta > 0 walks the last tree built, and there is none for this opening angle "
-                  "(none built yet, the last frame refused, or theta changed since): call nbody_compute_forces, nbody_step or nbody_tick first");
-    if (nbody::bh_last_deep(c->bh))
-      return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_field_at: the last tree was built deeper than 42 levels (nbody_set_bh_max_depth); "
-                  "such trees answer no field queries");
-  } else {
-    if ((rc = ensure_floor(c))) return rc;
-    if ((rc = ensure_probe_part(c, n))) return rc;
-  }
-  if ((rc = ensure_probe_staging(c, n))) return rc;
-  float *h_pts = (float *)c->probe_host, *h_acc = h_pts + 4 * (size_t)n;
-  float *d_pts = (float *)c->probe_dev, *d_acc = d_pts + 4 * (size_t)n;
-  for (size_t k = 0; k < (size_t)n; ++k) {
-    memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
-    h_pts[4 * k + 3] = 0.0f;
-  }
-  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    if (c->theta > 0.0f) {
-      HIP_TRY(c, nbody::bh_probe_walk(c->bh, d_pts, nullptr, d_acc, n, c->p.G, (float)(c->p.eps * c->p.eps), 0.0f, c->stream));
-      return NBODY_OK;
-    }
-    return queue_probe(c, d_pts, nullptr, d_acc, n, 0.0f);
-  });                                                              // (a query's device time counts as a pass under NBODY_KERNEL_FORCES)
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h_acc, d_acc, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)acc + k * acc_stride, h_acc + 4 * k, 12);
-  return NBODY_OK;
+  return query_points(c, "nbody_field_at", "field", "null buffer, n < 0 or a stride < 12", true, xyz, stride, n, acc, acc_stride, 3,
+                      [&](float *d_pts, float *d_acc) -> int {
+    if (!(c->theta > 0.0f)) return queue_probe(c, d_pts, nullptr, d_acc, n, 0.0f);
+    HIP_TRY(c, nbody::bh_probe_walk(c->bh, d_pts, nullptr, d_acc, n, c->p.G, (float)(c->p.eps * c->p.eps), 0.0f, c->stream));
+    return NBODY_OK;
+  });
 }
 
+// (no ensure_floor: the potential's d == 0 rule is the same under every zero_mode)
 int nbody_potential_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *phi, size_t phi_stride) {
-  if (c && c->multi) return multi_unsupported(c, "nbody_potential_at");
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if ((rc = probes_supported(c, "nbody_potential_at"))) return rc;
-  if (n < 0 || !xyz || !phi || stride < 12 || phi_stride < 4)
-    return fail(c, NBODY_ERR_INVALID, "nbody_potential_at: null buffer, n < 0, a point stride < 12 or a potential stride < 4");
-  if (n == 0) return NBODY_OK;
-  if (c->theta > 0.0f) {
-    if ((rc = probe_tree_ready(c, "nbody_potential_at", "potential"))) return rc;
-  } else {
-    if ((rc = ensure_probe_part(c, n))) return rc;
-  }
-  if ((rc = ensure_probe_staging(c, n))) return rc;
-  float *h_pts = (float *)c->probe_host, *h_phi = h_pts + 4 * (size_t)n;
-  float *d_pts = (float *)c->probe_dev, *d_phi = d_pts + 4 * (size_t)n;
-  for (size_t k = 0; k < (size_t)n; ++k) {
-    memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
-    h_pts[4 * k + 3] = 0.0f;
-  }
-  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-  rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    if (c->theta > 0.0f) {
-      HIP_TRY(c, nbody::bh_pot_walk(c->bh, c->posm, d_pts, nullptr, d_phi, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
-      return NBODY_OK;
-    }
-    nbody::PotLaunch L;
-    L.posm = c->posm; L.probe = d_pts; L.part = c->probe_part; L.phif = d_phi;
-    L.n_total = c->p.n_total; L.m = n; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
-    HIP_TRY(c, nbody::launch_pot(L, c->stream));
+  return query_points(c, "nbody_potential_at", "potential", "null buffer, n < 0, a point stride < 12 or a potential stride < 4", false, xyz,
+                      stride, n, phi, phi_stride, 1, [&](float *d_pts, float *d_phi) -> int {
+    if (!(c->theta > 0.0f)) return queue_pot(c, d_pts, n, nullptr, d_phi);
+    HIP_TRY(c, nbody::bh_pot_walk(c->bh, c->posm, d_pts, nullptr, d_phi, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
     return NBODY_OK;
-  });                                                              // (a query's device time counts as a pass under NBODY_KERNEL_FORCES)
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h_phi, d_phi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)phi + k * phi_stride, h_phi + k, 4);
-  return NBODY_OK;
+  });
 }
 
 int nbody_get_potentials(nbody_ctx *c, float *phi, size_t stride) {

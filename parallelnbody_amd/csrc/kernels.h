@@ -98,7 +98,7 @@ inline size_t probe_part_elems(int n_total, int m) {            // float4 elemen
 }
 hipError_t launch_probe(const ProbeLaunch &L, hipStream_t s);
 
-// The bodies' potential at theta = 0 — kernels_pot.hip: phi[k] = -sum_j G m_j / sqrt(|probe[k] - x_j|^2 + eps2) over all n_total bodies:
+// The bodies' potential at theta = 0 — kernels_probe.hip: phi[k] = -sum_j G m_j / sqrt(|probe[k] - x_j|^2 + eps2) over all n_total bodies:
 // fp32 terms, one fused chain per chunk of probe_geometry in body order, the chunks' rows added in chunk order in fp64, negated.  With
 // eps2 == 0 a pair at distance 0 adds nothing.  probe == nullptr: the points are the bodies themselves (m == n_total) and every body
 // leaves itself out by index.  phi64 gets the fp64 value, phif the value rounded once; either may be null.
@@ -226,12 +226,12 @@ hipError_t bh_leaf_order(BhState *b, int *out_host, hipStream_t s);
 hipError_t bh_stats(BhState *b, hipStream_t s, int *nodes, int *levels);   // waits for the stream when the last tree's counts are still on their way
 // out[body] = (ox, oy, oz, Size) of the leaf holding the body, for the last tree built
 hipError_t bh_leaf_boxes(BhState *b, void *out, hipStream_t s);
-// Octree::ComputeForces (OctreeSearch.h:99-108) from m points that are not bodies (pts: float4 x, y, z, unused), over the tree the
+// Octree::ComputeForces (OctreeSearch.h:99-108) from m points that are not bodies (kernels_bh_pot.hip; pts: float4 x, y, z, unused), over the tree the
 // frame queued last on `s` has built — the body walks' step test and term, one lane per point in the caller's order.  The kernel looks at
 // the frame's verdict and does nothing behind a frame refused or given up; it writes neither the verdict nor the tree.  dt > 0: the points
 // are tracers and get the bodies' kick-drift on (pts, vel) behind their walk.  Not for the tree of a deep frame (bh_last_deep).
 hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, double G, float eps2, float dt, hipStream_t s);
-// The potential from the same walk (kernels_bh_pot.hip): an accepted node adds G * M / ds in fp64, ds = sqrtf(d2 + eps2) correctly rounded;
+// The potential from the same walk: an accepted node adds G * M / ds in fp64, ds = sqrtf(d2 + eps2) correctly rounded;
 // phi = -(the fp64 sum in walk order) to phi64 and, rounded, to phif (either may be null).  pts == nullptr: the points are the bodies
 // (posm, n of them), walked in key order and written at the body's index — a body meets its own leaf at d == 0, which adds nothing.
 hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s);

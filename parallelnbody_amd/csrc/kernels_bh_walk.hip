@@ -1,7 +1,7 @@
 // Octree::ComputeForces (OctreeSearch.h:99-108) on the compact tree, and the Tick's update behind every walk (OctreeSearch.cpp:28-31)
 // — see bh_common.h.
 #include "bh_common.h"
-#include "tracer_update.h"
+#include "bh_force_term.h"
 
 namespace nbody {
 namespace bh {
@@ -10,51 +10,6 @@ template <typename T> __device__ __forceinline__ T mul_add_sep(T a, T b, T c) {
 #pragma clang fp contract(off)
   const T p = a * b;
   return c + p;
-}
-
-// One accepted node's term of Octree::ComputeForces (.h:104): float(G * M / pow(d, 3)) * (CoM - Pos), d = Dist.
-// The walks are bound by the instructions of this term (N = 2^20: 16 000 per wave), so:
-//  * (CoM - Pos) is taken as -(Pos - CoM), the difference the squared distance was made of: a - b and -(b - a) agree in every bit
-//    except that equal operands give +0 and -0 — and such a term goes into a sum that started at +0 and therefore never is -0, so
-//    adding either zero leaves every bit of it alone;
-//  * the correctly rounded square root is v_sqrt_f32 (one ulp) put right by the two fused residuals the compiler's own sqrtf uses,
-//    without its scaling for arguments below 2^-96 and its special cases, and the double-precision division likewise without its
-//    scaling and special cases: a wave with an argument below 2^-96, an infinite / NaN one or a mass that is not finite in any of
-//    its lanes takes sqrtf and the division themselves.
-// SOFT: Plummer softening — the same term of ds = sqrtf(d2 + eps2), one fp32 add (not fused) in front of the root; the fast path and
-// its guard look at ds2 the same way.  Where the walk goes (.h:102-103) is decided on the unsoftened d2 by the walk itself.  false:
-// eps2 is not read, and the term is the reference's, instruction for instruction.
-template <bool SOFT>
-__device__ __forceinline__ void force_term(float cx, float cy, float cz, float M, const float4 &p, double G, float eps2, float &tx,
-                                           float &ty, float &tz) {
-#pragma clang fp contract(off)
-  const float ex = p.x - cx, ey = p.y - cy, ez = p.z - cz;
-  float d2 = ex * ex + ey * ey;
-  d2 = d2 + ez * ez;
-  if constexpr (SOFT) d2 = d2 + eps2;                          // ds2 (eps2 == 0 would leave every bit of d2: it is never -0)
-  float d, s;                                                  // FVector::Dist, .h:101 (correctly rounded); the scale factor
-  if (__any(!(d2 >= 0x1p-96f) || d2 == __builtin_inff() || !(fabsf(M) <= 0x1.fffffep127f))) {
-    d = sqrtf(d2);
-    const double dd = (double)d;
-    s = (float)(G * (double)M / ((dd * dd) * dd));             // (d*d)*d in double = the correctly rounded cube
-  } else {
-    const float r = __builtin_amdgcn_sqrtf(d2);
-    const float below = __uint_as_float(__float_as_uint(r) - 1u), above = __uint_as_float(__float_as_uint(r) + 1u);
-    const float eb = __builtin_fmaf(-below, r, d2), ea = __builtin_fmaf(-above, r, d2);
-    d = eb <= 0.0f ? below : r;
-    d = ea > 0.0f ? above : d;
-    // ... and the correctly rounded double quotient is the compiler's own sequence — reciprocal, two Newton steps, quotient, one
-    // residual step — without the operand scaling and the special cases that cannot occur here: d in [2^-48, 2^64), so d^3 in
-    // [2^-144, 2^192), G M finite: every value on the way is a normal double (a mass of +-0 gives +0 where the division gives the
-    // mass's sign: a term of +-0 either way, which changes no sum).
-    const double dd = (double)d, den = (dd * dd) * dd, num = G * (double)M;
-    double rc = __builtin_amdgcn_rcp(den);
-    rc = __builtin_fma(rc, __builtin_fma(-den, rc, 1.0), rc);
-    rc = __builtin_fma(rc, __builtin_fma(-den, rc, 1.0), rc);
-    const double q0 = num * rc;
-    s = (float)__builtin_fma(__builtin_fma(-den, q0, num), rc, q0);
-  }
-  tx = s * -ex; ty = s * -ey; tz = s * -ez;
 }
 
 // own[]: a count per block of kB sorted positions, then every block adds up the counts before it and ranks its own bodies (two
@@ -698,75 +653,12 @@ __global__ __launch_bounds__(kB) void bh_walk_lane_kernel(SmallTree T, float4 *_
       if (node < nodes) BH_LANE_STEP(cm2, h2, cm, h, S.eps2)
     }
   }
-#endif   // (BH_LANE_STEP stays defined for bh_probe_walk_kernel below)
+#endif
   walk_lane_tail(valid, body, p, ax, ay, az, posm, vel, acc, dt, stage, S.off, next_size, pos_sorted, place);
 }
-
-// Octree::ComputeForces (.h:99-108) from a point that is NOT a body — nbody_field_at's points, the tracers of nbody_set_tracers —, one
-// lane per point in the caller's order, over the tree the last frame left in its global arrays: a leaf's CoM is its body's position and
-// mass, so this is the loop of bh_walk_lane_kernel with the position taken from `pts`, and at a body's own position it gives that body's
-// own sum in every bit (the body meets its own leaf at d == 0, which adds nothing).  HOP: the tree carries hop words (the larger
-// systems') and a step is the lane walk's own, BH_LANE_STEP; otherwise the plain loop on the node words and the levels' thresholds.
-// The same step test, the same force_term.  The kernel reads the frame's verdict and does nothing unless it is 0 — a frame refused,
-// given up or handed back, and every frame queued behind one, leaves tracers where they were —; it neither writes the verdict nor
-// touches the tree.  dt > 0: the point is a tracer and gets the bodies' update behind its walk (.cpp:29-30, multiply and add apart).
-template <bool HOP, bool SOFT>
-__global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *__restrict__ pts, float4 *__restrict__ vel,
-                                                           float4 *__restrict__ acc, int m, double G, float eps2, float dt) {
-#pragma clang fp contract(off)
-  const int k = blockIdx.x * kB + threadIdx.x;
-  const bool valid = k < m;
-  const int status = T.hdr[3], nodes_all = T.hdr[0];
-  if (status != 0) return;
-  const int nodes = valid ? nodes_all : 0;
-  const float4 p = pts[valid ? k : 0];
-  float ax = 0.f, ay = 0.f, az = 0.f;                          // Acceleration = ZeroVector, .cpp:84
-  int node = 0;
-#ifdef BH_LANE_STEP
-  if constexpr (HOP) {
-    float4 cm = T.com[0];
-    uint2 h = T.hop[0];
-    while (node < nodes) {
-      float4 cm2; uint2 h2;
-      BH_LANE_STEP(cm, h, cm2, h2, eps2)
-      cm = cm2; h = h2;
-    }
-  } else
-#endif
-  {
-    __shared__ float s_thr[kMaxLevels + 2];
-    if (threadIdx.x <= kMaxLevels) s_thr[threadIdx.x] = T.thr[threadIdx.x];
-    __syncthreads();
-    while (node < nodes) {
-      const float4 cm = T.com[node];
-      const unsigned int w = T.meta[node];
-      const bool leaf = (w & kLeafBit) != 0u;
-      const int past = leaf ? node + 1 : (int)(w & kLinkMask);
-      const float ex = p.x - cm.x, ey = p.y - cm.y, ez = p.z - cm.z;
-      float d2 = ex * ex + ey * ey;
-      d2 = d2 + ez * ez;
-      const bool take = leaf || d2 >= s_thr[(w >> kLevelShift) & 63u];   // .h:103
-      if (take && d2 != 0.f) {
-        float tx, ty, tz;
-        force_term<SOFT>(cm.x, cm.y, cm.z, cm.w, p, G, eps2, tx, ty, tz);
-        ax = ax + tx; ay = ay + ty; az = az + tz;
-      }
-      node = (take || d2 == 0.f) ? past : node + 1;           // .h:102: d == 0 ends the subtree
-    }
-  }
-  if (!valid) return;
-  acc[k] = make_float4(ax, ay, az, 0.f);
-  if (dt > 0.f) {
-    float4 v = vel[k], x = p;
-    tracer_kick_drift(dt, ax, ay, az, v, x);
-    vel[k] = v;
-    pts[k] = x;
-  }
-}
-#ifdef BH_LANE_STEP
+#ifdef BH_LANE_STEP                                            // (the lane kernel's alone; the walk from a point is kernels_bh_pot.hip's)
 #undef BH_LANE_STEP
 #endif
-
 
 #define BH_WALK_KERNELS(SOFT)                                                                                                          \
   template __global__ void bh_walk_compact_kernel<SOFT>(SmallTree, float4 *, float4 *, float4 *, int, float, double, float, float *,  \
@@ -784,10 +676,6 @@ __global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *
 BH_WALK_KERNELS(false)
 BH_WALK_KERNELS(true)
 #undef BH_WALK_KERNELS
-template __global__ void bh_probe_walk_kernel<false, false>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
-template __global__ void bh_probe_walk_kernel<false, true>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
-template __global__ void bh_probe_walk_kernel<true, false>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
-template __global__ void bh_probe_walk_kernel<true, true>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);
 
 }  // namespace bh
 }  // namespace nbody

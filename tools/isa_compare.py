@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Compare the instruction streams of the kernels two builds have in common, from the gfx950 code objects of their objects.
 
-A kernel of the NEW object whose last template argument is `false` is paired with the OLD kernel of the same name without that
-argument (bh_walk_rows_kernel<false> with bh_walk_rows_kernel, bh_walk_lane_kernel<true, false> with bh_walk_lane_kernel<true>), so
+A kernel is paired with the OLD kernel of the same name and template arguments (kernels in an anonymous namespace by their own
+names).  Where there is none, a kernel of the NEW object whose last template argument is `false` is paired with the OLD kernel of
+the same name without that argument (bh_walk_rows_kernel<false> with bh_walk_rows_kernel, bh_walk_lane_kernel<true, false> with bh_walk_lane_kernel<true>), so
 that a kernel that has gained a compile-time switch can be checked to be, in its `false` form, the kernel it was.  Addresses,
 encodings, comments and the padding behind a function are dropped; branch offsets are relative, so identical code compares equal
 wherever it was placed.
@@ -43,7 +44,7 @@ def kernels(obj, workdir):
 
 def base(name):
     """(name without return type and parameters, template arguments or None)"""
-    name = name.split("(")[0]
+    name = name.replace("(anonymous namespace)::", "").split("(")[0]   # (nbody::(anonymous namespace)::k<..>(..) is nbody::k<..>)
     name = name.split(" ")[-1] if not name.endswith(">") else name[name.rfind(" ", 0, name.find("<")) + 1:]
     if name.endswith(">"):
         i = name.find("<")
@@ -73,10 +74,12 @@ def main():
         old = {key_old(k): v for k, v in kernels(a.old, t_old).items() if a.only in k}
         new = {}
         for k, v in kernels(a.new, t_new).items():
-            if a.only in k and key_new(k) is not None:
-                new[key_new(k)] = v
-            elif a.only in k and base(k)[1] is None:
+            if a.only not in k:
+                continue
+            if key_old(k) in old or base(k)[1] is None:          # the same name on both sides: that pair
                 new[key_old(k)] = v
+            elif key_new(k) is not None:
+                new[key_new(k)] = v
     bad = 0
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
