@@ -297,6 +297,7 @@ def test_energy_fast_against_the_oracle(nb, oracle, name, eps, theta):
         assert e.energy_fast() == (ke, pe)                        # identical bits every run
     print(f"energy_fast {name} eps={eps} theta={theta}: pe rel err {abs(pe - pe0) / abs(pe0):.3e}, ke rel diff {abs(ke - ke1) / abs(ke1):.3e}")
     assert abs(ke - ke1) <= 1e-12 * abs(ke1) and abs(ke - ke0) <= 1e-12 * abs(ke0)
+    assert abs(pe1 - pe0) <= 1e-10 * abs(pe0)                     # the yardstick itself: energy()'s all-pairs potential
     assert abs(pe - pe0) < 2e-5 * abs(pe0)
 
 
