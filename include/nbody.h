@@ -488,9 +488,31 @@ NBODY_AMD_API int nbody_sym_plan_describe_even(int32_t n_total, int32_t bodies_p
 NBODY_AMD_API int32_t nbody_sym_plan_is_even(const nbody_ctx *ctx);
 
 /* Host only: register pairs of bodies (2 ... 8; two bodies each) a workgroup of forces_block_pk_kernel owns for a plain fp32
- * system of n_total bodies on a device with `compute_units` CUs — the rule of csrc/capi.hip (smallest ceil(workgroups /
+ * system of n_total bodies on a device with `compute_units` CUs — the rule of csrc/launch_policy.cpp (smallest ceil(workgroups /
  * CUs) x pairs, larger workgroups on a tie).  No result depends on it; the CPU tests check the rule. */
 NBODY_AMD_API int32_t nbody_block_pairs_describe(int32_t n_total, int32_t compute_units);
+
+/* Host only (no device needed): what a context created with these parameters reports on a device with `compute_units` CUs
+ * (<= 0: 256) and `device_total_bytes` of memory (0: unknown — no plan is refused for its size).  The launch policy is a function
+ * of exactly these inputs (csrc/launch_policy.h), so the CPU tests pin every size threshold through this call.  Set struct_size
+ * first.  Returns the code nbody_create would return for these parameters on such a device (NBODY_OK, NBODY_ERR_INVALID,
+ * NBODY_ERR_UNSUPPORTED); nbody_last_error(NULL) then gives the same text. */
+typedef struct nbody_launch_policy {
+    uint32_t struct_size;
+    int32_t tile, i_per_thread, j_split, blocks, threads;   /* nbody_get_launch_config */
+    int32_t algorithm, super_tile;                          /* nbody_get_algorithm */
+    int32_t plan_is_even;                                   /* nbody_sym_plan_is_even */
+    int32_t phases;                                         /* nbody_sym_pool_info ... */
+    int32_t exchange_ranks;                                 /* nbody_exchange_info: n_ranks */
+    int32_t wave;                                           /* block kernels: register pairs (fp32) / bodies per workgroup; 0 otherwise */
+    int32_t detector_slots;                                 /* hash slots of the coincident-body detector; 0 = none */
+    int32_t sym_slots, sym_min_sub;                         /* symmetric plan: resident workgroups, shortest strip in subtiles ... */
+    double sym_k;                                           /* ... and the strip divisor K (0 for an even-share plan) */
+    uint64_t pool_bytes;                                    /* ... nbody_sym_pool_info */
+    char kernel[64];                                        /* nbody_force_kernel_name */
+} nbody_launch_policy;
+NBODY_AMD_API int nbody_launch_policy_describe(const nbody_params *p, int32_t compute_units, uint64_t device_total_bytes,
+                                               nbody_launch_policy *out);
 
 /* ---- checkpoint / resume (build-defined: the reference keeps its state in a non-serialised TArray) ---------- */
 

@@ -49,6 +49,20 @@ class Params(ctypes.Structure):
     ]
 
 
+class LaunchPolicy(ctypes.Structure):
+    """struct nbody_launch_policy (include/nbody.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("tile", ctypes.c_int32), ("i_per_thread", ctypes.c_int32), ("j_split", ctypes.c_int32), ("blocks", ctypes.c_int32),
+        ("threads", ctypes.c_int32), ("algorithm", ctypes.c_int32), ("super_tile", ctypes.c_int32), ("plan_is_even", ctypes.c_int32),
+        ("phases", ctypes.c_int32), ("exchange_ranks", ctypes.c_int32), ("wave", ctypes.c_int32), ("detector_slots", ctypes.c_int32),
+        ("sym_slots", ctypes.c_int32), ("sym_min_sub", ctypes.c_int32),
+        ("sym_k", ctypes.c_double),
+        ("pool_bytes", ctypes.c_uint64),
+        ("kernel", ctypes.c_char * 64),
+    ]
+
+
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 DRAW_POINT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
 DRAW_BOX_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
@@ -150,6 +164,7 @@ def lib():
     sig("nbody_ic_reference_box", c_int, c_i32, c_f, fp, ctypes.c_uint64, fp, fp)
     sig("nbody_ic_plummer", c_int, c_i32, c_d, c_d, c_d, ctypes.c_uint64, fp, fp)
     sig("nbody_block_pairs_describe", c_i32, c_i32, c_i32)
+    sig("nbody_launch_policy_describe", c_int, ctypes.POINTER(Params), c_i32, ctypes.c_uint64, ctypes.POINTER(LaunchPolicy))
     sig("nbody_sym_plan_describe", c_int, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),
         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_i32), c_i32)
     sig("nbody_sym_plan_describe_tenths", c_int, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),

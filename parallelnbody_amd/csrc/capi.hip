@@ -1,6 +1,7 @@
 // C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches.  Host C++ over the
 // HIP runtime; no torch types, no exceptions across the boundary (the entry points that allocate host memory catch
-// std::bad_alloc), no CPU fallback.
+// std::bad_alloc), no CPU fallback.  Which kernel, geometry and plan a context gets — every size threshold — is decided in
+// launch_policy.{h,cpp} (host only, CPU-tested); nbody_create asks the device its CU count and memory and carries the answer out.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -10,10 +11,11 @@
 
 #include "bh_driver.h"
 #include "ctx.h"
+#include "launch_policy.h"
 
 namespace {
 
-using nbody::EventPair; using nbody::fail; using nbody::g_create_error; using nbody::timed_launch; using nbody::use_device;
+using nbody::detector_table_bytes; using nbody::env_flag; using nbody::env_int; using nbody::EventPair; using nbody::fail; using nbody::g_create_error; using nbody::timed_launch; using nbody::use_device;
 
 // A call on a multi-device context is answered by its Multi; its message becomes the context's.
 int multi_rc(nbody_ctx *c, int rc) {
@@ -24,266 +26,21 @@ int multi_unsupported(nbody_ctx *c, const char *who) {
   return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not available on a multi-device context (nbody_create_multi); use one context per device", who);
 }
 
-// Up to N = 16384 a workgroup owns a few bodies and spreads the j range over its lanes (forces_block_pk_kernel,
-// kernels_block.hip: one launch per step, no partial rows; 2 ... 8 register pairs of bodies per workgroup).  Above it the
-// symmetric pass (plain fp32; Kahan and fp64 go through the tile kernels up to their own threshold).  Whole steps without
-// events, same box (profiles/r03_block_kernel_by_n.txt): N = 14336 0.0538 ms against the symmetric pass's 0.0630, 16384 —
-// four full workgroups per CU — 0.0674 / 0.0735, 17408 0.0922 / 0.0710; round 2's one-pair-per-workgroup kernel
-// (small_pk_kernel, gone): N = 2000 0.0067 ms against 0.0053 now, 4096 0.0143 / 0.0096, 6000 0.0246 / 0.0150.
-constexpr int kSmallSystem = 6656;      // the threshold of rounds 1-2 (tile kernel above it); still Kahan's and the forced geometries'
-int block_max_n() { static const int v = [] { const char *e = getenv("NBODY_BLOCK_MAX_N"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 16385; }(); return v; }
-
-// Register pairs per workgroup for the block kernel.  A CU works through its workgroups two at a time (2 waves per SIMD at
-// ~200 VGPRs) and a workgroup left alone runs about twice as fast, so a CU's time is its number of workgroups times the
-// pairs each one carries: the bodies are cut so that ceil(workgroups / CUs) * pairs is smallest, larger workgroups first on
-// a tie (fewer prologues).  Measured against all of 2 ... 8 at fifteen sizes (profiles/r03_block_kernel_np_by_n.txt): the
-// rule picks the fastest or within 6 % of it.  A function of n_total and the CU count only.
-int block_pairs(int n_total, int cus) {
-  if (const char *e = getenv("NBODY_BLOCK_NP")) { const int v = atoi(e); if (v >= 1 && v <= 8) return v; }   // tuning only
-  if (cus <= 0) cus = 256;
-  int best = 8;
-  long long best_cost = -1;
-  for (int np = 8; np >= 2; --np) {
-    const long long wgs = (n_total + 2 * np - 1) / (2 * np);
-    const long long cost = (wgs + cus - 1) / cus * np;
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = np; }
-  }
-  return best;
+// eps^2 of the context's pair law: its own, or the floor of NBODY_ZERO_FLOOR once ensure_floor has computed it
+double pair_eps2(const nbody_ctx *c) {
+  const double eps2 = c->p.eps * c->p.eps;
+  return (eps2 == 0.0 && c->p.zero_mode == NBODY_ZERO_FLOOR && c->floor_eps2 > 0.0) ? c->floor_eps2 : eps2;
 }
 
-// forces_block_kernel (Kahan, fp64): 4 or 8 bodies per workgroup by the same rule
-int block_bodies(int n_total, int cus) {
-  if (const char *e = getenv("NBODY_BLOCK_NB")) { const int v = atoi(e); if (v == 4 || v == 8) return v; }   // tuning only
-  if (cus <= 0) cus = 256;
-  // on a tie eight, unless all workgroups of four are resident at once anyway (measured, whole steps in both precisions:
-  // N = 2000 6.8 - 7.5 us with four against 7.7 with eight; N = 4096 16.8 - 18.9 against 15.9 - 18.1)
-  const long long r8 = ((n_total + 7) / 8 + cus - 1) / cus, r4 = ((n_total + 3) / 4 + cus - 1) / cus;
-  return (r4 * 4 < r8 * 8 || (r4 * 4 == r8 * 8 && r4 <= 2)) ? 4 : 8;
-}
-
-int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  if (!e || !*e) return dflt;
-  const int v = atoi(e);
-  return v > 0 ? v : dflt;
-}
-
-int floor_pow2(long long v) { int p = 1; while ((long long)p * 2 <= v) p *= 2; return p; }
-
-// Launch geometry.  j_split is a function of n_total only, so that the per-body summation order
-// (and hence every bit of the trajectory) does not depend on how many GPUs share the bodies.
-void choose_geometry(nbody_ctx *c) {
-  const nbody_params &p = c->p;
-  c->tile = p.tile > 0 ? p.tile : 256;
-  if (p.i_per_thread > 0) c->ipt = p.i_per_thread > 4 ? 4 : p.i_per_thread;   // 8 and 16 exist for the symmetric kernel only
-  // whole steps without events (profiles/r02_small_system_thresholds.txt): N = 8192 0.0277 ms with four bodies per lane, 0.0258 with
-  // two; 10240 0.0444 / 0.0427; N = 16384: 0.102 with four, 0.106 with two
-  else c->ipt = (p.precision == NBODY_PREC_F64) ? 1 : (p.n_total >= 12288 ? 4 : (p.n_total >= kSmallSystem ? 2 : 1));
-  int js;
-  if (p.j_split > 0) {
-    js = p.j_split;
-  } else {
-    // aim at >= 2048 workgroups (8 per CU) down to an 8-way body partition; a chunk may be a single tile — small
-    // systems are short of workgroups, not of work per workgroup (N = 8192: 52 us with 8 chunks, 29 us with 32)
-    const long long per_block = 256LL * c->ipt;
-    long long iblocks8 = (p.n_total / 8 + per_block - 1) / per_block;
-    if (iblocks8 < 1) iblocks8 = 1;
-    js = floor_pow2((2048 + iblocks8 - 1) / iblocks8);
-    const int max_js = p.n_total / c->tile;
-    if (js > max_js) js = max_js;
-    if (js < 1) js = 1;
-  }
-  int chunk = (p.n_total + js - 1) / js;
-  chunk = (chunk + c->tile - 1) / c->tile * c->tile;
-  js = (p.n_total + chunk - 1) / chunk;
-  c->j_split = js;
-  c->j_chunk = chunk;
-  // Small and mid-size systems (the reference ships N = 2000): a workgroup owns a few bodies and its lanes split the j range
-  // (forces_block_pk_kernel; forces_block_kernel in the other two precisions) — one lane per body cannot fill the chip
-  // there.  Only when the caller left the geometry to us.  c->wave: register pairs per workgroup (plain fp32), bodies
-  // per workgroup (Kahan, fp64).
-  c->wave = 0;
-  const bool ours = p.algorithm != NBODY_ALGO_SYMMETRIC && p.tile == 0 && p.i_per_thread == 0 && p.j_split == 0;
-  int cus = 256;
-  { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
-  if (ours && p.precision == NBODY_PREC_F32 && p.zero_mode != NBODY_ZERO_SELECT && p.n_total < block_max_n()) {
-    c->wave = block_pairs(p.n_total, cus);
-  } else if (ours && p.precision == NBODY_PREC_F32_KAHAN && p.zero_mode != NBODY_ZERO_SELECT &&
-             p.n_total < env_int("NBODY_BLOCK_MAX_N_KAHAN", kSmallSystem)) {
-    // above kSmallSystem the packed Kahan tile kernel is faster (whole steps: profiles/r03_block_kernel_other_precisions.txt)
-    c->wave = block_bodies(p.n_total, cus);
-  } else if (ours && p.precision == NBODY_PREC_F64 && p.n_total < env_int("NBODY_BLOCK_MAX_N_F64", kSmallSystem)) {
-    c->wave = block_bodies(p.n_total, cus);
-  }
-  if (c->wave != 0) {
-    c->j_split = 1;
-    c->j_chunk = (p.n_total + c->tile - 1) / c->tile * c->tile;
-  }
-}
-
-// Which plain fp32 systems take the even-share plan by default: whole steps without events, one box, both forms of the kernel,
-// every bodies-per-lane choice under both plans (profiles/r05_even_share_vs_guided_by_n.txt; distinct / equal masses, best
-// guided -> best even-share): N = 20480 95.2 / 88.7 us -> 92.3 / 86.4, 24576 128.2 / 119.3 -> 123.7 / 113.4, 32768 206.7 /
-// 190.7 -> 199.6 / 182.3, 40960 302.9 / 281.1 -> 289.8 / 260.6, 65536 722.6 / 658.9 -> 703.3 / 630.7, 81920 1103.8 / 1014.1 ->
-// 1081.2 / 967.3, 98304 1555.6 / 1421.7 -> 1552.3 / 1392.5; N = 18432 and 131072: nothing in it.
-bool sym_even_default(int n_total, bool kahan) {
-  // Kahan contexts (eight bodies per lane at most, two waves per SIMD): profiles/r05_even_share_vs_guided_by_n_kahan.txt — N = 12288
-  // 51.1 / 49.3 us -> 49.8 / 47.5, 16384 77.8 / 75.0 -> 74.4 / 70.2, 24576 134.0 / 125.2 -> 127.6 / 116.1, 32768 212.8 / 196.1 ->
-  // 210.8 / 189.2; from 49152 on the guided strips are ahead (427.8 / 391.8 against 439.0 / 394.6)
-  if (kahan) return n_total >= env_int("NBODY_SYM_EVEN_KAHAN_MIN_N", 12288) && n_total < env_int("NBODY_SYM_EVEN_KAHAN_MAX_N", 40960);
-  // (with the detector's sparse table, profiles/r05_even_share_vs_block_kernel_13k_to_19k.txt: N = 17408 73.0 / 67.7 -> 70.2 / 67.1
-  // with four bodies per lane, 18432 78.4 / 74.6 -> 76.9 / 73.7, 19456 83.8 / 78.3 -> 83.2 / 79.7: everything the symmetric pass
-  // runs below 106496 bodies (and, below, up to 139264).  The same table has even shares ahead of the block kernel from N = 15360 — 61.1 / 57.6 -> 57.4 / 54.8,
-  // 16384 67.8 / 63.9 -> 64.4 / 61.2 —; the block kernel keeps those sizes for its one-launch step and what nbody_tick gets from it.)
-  // Upper end, with TWO items per slot from 90112 bodies on — passes of 1.5 ms and more: slots of unequal speed drift apart —
-  // (profiles/r05_even_share_rounds_at_larger_n.txt; guided -> one round -> two, distinct | equal masses): N = 98304 1596 -> 1590 ->
-  // 1566 us | 1450 -> 1420 -> 1403, 114688 2073 -> 2063 -> 2037 | 1894 -> 1855 -> 1831, 131072 2650 -> 2664 -> 2645 | 2428 -> 2392 ->
-  // 2381; from 147456 on nothing in it either way (3453 -> 3535 -> 3484 | 3160 -> 3185 -> 3118): even shares below 139264 bodies.
-  return n_total >= env_int("NBODY_SYM_EVEN_MIN_N", 16385) && n_total < env_int("NBODY_SYM_EVEN_MAX_N", 139264);
-}
-
-// Symmetric algorithm: applicability, bodies per lane, and the work plan (sym_plan.h).  Everything here is a function
-// of the parameters and of the device's CU count and total memory — never of what happens to be free — so that equal
-// GPUs arrive at equal plans (the ranks of a sharded job must) and results are reproducible from box to box.
-void choose_algorithm(nbody_ctx *c) {
-  const nbody_params &p = c->p;
-  c->sym = false;
-  if (p.algorithm == NBODY_ALGO_TILED) return;
-  if (p.zero_mode == NBODY_ZERO_SELECT) return;                         // compare+select lives in the one-sided kernel only
-  // whole steps, one box, final kernels (profiles/r02_threshold_symmetric_vs_one_sided.txt): N = 10240 one-sided 0.0597 ms vs
-  // symmetric 0.0597, N = 12288 0.0763 vs 0.0700, 14336 0.0934 vs 0.0841, 16384 (the one-sided geometry's best case) 0.0978
-  // vs 0.0948, 18432 0.1287 vs 0.1024, 20480 0.147 vs 0.116; Kahan and fp64 likewise from 12288 (0.0735 vs 0.0639, 0.129 vs 0.119)
-  // Round 3 (the fused update folds its two lists side by side; whole steps without events, same box: N = 8192 0.0266 ms
-  // one-sided vs 0.0366 symmetric, 9216 0.0351 vs 0.0325, 10240 0.0423 vs 0.0393, 11264 0.0438 vs 0.0413; Kahan 9216 0.0326 vs
-  // 0.0289, fp64 0.0774 vs 0.0658; distinct masses 0.0362 vs 0.0340): the symmetric pass from N = 9216
-  if (p.algorithm == NBODY_ALGO_AUTO && c->wave != 0) return;            // the block kernels' one-launch step (choose_geometry)
-  if (p.algorithm == NBODY_ALGO_AUTO && p.n_total < env_int("NBODY_SYM_MIN_N", 9216)) return;
-  const bool f64 = p.precision == NBODY_PREC_F64, kahan = p.precision == NBODY_PREC_F32_KAHAN;
-  if (f64 && !(p.eps > 0.0 || p.zero_mode == NBODY_ZERO_EXACT)) return;
-  // bodies per lane.  fp32: 2 * register pairs; more of them amortise the travelling sums' dpp moves over more
-  // arithmetic (tools/microbench6.hip) but make the i-set — the quantum of work — larger.  fp64: 2, or 4 at 2 waves/SIMD.
-  // The even-share plan (sym_plan.h): plain fp32, one context owning all bodies, two register pairs per lane and more —
-  // exactly one workgroup per slot, all of equal cost.  NBODY_SYM_EVEN = 0 / 1 forces the choice (A/B measurements, tests).
-  int even_env = -1;
-  if (const char *e = getenv("NBODY_SYM_EVEN")) { if (e[0] == '0' || e[0] == '1') even_env = e[0] - '0'; }
-  // (not where a test forces pool phases on a small system: the phased pass is the guided plan's)
-  const bool even_wanted = !f64 && p.i_count == p.n_total && env_int("NBODY_SYM_POOL_BUDGET_MB", 0) == 0 &&
-                           (even_env == 1 || (even_env < 0 && sym_even_default(p.n_total, kahan)));
-  int ipt = p.i_per_thread;
-  if (f64) {
-    if (ipt == 0) ipt = p.n_total >= 65536 ? 4 : 2;
-    if (ipt != 2 && ipt != 4) return;
-  } else {
-    if (ipt == 0 && even_wanted) {
-      // even shares have no quantum of work to keep small: sixteen bodies per lane (the fewest instructions per interaction)
-      // from N = 24576, eight from 20480, four below (same table: N = 20480 93.0 / 86.4 us with eight, 94.3 / 86.5 with sixteen; 22528 107.5 /
-      // 99.2 against 115.4 / 105.4; 24576 125.1 / 115.4 against 123.7 / 113.4; 32768 205.5 / 190.3 against 199.6 / 182.3)
-      // (Kahan: four below 22528 — N = 20480 95.0 / 88.7 us with four, 96.6 / 91.0 with eight —, eight above)
-      ipt = env_int("NBODY_SYM_IPT", kahan ? (p.n_total >= 22528 ? 8 : 4) : (p.n_total >= 24576 ? 16 : (p.n_total >= 20480 ? 8 : 4)));
-    } else if (ipt == 0) {
-      // measured on one box, sustained load (profiles/r02_sweep_symmetric_by_n.txt, r02_tune_mid_sizes.txt): sixteen bodies
-      // per lane win wherever the symmetric pass runs (N = 32768: 0.206 vs 0.211 ms with eight, 65536: 0.691 vs 0.718,
-      // 131072: 2.62 vs 2.70, 2^20: 162 vs 170.5 ms); the Kahan form has no sixteen (its running compensated sums double the
-      // accumulators) and runs eight
-      if (!kahan && p.n_total >= 40960) ipt = 16;      // whole step, N = 32768: 0.2353 ms with eight, 0.2408 with sixteen; 40960: 0.3355 / 0.3336
-      else if (p.n_total >= 24576) ipt = 8;
-      else if (p.n_total >= 17408) ipt = 4;
-      else ipt = 2;                                    // N = 12288: 0.0700 ms with two, 0.0713 with four; 16384: 0.0948 / 0.0964; 18432: 0.1037 / 0.1024
-      ipt = env_int("NBODY_SYM_IPT", ipt);
-      if (kahan && ipt == 16) ipt = 8;
-      // sharded slices must be whole i-sets
-      while (ipt > 2 && p.i_count != p.n_total && p.i_count % (256 * ipt) != 0) ipt /= 2;
-    }
-    if (ipt != 2 && ipt != 4 && ipt != 8 && ipt != 16) return;
-    if (ipt == 16 && kahan) return;
-  }
-  const int bi = 256 * ipt;
-  // workgroups the chip holds at a time: one wave of each per SIMD -> (waves per SIMD) per CU
-  int cus = 256;
-  { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
-  const int np = ipt / 2;
-  const int wps = f64 ? (ipt == 4 ? 2 : 4) : (np == 8 ? 2 : (np == 4 ? (kahan ? 2 : 3) : (kahan && np == 2 ? 3 : 4)));
-  c->sym_slots = cus * wps;
-  // A strip = 1/(K * slots) of the work still to hand out.  Large K = many short strips = best balance of the force pass but
-  // one i-side segment (bodies-per-i-set x 16 B, written and read back) per strip; small K = a first round of long strips.
-  // Long passes want K = 6 (N = 2^20, force pass: K = 3 170.1 ms — slots of unequal speed drift apart over 100 ms —, 6
-  // 164.1, 24 163.3 at three times the segments; profiles/r02_tune_guided_k_n2p20.txt).  Short passes do not care about K
-  // but their update pays for every segment (whole step, profiles/r02_tune_whole_step_mid_sizes.txt: N = 65536 K = 6
-  // 0.781 ms, K <= 3 0.752; N = 131072 2.780 vs 2.653; N = 32768 0.2675 vs 0.2518).
-  // What decides is how long the pass runs (fp64 at N = 262144 takes 25 ms and wants K = 6: 25.5 vs 26.9 ms with 3), so K
-  // follows the expected duration of this context's share: >= 15 ms 6, >= 5 ms 3, >= 0.5 ms 1.5, below 1.
-  {
-    const double rate = f64 ? 2.7e12 : (kahan ? 6.0e12 : 6.6e12);                      // interactions per second, measured
-    const double est_ms = (double)p.n_total * (double)p.i_count / rate * 1e3;
-    c->sym_k = est_ms >= 15.0 ? 6.0 : (est_ms >= 5.0 ? 3.0 : (est_ms >= 0.5 ? 1.5 : 1.0));
-  }
-  if (const char *e = getenv("NBODY_SYM_K")) { const int v = atoi(e); if (v >= 1) c->sym_k = v; }                     // tuning only
-  if (const char *e = getenv("NBODY_SYM_K_X10")) { const int v = atoi(e); if (v >= 5) c->sym_k = v / 10.0; }         // tuning only
-  // shortest strip, in 64-body subtiles: whole 256-body tiles from N = 131072, half tiles below (same table)
-  // (round 3, whole steps without events, four bodies per lane: N = 20480 0.0921 ms with two subtiles, 0.0888 with one; two
-  // bodies per lane — N = 16384 — do not care: 0.0737 / 0.0738)
-  c->sym_min_sub = env_int("NBODY_SYM_MIN_SUB", p.n_total >= 131072 ? 4 : (!f64 && ipt == 4 ? 1 : 2));
-  nbody::SymPlan *plan = new (std::nothrow) nbody::SymPlan();
-  if (!plan) return;
-  std::string why;
-  bool planned = false;
-  const bool even = even_wanted && np >= 2;
-  try {
-    if (even) {
-      const int rounds = env_int("NBODY_SYM_EVEN_ROUNDS", (!kahan && p.n_total >= 90112) ? 2 : 1);       // items per slot (sym_even_default)
-      planned = nbody::build_sym_plan_even(p.n_total, bi, std::max(1, (int)((long long)c->sym_slots * rounds * env_int("NBODY_SYM_EVEN_ITEMS_PCT", 100) / 100)), plan, &why,
-                                           env_int("NBODY_SYM_EVEN_COST_SYM", 82), env_int("NBODY_SYM_EVEN_COST_ONE", 74),
-                                           env_int("NBODY_SYM_EVEN_COST_MOVE", 26), env_int("NBODY_SYM_EVEN_OWN_PCT", nbody::kSymEvenOwnPct));
-      if (planned) { c->sym_k = 0.0; c->sym_min_sub = 0; }
-    } else
-    planned = nbody::build_sym_plan(p.n_total, p.i_begin, p.i_count, bi, c->sym_slots, c->sym_k, c->sym_min_sub, f64 ? 2 : 1, plan, &why,
-                                    0, env_int("NBODY_SYM_MAX_SUB", 0));
-  } catch (const std::bad_alloc &) {
-    why = "out of host memory";
-  }
-  // The partial-sum pool must fit comfortably: at most a third of the card's TOTAL memory (and 2^32 elements).  Beyond that
-  // (N = 2^23 on one 288 GB card: the j-side segments alone are 137 GB) the fp32 pass runs in PHASES that share one j-side
-  // area, sized so that the whole pool stays within 32 GB (sym_plan.h); fp64 has no phased form and leaves to the
-  // one-sided kernel.  NBODY_SYM_POOL_BUDGET_MB forces phases at any size (tests).
-  size_t free_b = 0, total_b = 0;
-  const int forced_mb = f64 ? 0 : env_int("NBODY_SYM_POOL_BUDGET_MB", 0);
-  const bool too_big = !planned ? why.find("2^32") != std::string::npos
-                                : (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0 &&
-                                   (double)plan->pool_elems * (f64 ? 32.0 : 16.0) > (double)total_b / 3.0);
-  if (!f64 && !even && (forced_mb > 0 || too_big)) {
-    const double cap = 32.0 * 1073741824.0 / 16.0;                                    // elements
-    double budget = forced_mb > 0 ? (double)forced_mb * 1048576.0 / 16.0 : 20.0 * 1073741824.0 / 16.0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      try {
-        planned = nbody::build_sym_plan(p.n_total, p.i_begin, p.i_count, bi, c->sym_slots, c->sym_k, c->sym_min_sub, 1, plan, &why,
-                                        (uint64_t)budget);
-      } catch (const std::bad_alloc &) { why = "out of host memory"; planned = false; }
-      if (!planned || forced_mb > 0 || (double)plan->pool_elems <= cap) break;
-      budget -= (double)plan->pool_elems - cap;                                       // the i-side segments took more than 12 GB
-      if (budget < 2.0 * 1073741824.0 / 16.0) { planned = false; why = "the i-side segments leave no room for a shared j-side area"; break; }
-    }
-    if (planned && forced_mb == 0 && (double)plan->pool_elems > cap) { planned = false; why = "the partial-sum pool would exceed 32 GB even in phases"; }
-  } else if (planned && too_big) {
-    planned = false; why = "the partial-sum pool would exceed a third of the device memory";
-  }
-  if (!planned) {
-    g_create_error = "symmetric plan: " + why;
-    delete plan;
-    return;
-  }
-  c->plan = plan;
-  c->sym_bi = bi; c->sym_np = f64 ? ipt / 2 : np; c->sym_pad = plan->n_pad; c->sym_items_n = (int)plan->items.size();
-  c->sym_nsrc = plan->n_src; c->sym_pool_elems = (size_t)plan->pool_elems; c->sym_n_local = plan->n_local;
-  c->sym_phase_item0 = plan->phase_item0; c->sym_n_gran = plan->n_gran;
-  c->sym_even = plan->even;
-  c->sym = true;
-  c->wave = 0;            // the small-system one-launch step belongs to the one-sided path
+// the coincident-body detector's table, cleared on the context's stream
+hipError_t clear_dup_table(const nbody_ctx *c, void *table) {
+  return hipMemsetAsync(table, 0, detector_table_bytes(c->sym_dup_slots), c->stream);
 }
 
 // Fused stepping (update_sym_fused_kernel) is for fp32 symmetric contexts that own all bodies AND their position buffer:
 // then nothing but this library's kernels moves a body, and the update can prepare the next pass.
 bool sym_fused(const nbody_ctx *c) {
-  static const bool off = [] { const char *e = getenv("NBODY_SYM_NO_FUSE"); return e && e[0] == '1'; }();   // A/B measurements only
+  static const bool off = env_flag("NBODY_SYM_NO_FUSE") == 1;   // A/B measurements only; latched at first use
   return !off && c->sym && c->p.precision != NBODY_PREC_F64 && c->sym_nsrc == 1 && c->own_posm && !c->posm_escaped &&
          c->sym_phase_item0.size() == 2 &&
          (c->sym_dup_table == nullptr || c->sym_dup_table2 != nullptr);
@@ -299,8 +56,7 @@ nbody::SymLaunch make_sym_launch(const nbody_ctx *c) {
   L.even = c->sym_even ? 1 : 0; L.wrap = c->sym_n_gran * 64;
   L.precision = c->p.precision == NBODY_PREC_F64 ? NBODY_PREC_F64 : NBODY_PREC_F32;
   L.kahan = c->p.precision == NBODY_PREC_F32_KAHAN ? 1 : 0;
-  L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-  if (L.eps2 == 0.0 && c->p.zero_mode == NBODY_ZERO_FLOOR && c->floor_eps2 > 0.0) L.eps2 = c->floor_eps2;
+  L.G = c->p.G; L.eps2 = pair_eps2(c);
   L.dup_table = c->sym_dup_table; L.dup_slots = c->sym_dup_slots;
   L.general = c->sym_general;
   L.n_local = c->sym_n_local; L.own_begin = c->p.i_begin; L.own_count = c->p.i_count;
@@ -326,12 +82,11 @@ nbody::ForceLaunch make_launch(const nbody_ctx *c) {
   L.posm = c->posm; L.accp = c->accp;
   L.n_total = c->p.n_total; L.i_begin = c->p.i_begin; L.i_count = c->p.i_count;
   L.tile = c->tile; L.ipt = c->ipt; L.j_split = c->j_split; L.j_chunk = c->j_chunk;
-  L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.precision = c->p.precision;
+  L.G = c->p.G; L.eps2 = pair_eps2(c); L.precision = c->p.precision;
   L.zero_mode = (c->p.zero_mode == NBODY_ZERO_SELECT) ? 2 : 1;
   L.wave = c->wave;
   L.guarded = env_int("NBODY_SYM_GUARDED", 0) == 1 ? 1 : 0;        // A/B measurements and tests: no bare pair law anywhere
   L.dup_table = c->sym_dup_table; L.dup_slots = c->sym_dup_slots;
-  if (L.eps2 == 0.0 && c->p.zero_mode == NBODY_ZERO_FLOOR && c->floor_eps2 > 0.0) L.eps2 = c->floor_eps2;
   // equal-mass form of the packed one-sided kernel: the host's scan of the uploaded state stands while nothing else writes
   // the position buffer ("not equal" always stands: the device word is sticky); otherwise the device looks before the launch
   L.general = c->sym_general;
@@ -377,8 +132,7 @@ int queue_probe(nbody_ctx *c, void *pts, void *vel, void *acc, int m, float dt) 
   nbody::ProbeLaunch L;
   L.posm = c->posm; L.probe = pts; L.part = c->probe_part; L.acc = acc; L.pos_out = pts; L.vel = vel;
   L.n_total = c->p.n_total; L.m = m;
-  L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-  if (L.eps2 == 0.0 && c->p.zero_mode == NBODY_ZERO_FLOOR && c->floor_eps2 > 0.0) L.eps2 = c->floor_eps2;
+  L.G = c->p.G; L.eps2 = pair_eps2(c);
   L.dt = dt;
   L.clk = c->clk;
   HIP_TRY(c, nbody::launch_probe(L, c->stream));
@@ -401,7 +155,7 @@ int queue_forces(nbody_ctx *c, int phase) {
     // a fused context about to run the preparation kernel again (new state): its current table may hold the entries
     // the last update left for positions that are gone
     if (L.fused && !L.skip_prep && L.dup_table && L.eps2 == 0.0)
-      HIP_TRY(c, hipMemsetAsync(L.dup_table, 0, (size_t)L.dup_slots * 8 + 64, c->stream));
+      HIP_TRY(c, clear_dup_table(c, L.dup_table));
     if (c->p.precision == NBODY_PREC_F64) {
       HIP_TRY(c, nbody::launch_forces_sym(L, c->stream));          // the fp64 launcher runs its whole pass
     } else {
@@ -426,7 +180,7 @@ int queue_forces(nbody_ctx *c, int phase) {
         L.j_ptr = (const unsigned int *)c->sym_jptr + (size_t)q * ((size_t)c->sym_n_gran + 1);
         HIP_TRY(c, nbody::launch_forces_sym(L, c->stream));
         if (a >= b && folded_in_first_go && L.dup_table && L.eps2 == 0.0)
-          HIP_TRY(c, hipMemsetAsync(L.dup_table, 0, (size_t)L.dup_slots * 8 + 64, c->stream));
+          HIP_TRY(c, clear_dup_table(c, L.dup_table));
         first = false;
       }
     }
@@ -566,15 +320,61 @@ bool in_pinned(const nbody_ctx *c, const void *dst, size_t bytes) {
   return false;
 }
 
-// The staged, packed FParticle records -> the caller's array (records `stride` bytes apart).
-void unstage_particles(const nbody_ctx *c, void *aos, size_t stride, size_t count) {
-  if (stride == sizeof(nbody_particle)) {
-    memcpy(aos, c->h_stage, count * sizeof(nbody_particle));
+// `count` staged records of record_bytes each (src_stride apart: packed unless given) -> the caller's array, records `stride` bytes apart
+void scatter_records(void *dst, size_t stride, const void *src, size_t record_bytes, size_t count, size_t src_stride = 0) {
+  if (src_stride == 0) src_stride = record_bytes;
+  if (stride == record_bytes && src_stride == record_bytes) {
+    memcpy(dst, src, count * record_bytes);
     return;
   }
-  char *base = (char *)aos;
-  const char *src = (const char *)c->h_stage;
-  for (size_t i = 0; i < count; ++i) memcpy(base + i * stride, src + i * sizeof(nbody_particle), sizeof(nbody_particle));
+  for (size_t i = 0; i < count; ++i) memcpy((char *)dst + i * stride, (const char *)src + i * src_stride, record_bytes);
+}
+
+// Does the caller's FParticle array take the records by DMA — packed, and inside memory it pinned for this context?
+bool mirror_is_direct(const nbody_ctx *c, const void *aos, size_t stride) {
+  return stride == sizeof(nbody_particle) && in_pinned(c, aos, (size_t)c->p.i_count * sizeof(nbody_particle));
+}
+
+// The owned bodies' FParticle records, queued: packed on the device, then copied to the caller's pinned mirror (*direct) or to the
+// staging buffer (scatter_records delivers from there once the stream has been waited for).
+int queue_particle_mirror(nbody_ctx *c, void *aos, size_t stride, bool *direct) {
+  const size_t bytes = (size_t)c->p.i_count * sizeof(nbody_particle);
+  if (int rc = ensure_stage(c, bytes)) return rc;
+  HIP_TRY(c, nbody::launch_pack_particles(c->p.precision, c->posm, c->vel, c->acc, (float *)c->d_stage, c->p.i_begin,
+                                          c->p.i_count, c->stream));
+  *direct = mirror_is_direct(c, aos, stride);
+  HIP_TRY(c, hipMemcpyAsync(*direct ? aos : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
+  return NBODY_OK;
+}
+
+// For the launches that write the frame's records themselves, straight into page-locked host memory — the caller's own mirror if it
+// pinned it (nbody_pin_host_buffer; align16: and only if it is 16-byte aligned), the context's staging buffer otherwise: no copy to
+// wait for (profiles/r03_tick_parts_n2000.txt: the 80 KB copy of the shipped scene's mirror cost 12.7 us of a 32.7 us frame).
+// *dev: that memory's device pointer.
+int mirror_device_ptr(nbody_ctx *c, void *aos, size_t stride, bool align16, bool *direct, void **dev) {
+  if (int rc = ensure_stage(c, (size_t)c->p.i_count * sizeof(nbody_particle))) return rc;
+  *direct = mirror_is_direct(c, aos, stride) && (!align16 || ((uintptr_t)aos & 15u) == 0);
+  HIP_TRY(c, hipHostGetDevicePointer(dev, *direct ? aos : c->h_stage, 0));
+  return NBODY_OK;
+}
+
+// ComputeCubeSize of the owned bodies' current positions, queued: its bit pattern arrives in h_scratch
+int queue_bounds(nbody_ctx *c) {
+  HIP_TRY(c, hipMemsetAsync(c->scratch, 0, 4, c->stream));
+  HIP_TRY(c, nbody::launch_bounds(c->p.precision, c->posm, c->p.i_begin, c->p.i_count, (unsigned int *)c->scratch, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 4, hipMemcpyDeviceToHost, c->stream));
+  return NBODY_OK;
+}
+
+// the two sums an energy reduction left in the scratch, waited for
+int read_energy(nbody_ctx *c, double *ke, double *pe) {
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  double v[2];
+  memcpy(v, c->h_scratch, 16);
+  if (ke) *ke = v[0];
+  if (pe) *pe = v[1];
+  return NBODY_OK;
 }
 
 // The position buffer becomes visible to (or is replaced by) the caller: bodies may move behind the library's back from
@@ -583,7 +383,7 @@ void unstage_particles(const nbody_ctx *c, void *aos, size_t stride, size_t coun
 int posm_escapes(nbody_ctx *c) {
   if (c->posm_escaped) return NBODY_OK;
   if (c->sym_dup_table2)
-    HIP_TRY(c, hipMemsetAsync(c->sym_dup_table, 0, (size_t)c->sym_dup_slots * 8 + 64, c->stream));
+    HIP_TRY(c, clear_dup_table(c, c->sym_dup_table));
   c->posm_escaped = true;
   c->sym_posg_valid = false;
   if (c->bh) nbody::bh_positions_external(c->bh);
@@ -594,6 +394,40 @@ int check_ready(nbody_ctx *c) {
   if (!c) return NBODY_ERR_INVALID;
   if (!c->have_state) return fail(c, NBODY_ERR_STATE, "no particles set (call nbody_set_particles / nbody_set_state_soa first)");
   return use_device(c);
+}
+
+// nbody_set_state_soa / nbody_set_state_soa_f64 (`who`): the whole state as T x 4
+template <typename T>
+int set_state_soa(nbody_ctx *c, const T *posm4, const T *vel4, int32_t n, const char *who) try {
+  if (!c || !posm4 || !vel4) return c ? fail(c, NBODY_ERR_INVALID, "%s: null buffer", who) : NBODY_ERR_INVALID;
+  if (n != c->p.n_total) return fail(c, NBODY_ERR_INVALID, "%s: n = %d but the context holds %d bodies", who, n, c->p.n_total);
+  if (c->multi) {
+    int rc;
+    if constexpr (sizeof(T) == 8) rc = nbody::multi_set_state_soa_f64(c->multi, posm4, vel4, n);
+    else rc = nbody::multi_set_state_soa(c->multi, posm4, vel4, n);
+    if (!multi_rc(c, rc)) { c->have_state = true; c->steps_done = 0; }
+    return rc;
+  }
+  return upload_soa<T>(c, posm4, vel4);
+} catch (const std::bad_alloc &) {
+  return fail(c, NBODY_ERR_NOMEM, "%s: out of host memory", who);
+}
+
+// nbody_get_state_soa / nbody_get_state_soa_f64 (`who`): the owned bodies' state as T x 4, each array optional
+template <typename T>
+int get_state_soa(nbody_ctx *c, T *posm4, T *vel4, T *acc4, const char *who) try {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (c->multi) {
+    if constexpr (sizeof(T) == 8) return multi_rc(c, nbody::multi_get_state_soa_f64(c->multi, posm4, vel4, acc4));
+    else return multi_rc(c, nbody::multi_get_state_soa(c->multi, posm4, vel4, acc4));
+  }
+  if (posm4 && (rc = download4<T>(c, c->posm, (size_t)c->p.i_begin, (size_t)c->p.i_count, posm4))) return rc;
+  if (vel4 && (rc = download4<T>(c, c->vel, 0, (size_t)c->p.i_count, vel4))) return rc;
+  if (acc4 && (rc = download4<T>(c, c->acc, 0, (size_t)c->p.i_count, acc4))) return rc;
+  return NBODY_OK;
+} catch (const std::bad_alloc &) {
+  return fail(c, NBODY_ERR_NOMEM, "%s: out of host memory", who);
 }
 
 }  // namespace
@@ -623,32 +457,10 @@ const char *nbody_last_error(const nbody_ctx *ctx) { return ctx ? ctx->err.c_str
 int nbody_create(const nbody_params *pin, nbody_ctx **out) try {
   if (!pin || !out) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: null argument");
   *out = nullptr;
-  if (pin->struct_size != sizeof(nbody_params))
-    return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: struct_size %u != %zu", pin->struct_size, sizeof(nbody_params));
+  std::string why;
+  if (int rc = nbody::validate_params(*pin, &why)) return fail(nullptr, rc, "%s", why.c_str());
   nbody_params p = *pin;
-  if (p.n_total <= 0) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: n_total must be > 0");
-  if (p.i_begin < 0 || p.i_begin >= p.n_total) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: i_begin out of range");
-  if (p.i_count == 0) p.i_count = p.n_total - p.i_begin;
-  if (p.i_count < 0 || p.i_begin + p.i_count > p.n_total)
-    return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: owned range [%d,%d) exceeds n_total %d", p.i_begin,
-                p.i_begin + p.i_count, p.n_total);
-  if (p.precision != NBODY_PREC_F32 && p.precision != NBODY_PREC_F32_KAHAN && p.precision != NBODY_PREC_F64)
-    return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: unknown precision %d", p.precision);
-  if (!(p.eps >= 0.0) || !std::isfinite(p.G)) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: bad G/eps");
-  if (!(p.theta >= 0.0f)) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: theta must be >= 0");
-  if (p.tile != 0 && p.tile != 64 && p.tile != 128 && p.tile != 256 && p.tile != 512)
-    return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: tile must be 64, 128, 256 or 512");
-  if (p.i_per_thread != 0 && p.i_per_thread != 1 && p.i_per_thread != 2 && p.i_per_thread != 4 && p.i_per_thread != 8 &&
-      p.i_per_thread != 16)
-    return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: i_per_thread must be 1, 2, 4, 8 or 16");
-  if (p.i_per_thread == 16 && (p.algorithm == NBODY_ALGO_TILED || p.precision != NBODY_PREC_F32))
-    return fail(nullptr, NBODY_ERR_UNSUPPORTED, "nbody_create: i_per_thread 16 exists for the plain fp32 symmetric kernel only");
-  if (p.i_per_thread == 8 && (p.algorithm == NBODY_ALGO_TILED || p.precision == NBODY_PREC_F64))
-    return fail(nullptr, NBODY_ERR_UNSUPPORTED, "nbody_create: i_per_thread 8 exists for the fp32 symmetric kernels only");
-  if (p.j_split < 0) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: j_split must be >= 0");
-  if (p.zero_mode < 0 || p.zero_mode > NBODY_ZERO_FLOOR) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: unknown zero_mode %d", p.zero_mode);
-  if (p.algorithm < 0 || p.algorithm > NBODY_ALGO_SYMMETRIC) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: unknown algorithm %d", p.algorithm);
-  if (p.bh_div_mode != 0 && p.bh_div_mode != 1) return fail(nullptr, NBODY_ERR_INVALID, "nbody_create: bh_div_mode must be 0 or 1");
+  p.i_count = nbody::owned_count(p);
 
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -660,32 +472,44 @@ int nbody_create(const nbody_params *pin, nbody_ctx **out) try {
   if ((e = hipSetDevice(p.device)) != hipSuccess)      // before anything that asks the device questions (free memory)
     return fail(nullptr, NBODY_ERR_HIP, "nbody_create: hipSetDevice(%d): %s", p.device, hipGetErrorString(e));
 
+  // the two facts about the device the policy may depend on (launch_policy.h), asked once
+  nbody::DeviceFacts dev{0, 0};
+  { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p.device) == hipSuccess) dev.cus = prop.multiProcessorCount; }
+  { size_t free_b = 0, total_b = 0; if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) dev.total_bytes = total_b; }
+  nbody::LaunchPolicy pol;
+  if (int rc = nbody::choose_policy(p, dev, &pol, &why)) return fail(nullptr, rc, "%s", why.c_str());
+
   nbody_ctx *c = new (std::nothrow) nbody_ctx();
   if (!c) return fail(nullptr, NBODY_ERR_NOMEM, "nbody_create: out of host memory");
   c->p = p;
   c->theta = p.theta;
   c->elem = (p.precision == NBODY_PREC_F64) ? 32 : 16;
-  choose_geometry(c);
-  choose_algorithm(c);
-  if ((p.i_per_thread == 8 || p.i_per_thread == 16) && !(c->sym && c->sym_bi == 256 * p.i_per_thread)) {
-    delete c;
-    return fail(nullptr, NBODY_ERR_UNSUPPORTED,
-                "nbody_create: i_per_thread %d needs the fp32 symmetric kernel (N >= 9216 or NBODY_ALGO_SYMMETRIC; "
-                "sharded slices in multiples of %d bodies)", p.i_per_thread, 256 * p.i_per_thread);
-  }
-  if (p.algorithm == NBODY_ALGO_SYMMETRIC && !c->sym) {
-    const std::string why = g_create_error;
-    delete c;
-    return fail(nullptr, NBODY_ERR_UNSUPPORTED,
-                "nbody_create: NBODY_ALGO_SYMMETRIC needs fp32 (i_per_thread 2, 4, 8 or 16, zero_mode != SELECT) or "
-                "fp64 (i_per_thread 2 or 4) and, when sharded, equal slices that are a multiple of 256*i_per_thread bodies%s%s",
-                why.empty() ? "" : " — ", why.c_str());
-  }
+  c->tile = pol.tile; c->ipt = pol.ipt; c->j_split = pol.j_split; c->j_chunk = pol.j_chunk; c->wave = pol.wave;
+  c->sym = pol.sym; c->sym_even = pol.sym_even; c->sym_slots = pol.sym_slots; c->sym_k = pol.sym_k; c->sym_min_sub = pol.sym_min_sub;
+  c->sym_bi = pol.sym_bi; c->sym_np = pol.sym_np; c->sym_pad = pol.sym_pad; c->sym_items_n = pol.sym_items_n; c->sym_nsrc = pol.sym_nsrc;
+  c->sym_pool_elems = (size_t)pol.sym_pool_elems; c->sym_n_local = pol.sym_n_local; c->sym_n_gran = pol.sym_n_gran;
+  c->sym_phase_item0 = pol.plan.phase_item0;
+  c->sym_dup_slots = pol.dup_slots;
 
-  auto bail = [&](hipError_t he, const char *what) {
-    fail(nullptr, NBODY_ERR_HIP, "nbody_create: %s: %s", what, hipGetErrorString(he));
+  auto bail = [&](hipError_t he, const char *what, const char *what2 = "") {
+    fail(nullptr, NBODY_ERR_HIP, "nbody_create: %s%s: %s", what, what2, hipGetErrorString(he));
     nbody_destroy(c);
     return NBODY_ERR_HIP;
+  };
+  // allocate and fill from the host: a list of the plan
+  auto up = [&](void **dst, const void *src, size_t bytes, const char *what) -> hipError_t {
+    hipError_t he = hipMalloc(dst, bytes ? bytes : 4);
+    if (he != hipSuccess) { fail(nullptr, NBODY_ERR_HIP, "nbody_create: hipMalloc %s: %s", what, hipGetErrorString(he)); return he; }
+    if (bytes) he = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    return he;
+  };
+  // allocate and zero (zalloc_op: which of the two calls failed).  The fill runs on the null stream: the wait at the end of this
+  // function covers every one of them.
+  const char *zalloc_op = "";
+  auto zalloc = [&](void **dst, size_t bytes) -> hipError_t {
+    zalloc_op = "hipMalloc ";
+    const hipError_t he = hipMalloc(dst, bytes);
+    return he != hipSuccess ? he : (zalloc_op = "hipMemset ", hipMemset(*dst, 0, bytes));
   };
   if ((e = hipSetDevice(p.device)) != hipSuccess) return bail(e, "hipSetDevice");
   if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
@@ -696,92 +520,43 @@ int nbody_create(const nbody_params *pin, nbody_ctx **out) try {
   c->own_vel = true;
   if ((e = hipMalloc(&c->acc, (size_t)p.i_count * c->elem)) != hipSuccess) return bail(e, "hipMalloc acc");
   c->own_acc = true;
+  const size_t table_bytes = detector_table_bytes(pol.dup_slots);
   if (c->sym) {
-    const nbody::SymPlan &P = *c->plan;
-    auto up = [&](void **dst, const void *src, size_t bytes, const char *what) -> hipError_t {
-      hipError_t he = hipMalloc(dst, bytes ? bytes : 4);
-      if (he != hipSuccess) { fail(nullptr, NBODY_ERR_HIP, "nbody_create: hipMalloc %s: %s", what, hipGetErrorString(he)); return he; }
-      if (bytes) he = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-      return he;
-    };
+    const nbody::SymPlan &P = pol.plan;
     if ((e = hipMalloc(&c->sym_pool, c->sym_pool_elems * c->elem)) != hipSuccess) return bail(e, "hipMalloc partial-sum pool");
     if ((e = up(&c->sym_items, P.items.data(), P.items.size() * sizeof(nbody::SymItem), "work items")) != hipSuccess) return bail(e, "work items");
     if ((e = up(&c->sym_iptr, P.i_ptr.data(), P.i_ptr.size() * 4, "i-side list")) != hipSuccess) return bail(e, "i-side list");
     if ((e = up(&c->sym_ioff, P.i_off.data(), P.i_off.size() * 4, "i-side list")) != hipSuccess) return bail(e, "i-side list");
     if ((e = up(&c->sym_jptr, P.j_ptr.data(), P.j_ptr.size() * 4, "j-side list")) != hipSuccess) return bail(e, "j-side list");
     if ((e = up(&c->sym_joff, P.j_off.data(), P.j_off.size() * 4, "j-side list")) != hipSuccess) return bail(e, "j-side list");
-    delete c->plan; c->plan = nullptr;
     if (p.precision != NBODY_PREC_F64 &&
         (e = hipMalloc(&c->sym_posg, (size_t)c->sym_pad * 16)) != hipSuccess) return bail(e, "hipMalloc scaled positions");
-    // NBODY_SYM_GUARDED=1 (A/B measurements only): always run the guarded kernel, no coincident-body detector
-    const char *guarded = getenv("NBODY_SYM_GUARDED");
-    if (p.eps == 0.0 && p.zero_mode == NBODY_ZERO_EXACT && !(guarded && guarded[0] == '1')) {
-      // How sparse: a body's entry is a chain of dependent device-scope compare-and-swaps (linear probing), each a round trip
-      // to memory, and the update kernel ends with the LONGEST chain of the system.  At a power of two >= 2 N slots (load up to
-      // 0.5; rounds 1-4) that chain was most of the fused update of a mid-size system: update kernel, slots >= 2 N / 4 N / 16 N /
-      // 64 N (profiles/r05_ab_detector_table_sparsity.txt, r05_ab_update_kernel_parts.txt): N = 20480 12.6 / 10.6 / 9.8 / 11.3 us,
-      // 32768 20.3 / 12.8 / 11.0 / 12.4, 65536 23.6 / 15.8 / 14.0 / 16.1 — and the table is cleared once per pass, which is what
-      // large systems see: N = 262144 153 / 155 / 166 / 193 us.  Hence 16 N below 131072 bodies, 4 N from there on.
-      int slots = 1024;
-      const int factor = env_int("NBODY_SYM_DUP_FACTOR", p.n_total < 131072 ? 16 : 4);
-      while ((long long)slots < (long long)factor * p.n_total && slots < (1 << 30)) slots *= 2;
-      c->sym_dup_slots = slots;
-      if ((e = hipMalloc(&c->sym_dup_table, (size_t)slots * 8 + 64)) != hipSuccess) return bail(e, "hipMalloc duplicate detector");
-      if ((e = hipMemset(c->sym_dup_table, 0, (size_t)slots * 8 + 64)) != hipSuccess) return bail(e, "hipMemset duplicate detector");
-      if (p.precision != NBODY_PREC_F64 && c->sym_nsrc == 1) {       // fused stepping alternates between two tables
-        if ((e = hipMalloc(&c->sym_dup_table2, (size_t)slots * 8 + 64)) != hipSuccess) return bail(e, "hipMalloc duplicate detector");
-        if ((e = hipMemset(c->sym_dup_table2, 0, (size_t)slots * 8 + 64)) != hipSuccess) return bail(e, "hipMemset duplicate detector");
-      }
-    }
-    // equal-mass kernels (not with the eps floor, which is sized for G m |d|^-3, not for a bare |d|^-3).
-    // NBODY_SYM_NO_UNI=1 (A/B measurements only) keeps every context on the general kernels.
-    const char *no_uni = getenv("NBODY_SYM_NO_UNI");
-    if (p.zero_mode != NBODY_ZERO_FLOOR && !(no_uni && no_uni[0] == '1')) {
-      if ((e = hipMalloc(&c->sym_general, 64)) != hipSuccess) return bail(e, "hipMalloc equal-mass flag");
-      if ((e = hipMemset(c->sym_general, 0, 64)) != hipSuccess) return bail(e, "hipMemset equal-mass flag");
-    }
+    if (pol.dup_tables >= 1 && (e = zalloc(&c->sym_dup_table, table_bytes)) != hipSuccess) return bail(e, zalloc_op, "duplicate detector");
+    if (pol.dup_tables == 2 && (e = zalloc(&c->sym_dup_table2, table_bytes)) != hipSuccess) return bail(e, zalloc_op, "duplicate detector");
+    if (pol.equal_mass_word && (e = zalloc(&c->sym_general, 64)) != hipSuccess) return bail(e, zalloc_op, "equal-mass flag");
     if ((e = hipMalloc(&c->sym_send, (size_t)p.n_total * c->elem)) != hipSuccess) return bail(e, "hipMalloc send row");
     c->own_send = true;
-    if (c->sym_nsrc > 1) {
+    if (pol.recv_is_send) {
+      c->sym_recv = c->sym_send;
+    } else {
       if ((e = hipMalloc(&c->sym_recv, (size_t)c->sym_nsrc * p.i_count * c->elem)) != hipSuccess) return bail(e, "hipMalloc recv rows");
       c->own_recv = true;
-    } else {
-      c->sym_recv = c->sym_send;
     }
   } else {
     if ((e = hipMalloc(&c->accp, (size_t)c->j_split * p.i_count * c->elem)) != hipSuccess) return bail(e, "hipMalloc accp");
-    // packed one-sided kernel, exact d == 0: the same detector lets the tiles that hold no self pair run unguarded
-    // (N = 2^20: 276.8 -> 248.8 ms).  Below N = 32768 the detector's two extra launches cost more than they save
-    // (N = 8192: 27 -> 43 us).
-    const char *guarded = getenv("NBODY_SYM_GUARDED");
-    if (p.precision != NBODY_PREC_F64 && !c->wave && c->ipt % 2 == 0 && p.eps == 0.0 && p.zero_mode == NBODY_ZERO_EXACT &&
-        p.n_total >= 32768 &&
-        !(guarded && guarded[0] == '1')) {
-      int slots = 1024;                                              // as sparse as the symmetric pass's (above): short chains
-      const int factor = env_int("NBODY_SYM_DUP_FACTOR", p.n_total < 131072 ? 16 : 4);
-      while ((long long)slots < (long long)factor * p.n_total && slots < (1 << 30)) slots *= 2;
-      c->sym_dup_slots = slots;
-      if ((e = hipMalloc(&c->sym_dup_table, (size_t)slots * 8 + 64)) != hipSuccess) return bail(e, "hipMalloc duplicate detector");
-    }
-    // equal-mass form of the packed one-sided kernel and of the block kernel (not small_pk_kernel)
-    const char *no_uni = getenv("NBODY_SYM_NO_UNI");
-    if (p.precision != NBODY_PREC_F64 && ((c->wave >= 2 && p.precision == NBODY_PREC_F32) || (!c->wave && c->ipt % 2 == 0)) && p.zero_mode != NBODY_ZERO_SELECT &&
-        p.zero_mode != NBODY_ZERO_FLOOR && !(no_uni && no_uni[0] == '1')) {
-      if ((e = hipMalloc(&c->sym_general, 64)) != hipSuccess) return bail(e, "hipMalloc equal-mass flag");
-      if ((e = hipMemset(c->sym_general, 0, 64)) != hipSuccess) return bail(e, "hipMemset equal-mass flag");
-    }
+    // (the packed one-sided kernel's detector table is not cleared here: its launcher clears it before every pass)
+    if (pol.dup_tables >= 1 && (e = hipMalloc(&c->sym_dup_table, table_bytes)) != hipSuccess) return bail(e, "hipMalloc duplicate detector");
+    if (pol.equal_mass_word && (e = zalloc(&c->sym_general, 64)) != hipSuccess) return bail(e, zalloc_op, "equal-mass flag");
   }
-  if ((e = hipMalloc(&c->scratch, 64)) != hipSuccess) return bail(e, "hipMalloc scratch");
-  if ((e = hipMemset(c->scratch, 0, 64)) != hipSuccess) return bail(e, "hipMemset scratch");
+  if ((e = zalloc(&c->scratch, 64)) != hipSuccess) return bail(e, zalloc_op, "scratch");
   if (p.time_kernels) {
     // NBODY_SYM_ITEM_CLOCKS=1 (tools/even_items.py): room for every work item's own two stamps, word 2 says so
     c->clk_items = (c->sym && env_int("NBODY_SYM_ITEM_CLOCKS", 0) == 1) ? c->sym_items_n : 0;
     const size_t clk_bytes = 64 + 16 * (size_t)c->clk_items;
-    if ((e = hipMalloc(&c->clk, clk_bytes)) != hipSuccess) return bail(e, "hipMalloc clock words");
-    if ((e = hipMemset(c->clk, 0, clk_bytes)) != hipSuccess) return bail(e, "hipMemset clock words");
+    if ((e = zalloc((void **)&c->clk, clk_bytes)) != hipSuccess) return bail(e, zalloc_op, "clock words");
     if (c->clk_items) { const unsigned long long one = 1; if ((e = hipMemcpy(c->clk + 2, &one, 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy clock words"); }
     (void)hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, p.device);
-    (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, p.device);
+    c->cus = dev.cus;
   }
   if ((e = hipHostMalloc(&c->h_scratch, 64, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
   // the hipMemset calls above run on the null stream and return early; the context's own stream is non-blocking and would not
@@ -904,22 +679,12 @@ int nbody_synchronize(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-int nbody_set_state_soa(nbody_ctx *c, const float *posm4, const float *vel4, int32_t n) try {
-  if (!c || !posm4 || !vel4) return c ? fail(c, NBODY_ERR_INVALID, "nbody_set_state_soa: null buffer") : NBODY_ERR_INVALID;
-  if (n != c->p.n_total) return fail(c, NBODY_ERR_INVALID, "nbody_set_state_soa: n = %d but the context holds %d bodies", n, c->p.n_total);
-  if (c->multi) { const int rc = multi_rc(c, nbody::multi_set_state_soa(c->multi, posm4, vel4, n)); if (!rc) { c->have_state = true; c->steps_done = 0; } return rc; }
-  return upload_soa<float>(c, posm4, vel4);
-} catch (const std::bad_alloc &) {
-  return fail(c, NBODY_ERR_NOMEM, "nbody_set_state_soa: out of host memory");
+int nbody_set_state_soa(nbody_ctx *c, const float *posm4, const float *vel4, int32_t n) {
+  return set_state_soa<float>(c, posm4, vel4, n, "nbody_set_state_soa");
 }
 
-int nbody_set_state_soa_f64(nbody_ctx *c, const double *posm4, const double *vel4, int32_t n) try {
-  if (!c || !posm4 || !vel4) return c ? fail(c, NBODY_ERR_INVALID, "nbody_set_state_soa_f64: null buffer") : NBODY_ERR_INVALID;
-  if (n != c->p.n_total) return fail(c, NBODY_ERR_INVALID, "nbody_set_state_soa_f64: n = %d but the context holds %d bodies", n, c->p.n_total);
-  if (c->multi) { const int rc = multi_rc(c, nbody::multi_set_state_soa_f64(c->multi, posm4, vel4, n)); if (!rc) { c->have_state = true; c->steps_done = 0; } return rc; }
-  return upload_soa<double>(c, posm4, vel4);
-} catch (const std::bad_alloc &) {
-  return fail(c, NBODY_ERR_NOMEM, "nbody_set_state_soa_f64: out of host memory");
+int nbody_set_state_soa_f64(nbody_ctx *c, const double *posm4, const double *vel4, int32_t n) {
+  return set_state_soa<double>(c, posm4, vel4, n, "nbody_set_state_soa_f64");
 }
 
 }  // extern "C"
@@ -1165,9 +930,7 @@ int nbody_get_bounds(nbody_ctx *c, float *size) {
   if (rc) return rc;
   if (!size) return fail(c, NBODY_ERR_INVALID, "nbody_get_bounds: null output");
   if (c->multi) return multi_rc(c, nbody::multi_get_bounds(c->multi, size));
-  HIP_TRY(c, hipMemsetAsync(c->scratch, 0, 4, c->stream));
-  HIP_TRY(c, nbody::launch_bounds(c->p.precision, c->posm, c->p.i_begin, c->p.i_count, (unsigned int *)c->scratch, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 4, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = queue_bounds(c))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   memcpy(size, c->h_scratch, 4);
   return NBODY_OK;
@@ -1181,13 +944,7 @@ int nbody_energy(nbody_ctx *c, double *ke, double *pe) {
     HIP_TRY(c, hipMalloc(&c->energy_part, nbody::energy_partials(c->p.n_total, c->p.i_count) * sizeof(double)));
   HIP_TRY(c, nbody::launch_energy(c->p.precision, c->posm, c->vel, c->p.n_total, c->p.i_begin, c->p.i_count, c->p.G,
                                   c->p.eps * c->p.eps, (double *)c->energy_part, (double *)c->scratch, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  double v[2];
-  memcpy(v, c->h_scratch, 16);
-  if (ke) *ke = v[0];
-  if (pe) *pe = v[1];
-  return NBODY_OK;
+  return read_energy(c, ke, pe);
 }
 
 int nbody_get_positions(nbody_ctx *c, float *xyz, size_t stride, int32_t first, int32_t count) {
@@ -1204,39 +961,16 @@ int nbody_get_positions(nbody_ctx *c, float *xyz, size_t stride, int32_t first, 
   const bool direct = stride == 12 && in_pinned(c, xyz, bytes);     // caller's pinned buffer: DMA straight into it
   HIP_TRY(c, hipMemcpyAsync(direct ? (void *)xyz : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (direct) return NBODY_OK;
-  if (stride == 12) {
-    memcpy(xyz, c->h_stage, bytes);
-  } else {
-    char *o = (char *)xyz;
-    const char *src = (const char *)c->h_stage;
-    for (int i = 0; i < count; ++i) memcpy(o + (size_t)i * stride, src + (size_t)i * 12, 12);
-  }
+  if (!direct) scatter_records(xyz, stride, c->h_stage, 12, (size_t)count);
   return NBODY_OK;
 }
 
-int nbody_get_state_soa(nbody_ctx *c, float *posm4, float *vel4, float *acc4) try {
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if (c->multi) return multi_rc(c, nbody::multi_get_state_soa(c->multi, posm4, vel4, acc4));
-  if (posm4 && (rc = download4<float>(c, c->posm, (size_t)c->p.i_begin, (size_t)c->p.i_count, posm4))) return rc;
-  if (vel4 && (rc = download4<float>(c, c->vel, 0, (size_t)c->p.i_count, vel4))) return rc;
-  if (acc4 && (rc = download4<float>(c, c->acc, 0, (size_t)c->p.i_count, acc4))) return rc;
-  return NBODY_OK;
-} catch (const std::bad_alloc &) {
-  return fail(c, NBODY_ERR_NOMEM, "nbody_get_state_soa: out of host memory");
+int nbody_get_state_soa(nbody_ctx *c, float *posm4, float *vel4, float *acc4) {
+  return get_state_soa<float>(c, posm4, vel4, acc4, "nbody_get_state_soa");
 }
 
-int nbody_get_state_soa_f64(nbody_ctx *c, double *posm4, double *vel4, double *acc4) try {
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if (c->multi) return multi_rc(c, nbody::multi_get_state_soa_f64(c->multi, posm4, vel4, acc4));
-  if (posm4 && (rc = download4<double>(c, c->posm, (size_t)c->p.i_begin, (size_t)c->p.i_count, posm4))) return rc;
-  if (vel4 && (rc = download4<double>(c, c->vel, 0, (size_t)c->p.i_count, vel4))) return rc;
-  if (acc4 && (rc = download4<double>(c, c->acc, 0, (size_t)c->p.i_count, acc4))) return rc;
-  return NBODY_OK;
-} catch (const std::bad_alloc &) {
-  return fail(c, NBODY_ERR_NOMEM, "nbody_get_state_soa_f64: out of host memory");
+int nbody_get_state_soa_f64(nbody_ctx *c, double *posm4, double *vel4, double *acc4) {
+  return get_state_soa<double>(c, posm4, vel4, acc4, "nbody_get_state_soa_f64");
 }
 
 int nbody_get_particles(nbody_ctx *c, void *aos, size_t stride) {
@@ -1244,15 +978,10 @@ int nbody_get_particles(nbody_ctx *c, void *aos, size_t stride) {
   if (rc) return rc;
   if (!aos || stride < sizeof(nbody_particle)) return fail(c, NBODY_ERR_INVALID, "nbody_get_particles: null buffer or stride < 40");
   if (c->multi) return multi_rc(c, nbody::multi_get_particles(c->multi, aos, stride));
-  const size_t ic = (size_t)c->p.i_count;
-  const size_t bytes = ic * sizeof(nbody_particle);
-  if ((rc = ensure_stage(c, bytes))) return rc;
-  HIP_TRY(c, nbody::launch_pack_particles(c->p.precision, c->posm, c->vel, c->acc, (float *)c->d_stage, c->p.i_begin,
-                                          c->p.i_count, c->stream));
-  const bool direct = stride == sizeof(nbody_particle) && in_pinned(c, aos, bytes);
-  HIP_TRY(c, hipMemcpyAsync(direct ? aos : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
+  bool direct = false;
+  if ((rc = queue_particle_mirror(c, aos, stride, &direct))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (!direct) unstage_particles(c, aos, stride, ic);
+  if (!direct) scatter_records(aos, stride, c->h_stage, sizeof(nbody_particle), (size_t)c->p.i_count);
   return NBODY_OK;
 }
 
@@ -1280,20 +1009,13 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
     if ((rc = nbody::ensure_bh(c))) return rc;
     bh_frame = true;
   }
-  const size_t ic = (size_t)c->p.i_count, bytes = ic * sizeof(nbody_particle);
+  const size_t ic = (size_t)c->p.i_count;
+  bool direct = false;                                           // the records go straight into the caller's pinned mirror
   // systems on the one-launch step (theta == 0, up to 16384 bodies): the same launch leaves Size (of the positions before
   // the update, as .cpp:26 has it) and the frame's FParticle records — one kernel, the copies, one wait
   if (live && c->theta == 0.0f && (size || aos) && c->p.precision == NBODY_PREC_F32 && one_launch_ok(c)) {
-    // the records go straight into page-locked host memory — the caller's own mirror if it pinned it (nbody_pin_host_buffer),
-    // the context's staging buffer otherwise: no copy to wait for (profiles/r03_tick_parts_n2000.txt: the 80 KB copy of the
-    // shipped scene's mirror cost 12.7 us of a 32.7 us frame)
-    bool direct = false;
     void *stage = nullptr;
-    if (aos) {
-      if ((rc = ensure_stage(c, bytes))) return rc;
-      direct = stride == sizeof(nbody_particle) && in_pinned(c, aos, bytes) && ((uintptr_t)aos & 15u) == 0;
-      HIP_TRY(c, hipHostGetDevicePointer(&stage, direct ? aos : c->h_stage, 0));
-    }
+    if (aos && (rc = mirror_device_ptr(c, aos, stride, true, &direct, &stage))) return rc;
     unsigned int *words = (unsigned int *)c->scratch + 8;        // two words that take turns: this frame's (zero), the next one's
     unsigned int *cur = words + c->tick_word, *nxt = words + (c->tick_word ^ 1);
     if ((rc = step_one_launch(c, dt, stage, size ? cur : nullptr, size ? nxt : nullptr))) return rc;
@@ -1301,46 +1023,28 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
     if (size) { c->tick_word ^= 1; HIP_TRY(c, hipMemcpyAsync(c->h_scratch, cur, 4, hipMemcpyDeviceToHost, c->stream)); }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (size) memcpy(size, c->h_scratch, 4);
-    if (aos && !direct) unstage_particles(c, aos, stride, ic);
+    if (aos && !direct) scatter_records(aos, stride, c->h_stage, sizeof(nbody_particle), ic);
     return NBODY_OK;
   }
-  bool bh_direct = false;
   void *bh_stage = nullptr;
   if (bh_frame) {                                                // the walk writes the frame's records itself, Size rides with the verdict
-    // ... straight into page-locked host memory: the caller's mirror if it is pinned, the staging buffer otherwise
-    if (aos) {
-      if ((rc = ensure_stage(c, bytes))) return rc;
-      bh_direct = stride == sizeof(nbody_particle) && in_pinned(c, aos, bytes);
-      HIP_TRY(c, hipHostGetDevicePointer(&bh_stage, bh_direct ? aos : c->h_stage, 0));
-    }
+    if (aos && (rc = mirror_device_ptr(c, aos, stride, false, &direct, &bh_stage))) return rc;
     if ((rc = nbody::bh_queue_frame(c, dt, false, false, (float *)bh_stage))) return rc;
   } else if (live && size) {                                     // .cpp:26, 47-56: bounds of the positions BEFORE the step
-    HIP_TRY(c, hipMemsetAsync(c->scratch, 0, 4, c->stream));
-    HIP_TRY(c, nbody::launch_bounds(c->p.precision, c->posm, c->p.i_begin, c->p.i_count, (unsigned int *)c->scratch, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = queue_bounds(c))) return rc;
   }
   if (live && !bh_frame && (rc = nbody_step(c, dt, 1))) return rc;   // .cpp:27-31
-  bool direct = false;
-  if (aos) {                                                     // .cpp:33,41: what the frame draws
-    if ((rc = ensure_stage(c, bytes))) return rc;
-    if (!bh_frame)
-      HIP_TRY(c, nbody::launch_pack_particles(c->p.precision, c->posm, c->vel, c->acc, (float *)c->d_stage, c->p.i_begin,
-                                              c->p.i_count, c->stream));
-    direct = stride == sizeof(nbody_particle) && in_pinned(c, aos, bytes);
-    if (!bh_frame) HIP_TRY(c, hipMemcpyAsync(direct ? aos : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
-  }
+  if (aos && !bh_frame && (rc = queue_particle_mirror(c, aos, stride, &direct))) return rc;   // .cpp:33,41: what the frame draws
   int frame_rc = NBODY_OK;
   if (bh_frame) frame_rc = nbody::bh_run_frames(c, dt, 1, (float *)bh_stage, true);   // the frame's one wait (and, given up or handed back, once more)
   else HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (bh_frame && frame_rc != NBODY_OK && aos) {                 // a refused frame wrote no records: deliver the untouched state
-    HIP_TRY(c, nbody::launch_pack_particles(c->p.precision, c->posm, c->vel, c->acc, (float *)c->d_stage, c->p.i_begin,
-                                            c->p.i_count, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(direct ? aos : c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = queue_particle_mirror(c, aos, stride, &direct))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (bh_frame) { if (size) *size = nbody::bh_last_size(c->bh); }
   else if (live && size) memcpy(size, c->h_scratch, 4);
-  if (aos && !direct) unstage_particles(c, aos, stride, ic);
+  if (aos && !direct) scatter_records(aos, stride, c->h_stage, sizeof(nbody_particle), ic);
   return frame_rc;
 }
 
@@ -1576,8 +1280,7 @@ int nbody_bh_leaf_boxes(nbody_ctx *c, float *boxes, size_t stride) {
   HIP_TRY(c, nbody::bh_leaf_boxes(c->bh, c->d_stage, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (stride == 16) memcpy(boxes, c->h_stage, bytes);
-  else for (int i = 0; i < c->p.n_total; ++i) memcpy((char *)boxes + (size_t)i * stride, (const char *)c->h_stage + (size_t)i * 16, 16);
+  scatter_records(boxes, stride, c->h_stage, 16, (size_t)c->p.n_total);
   return NBODY_OK;
 }
 
@@ -1687,7 +1390,7 @@ int query_points(nbody_ctx *c, const char *who, const char *what, const char *ba
   if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return launch(d_pts, d_out); }))) return rc;
   HIP_TRY(c, hipMemcpyAsync(h_out, d_out, (size_t)n * out_floats * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t k = 0; k < (size_t)n; ++k) memcpy((char *)out + k * out_stride, h_out + out_floats * k, 4 * (size_t)width);
+  scatter_records(out, out_stride, h_out, 4 * (size_t)width, (size_t)n, 4 * out_floats);
   return NBODY_OK;
 }
 }  // namespace
@@ -1724,8 +1427,7 @@ int nbody_get_potentials(nbody_ctx *c, float *phi, size_t stride) {
   if ((rc = queue_body_potentials(c, "nbody_get_potentials", nullptr, (float *)c->d_stage))) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (stride == 4) memcpy(phi, c->h_stage, n * 4);
-  else for (size_t k = 0; k < n; ++k) memcpy((char *)phi + k * stride, (const char *)c->h_stage + k * 4, 4);
+  scatter_records(phi, stride, c->h_stage, 4, n);
   return NBODY_OK;
 }
 
@@ -1739,13 +1441,7 @@ int nbody_energy_fast(nbody_ctx *c, double *ke, double *pe) {
   double *phi64 = (double *)c->pot64, *partials = phi64 + n;
   if ((rc = queue_body_potentials(c, "nbody_energy_fast", phi64, nullptr))) return rc;
   HIP_TRY(c, nbody::launch_energy_fast(c->posm, c->vel, phi64, n, partials, (double *)c->scratch, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  double v[2];
-  memcpy(v, c->h_scratch, 16);
-  if (ke) *ke = v[0];
-  if (pe) *pe = v[1];
-  return NBODY_OK;
+  return read_energy(c, ke, pe);
 }
 
 int nbody_set_tracers(nbody_ctx *c, const float *pos4, const float *vel4, int32_t n) {
@@ -1882,16 +1578,7 @@ int nbody_kernel_clock(nbody_ctx *c, double *shader_mhz, int32_t *compute_units)
 const char *nbody_force_kernel_name(const nbody_ctx *c) {
   if (!c) return "";
   if (c->multi) return nbody_force_kernel_name(nbody::multi_part(c->multi, 0));
-  if (c->theta > 0.0f) return c->p.n_total <= 4096 ? "bh_walk_compact_kernel (+ bh_small_build_kernel)" : "bh_walk_lane_kernel (+ tree build)";
-  if (c->sym) return c->p.precision == NBODY_PREC_F64 ? "forces_sym_f64_kernel" : "forces_sym_pk_kernel";
-  if (c->wave) return c->p.precision == NBODY_PREC_F32 ? "forces_block_pk_kernel" : "forces_block_kernel";
-  if (c->p.precision != NBODY_PREC_F64 && c->ipt % 2 == 0 && (c->p.eps > 0.0 || c->p.zero_mode != NBODY_ZERO_SELECT))
-    return "forces_tile_pk_kernel";
-  return "forces_tile_kernel";
-}
-
-int32_t nbody_block_pairs_describe(int32_t n_total, int32_t compute_units) {
-  return n_total > 0 ? block_pairs(n_total, compute_units) : 0;
+  return nbody::force_kernel_name(c->sym, c->wave, c->ipt, c->p, c->theta);
 }
 
 int nbody_get_algorithm(nbody_ctx *c, int32_t *algorithm, int32_t *super_tile) {

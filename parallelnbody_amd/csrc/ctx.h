@@ -12,6 +12,7 @@
 
 #include "../../include/nbody.h"
 #include "kernels.h"
+#include "launch_policy.h"   // (g_create_error lives there: the policy's describe call reports through it too)
 #include "multi.h"
 #include "sym_plan.h"
 
@@ -103,8 +104,6 @@ struct nbody_ctx {
 };
 
 namespace nbody {
-
-inline thread_local std::string g_create_error;   // what nbody_last_error(nullptr) reports: a failed creation has no context to keep it
 
 inline int fail(nbody_ctx *c, int code, const char *fmt, ...) {
   char buf[512];

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "../../include/nbody.h"
+#include "launch_policy.h"
 #include "pk_common.h"
 #include "sym_common.h"
 
@@ -726,15 +727,8 @@ hipError_t launch_forces(const ForceLaunch &L, hipStream_t s) {
 }
 
 void forces_geometry(const ForceLaunch &L, int *blocks, int *threads) {
-  if (L.wave != 0) {
-    const int per = L.precision == NBODY_PREC_F32 ? 2 * L.wave : L.wave;   // bodies of a workgroup
-    if (blocks) *blocks = (L.i_count + per - 1) / per;
-    if (threads) *threads = kBlock;
-    return;
-  }
-  const int iblocks = (L.i_count + kBlock * L.ipt - 1) / (kBlock * L.ipt);
-  if (blocks) *blocks = iblocks * L.j_split;
-  if (threads) *threads = kBlock;
+  static_assert(kBlock == 256, "launch_policy.cpp's forces_geometry counts workgroups of 256 lanes");
+  forces_geometry(L.wave, L.precision, L.ipt, L.j_split, L.i_count, blocks, threads);
 }
 
 hipError_t launch_update(int precision, void *posm, void *vel, void *acc, const void *accp, int i_begin, int i_count,

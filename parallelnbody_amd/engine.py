@@ -103,6 +103,48 @@ def sym_plan_even(n_total, bodies_per_iset=2048, n_items=768):
     return items, pe.value
 
 
+def _params(n_total, i_begin=0, i_count=0, device=0, precision="f32", G=REF_G, eps=0.0, tile=0, i_per_thread=0, j_split=0,
+            time_kernels=False, zero_mode=0, algorithm=0, theta=0.0, bh_div_mode=0):
+    """struct nbody_params from NBodyEngine's keywords."""
+    p = Params()
+    _lib.lib().nbody_default_params(ctypes.byref(p))
+    p.n_total, p.i_begin, p.i_count, p.device = n_total, i_begin, i_count, device
+    p.precision = _PREC[precision] if isinstance(precision, str) else int(precision)
+    p.G, p.eps = G, eps
+    p.tile, p.i_per_thread, p.j_split = tile, i_per_thread, j_split
+    p.time_kernels = 1 if time_kernels else 0
+    p.zero_mode = zero_mode
+    p.algorithm = algorithm
+    p.theta = theta
+    p.bh_div_mode = bh_div_mode
+    return p
+
+
+_ALGO_NAME = {_lib.ALGO_TILED: "tiled", _lib.ALGO_SYMMETRIC: "symmetric"}
+
+
+def launch_policy(n_total, *, compute_units=256, device_total_bytes=0, **engine_keywords):
+    """What NBodyEngine(n_total, **engine_keywords) would report on a device with `compute_units` CUs and `device_total_bytes` of
+    memory (0: unknown, no plan is refused for its size) — host only, no device needed (nbody_launch_policy_describe).  The keys of
+    NBodyEngine.launch_config() plus pool_bytes, phases (sym_pool()), exchange_ranks, wave, detector_slots and the symmetric plan's
+    sym_slots, sym_k, sym_min_sub.  Raises NBodyError where the creation would fail for its arguments or its plan."""
+    L = _lib.lib()
+    p = _params(n_total, **engine_keywords)
+    out = _lib.LaunchPolicy()
+    out.struct_size = ctypes.sizeof(out)
+    rc = L.nbody_launch_policy_describe(ctypes.byref(p), compute_units, device_total_bytes, ctypes.byref(out))
+    if rc:
+        raise NBodyError(rc, L.nbody_last_error(None).decode())
+    cfg = {k: getattr(out, k) for k in ("tile", "i_per_thread", "j_split", "blocks", "threads")}
+    cfg["algorithm"] = _ALGO_NAME[out.algorithm]
+    cfg["super_tile"] = out.super_tile
+    cfg["kernel"] = out.kernel.decode()
+    cfg["plan"] = ("even" if out.plan_is_even else "guided") if cfg["algorithm"] == "symmetric" else None
+    for k in ("pool_bytes", "phases", "exchange_ranks", "wave", "detector_slots", "sym_slots", "sym_k", "sym_min_sub"):
+        cfg[k] = getattr(out, k)
+    return cfg
+
+
 def device_count():
     return int(_lib.lib().nbody_device_count())
 
@@ -113,17 +155,8 @@ class NBodyEngine:
     def __init__(self, n_total, *, i_begin=0, i_count=0, device=0, precision="f32", G=REF_G, eps=0.0, tile=0,
                  i_per_thread=0, j_split=0, time_kernels=False, zero_mode=0, algorithm=0, theta=0.0, devices=None, bh_div_mode=0):
         L = _lib.lib()
-        p = Params()
-        L.nbody_default_params(ctypes.byref(p))
-        p.n_total, p.i_begin, p.i_count, p.device = n_total, i_begin, i_count, device
-        p.precision = _PREC[precision] if isinstance(precision, str) else int(precision)
-        p.G, p.eps = G, eps
-        p.tile, p.i_per_thread, p.j_split = tile, i_per_thread, j_split
-        p.time_kernels = 1 if time_kernels else 0
-        p.zero_mode = zero_mode
-        p.algorithm = algorithm
-        p.theta = theta
-        p.bh_div_mode = bh_div_mode
+        p = _params(n_total, i_begin, i_count, device, precision, G, eps, tile, i_per_thread, j_split, time_kernels, zero_mode,
+                    algorithm, theta, bh_div_mode)
         h = ctypes.c_void_p()
         if devices is not None:
             # one context over several GPUs, driven from this thread (nbody_create_multi: RCCL between the devices)
@@ -478,7 +511,7 @@ class NBodyEngine:
         cfg = dict(zip(("tile", "i_per_thread", "j_split", "blocks", "threads"), (x.value for x in v)))
         algo, st = ctypes.c_int32(), ctypes.c_int32()
         self._check(self._L.nbody_get_algorithm(self._h, ctypes.byref(algo), ctypes.byref(st)))
-        cfg["algorithm"] = {_lib.ALGO_TILED: "tiled", _lib.ALGO_SYMMETRIC: "symmetric"}[algo.value]
+        cfg["algorithm"] = _ALGO_NAME[algo.value]
         cfg["super_tile"] = st.value
         cfg["kernel"] = self._L.nbody_force_kernel_name(self._h).decode()
         cfg["plan"] = ("even" if self._L.nbody_sym_plan_is_even(self._h) else "guided") if cfg["algorithm"] == "symmetric" else None

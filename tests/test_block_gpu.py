@@ -198,7 +198,7 @@ def test_energy_drift_of_the_one_launch_step(nb):
 
 
 def test_bits_do_not_depend_on_how_many_bodies_share_a_workgroup(nb):
-    # the register pairs per workgroup follow the CU count (block_pairs, csrc/capi.hip); no sum may depend on them
+    # the register pairs per workgroup follow the CU count (block_pairs, csrc/launch_policy.cpp); no sum may depend on them
     n = 7001
     posm, vel = scene(n, 123)
     ref = None

@@ -133,7 +133,7 @@ def test_even_shares_step_the_same_bits_every_time(nb, oracle, n, ipt):
 
 def test_which_systems_take_even_shares_by_default(nb):
     """Plain fp32, one context owning all bodies, 16385 <= N < 139264 — every size the symmetric pass runs below 139264 —
-    (csrc/capi.hip sym_even_default): sixteen bodies per lane from 24576, eight from 20480, four below; fp64 and sharded contexts and
+    (csrc/launch_policy.cpp sym_even_default): sixteen bodies per lane from 24576, eight from 20480, four below; fp64 and sharded contexts and
     larger systems keep the guided strips."""
     for n, plan, ipt in ((16385, "even", 4), (20479, "even", 4), (20480, "even", 8), (24575, "even", 8), (24576, "even", 16), (65536, "even", 16),
                          (90111, "even", 16), (90112, "even", 16), (139263, "even", 16), (139264, "guided", 16), (1 << 18, "guided", 16)):

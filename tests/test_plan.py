@@ -5,6 +5,8 @@ A plan is correct when, over all ranks of a job, every unordered pair of differe
 (symmetric strips) or, inside an i-set's own block, every ordered pair once (one-sided strips), and when no two partial-sum
 segments overlap.  The GPU parity tests then check the arithmetic; this file checks the bookkeeping for the sizes
 BASELINE.json names and for ragged / sharded ones."""
+import os
+
 import numpy as np
 import pytest
 
@@ -62,12 +64,18 @@ def test_every_pair_exactly_once(nb, n, ranks, bi, slots, own_mode):
 
 
 @pytest.mark.parametrize("n,ranks,bi,slots,k,min_sub", [
-    # what capi's choose_algorithm arrives at on a 256-CU device with the guided plan (the default outside 16385 <= N < 139264,
-    # and for Kahan, fp64 and sharded contexts everywhere): (bodies per i-set, workgroup slots, K, shortest strip)
-    (12288, 1, 512, 1024, 1, 2), (16384, 1, 512, 1024, 1, 2), (20480, 1, 1024, 1024, 1, 2), (32768, 1, 2048, 768, 1, 2),
+    # what the launch policy (csrc/launch_policy.cpp) arrives at for a plain fp32 NBODY_ALGO_SYMMETRIC context on a 256-CU device
+    # with the guided plan (the default outside 16385 <= N < 139264, and for Kahan, fp64 and sharded contexts everywhere): (bodies
+    # per i-set, workgroup slots, K, shortest strip) — checked against it below
+    (12288, 1, 512, 1024, 1, 2), (16384, 1, 512, 1024, 1, 2), (20480, 1, 1024, 1024, 1, 1), (32768, 1, 2048, 768, 1, 2),
     (65536, 1, 4096, 512, 1.5, 2), (131072, 1, 4096, 512, 1.5, 4), (262144, 1, 4096, 512, 3, 4), (65536, 2, 4096, 512, 1, 2),
     (131072, 8, 4096, 512, 1, 4), (100003, 1, 4096, 512, 1.5, 2)])
-def test_the_librarys_own_plans_cover_every_pair_once(nb, n, ranks, bi, slots, k, min_sub):
+def test_the_librarys_own_plans_cover_every_pair_once(nb, monkeypatch, n, ranks, bi, slots, k, min_sub):
+    for var in [v for v in os.environ if v.startswith("NBODY_")]:
+        monkeypatch.delenv(var)
+    monkeypatch.setenv("NBODY_SYM_EVEN", "0")                     # the guided plan also where even shares are the default
+    cfg = nb.launch_policy(n, compute_units=256, i_count=n // ranks if ranks > 1 else 0, algorithm=nb._lib.ALGO_SYMMETRIC)
+    assert (cfg["plan"], cfg["super_tile"], cfg["sym_slots"], cfg["sym_k"], cfg["sym_min_sub"]) == ("guided", bi, slots, k, min_sub)
     sym, one, _ = _coverage(nb, n, ranks, bi, slots, k, min_sub, 1)
     T, G = sym.shape
     blk = np.arange(G) * 64 // bi
@@ -158,7 +166,7 @@ def test_pool_phases_share_one_j_side_area(nb, n, ranks, bi, budget_frac):
 
 
 def test_block_kernel_pairs_per_workgroup_rule():
-    """forces_block_pk_kernel: how many register pairs of bodies a workgroup owns (csrc/capi.hip block_pairs).  A CU works
+    """forces_block_pk_kernel: how many register pairs of bodies a workgroup owns (csrc/launch_policy.cpp block_pairs).  A CU works
     through ceil(workgroups / CUs) workgroups of `pairs` pairs each: the rule takes the smallest product, larger workgroups
     on a tie.  Checked against the choices measured fastest (or within 6 %) in profiles/r03_block_kernel_np_by_n.txt."""
     import math

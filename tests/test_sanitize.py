@@ -1,5 +1,5 @@
 """Host-side code under AddressSanitizer + UBSan (CPU build only; the GPU pool runs no sanitizers): the oracle's C and
-the product's host-only C++ (initial-condition generators, the symmetric pass's work planner) are compiled with -fsanitize=address,undefined into a small
+the product's host-only C++ (initial-condition generators, the symmetric pass's work planner, the launch policy) are compiled with -fsanitize=address,undefined into a small
 driver and run on the shipped-scene sizes.  The reference has no sanitizer story; its latent hazards —
 unbounded recursion on coincident bodies, raw pointers into TArray storage — are the cases exercised here."""
 import os
@@ -15,6 +15,7 @@ DRIVER = r"""
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "../include/nbody.h"
 int oracle_forces_direct_f32(int, const float*, const float*, double, float, int, int, int, float*, int);
 int oracle_octree_forces_f32(int, const float*, const float*, const float*, float, float, double, int, float*, float*, int*);
@@ -68,6 +69,23 @@ int main(void) {
     if (nbody_sym_plan_describe_even(100003, 2048, 768, &n_items, &pool, NULL, 0) != 0 || n_items != 768) return 17;
     if (nbody_sym_plan_describe_even(700, 512, 100000, &n_items, &pool, NULL, 0) != 0 || n_items < 2) return 18;
     if (nbody_sym_plan_describe_even(65536, 1000, 512, &n_items, &pool, NULL, 0) == 0) return 19; }
+  /* the launch policy (csrc/launch_policy.cpp): a refused creation, a sharded slice, the block kernel, an even-share plan and a
+     pass in pool phases (N = 2^22 on a 64 GiB card) */
+  { nbody_params p; nbody_launch_policy pol;
+    memset(&p, 0, sizeof p); p.struct_size = sizeof p; p.G = 1e4;
+    memset(&pol, 0, sizeof pol); pol.struct_size = sizeof pol;
+    p.n_total = 65536; p.zero_mode = NBODY_ZERO_SELECT; p.algorithm = NBODY_ALGO_SYMMETRIC;
+    if (nbody_launch_policy_describe(&p, 256, 0, &pol) != NBODY_ERR_UNSUPPORTED) return 20;
+    p.zero_mode = NBODY_ZERO_EXACT; p.algorithm = NBODY_ALGO_AUTO; p.i_begin = 16384; p.i_count = 16384;
+    if (nbody_launch_policy_describe(&p, 256, 0, &pol) != NBODY_OK || pol.exchange_ranks != 4 || pol.plan_is_even) return 21;
+    p.i_begin = p.i_count = 0; p.n_total = 2000;
+    if (nbody_launch_policy_describe(&p, 0, 0, &pol) != NBODY_OK || pol.wave < 2 || strcmp(pol.kernel, "forces_block_pk_kernel")) return 22;
+    p.n_total = 32768;
+    if (nbody_launch_policy_describe(&p, 256, 0, &pol) != NBODY_OK || !pol.plan_is_even || pol.blocks != 512) return 23;
+    p.n_total = 1 << 22;
+    if (nbody_launch_policy_describe(&p, 256, 64ull << 30, &pol) != NBODY_OK || pol.phases < 2 || pol.pool_bytes > (32ull << 30)) return 24;
+    p.n_total = 0;
+    if (nbody_launch_policy_describe(&p, 256, 0, &pol) != NBODY_ERR_INVALID) return 25; }
   printf("sanitized run ok, nodes %d, |a0| %g\n", nodes, sqrt(acc[0]*acc[0] + acc[1]*acc[1] + acc[2]*acc[2]));
   free(posm); free(vel); free(pos); free(v3); free(m); free(acc); free(acc2);
   return 0;
@@ -86,10 +104,12 @@ def test_host_code_is_clean_under_asan_and_ubsan(tmp_path):
                            "-o", str(tmp_path / "ic.o")])
     subprocess.check_call(["g++", "-std=c++17", "-c", *san, os.path.join(ROOT, "parallelnbody_amd", "csrc", "sym_plan.cpp"),
                            "-o", str(tmp_path / "sym_plan.o")])
+    subprocess.check_call(["g++", "-std=c++17", "-c", *san, os.path.join(ROOT, "parallelnbody_amd", "csrc", "launch_policy.cpp"),
+                           "-o", str(tmp_path / "launch_policy.o")])
     subprocess.check_call(["gcc", "-std=c11", "-c", *san, str(drv), "-o", str(tmp_path / "driver.o")])
     exe = tmp_path / "driver"
     subprocess.check_call(["g++", *san, str(tmp_path / "driver.o"), str(tmp_path / "oracle.o"), str(tmp_path / "ic.o"),
-                           str(tmp_path / "sym_plan.o"), "-lm", "-o", str(exe)])
+                           str(tmp_path / "sym_plan.o"), str(tmp_path / "launch_policy.o"), "-lm", "-o", str(exe)])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
     out = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
