@@ -395,6 +395,58 @@ NBODY_AMD_API int nbody_get_state_soa_f64(nbody_ctx *ctx, double *posm4, double 
  * reference counterpart). */
 NBODY_AMD_API int nbody_energy(nbody_ctx *ctx, double *ke, double *pe);
 
+/*
+ * Bulk diagnostics of the owned bodies in one O(N) pass over the state (build-defined: the reference computes none): what a host checks
+ * after "does the energy hold", without reading 40 B per body back.  Every context answers: all three precisions, theta == 0 and
+ * theta > 0, deep-tree contexts, slice contexts and nbody_create_multi.
+ *
+ * nbody_get_moments: RAW sums over the owned bodies [i_begin, i_begin + i_count), about the ORIGIN.  Raw sums add: the shares of slice
+ *   contexts add field by field to the system's totals, as nbody_energy's shares do, and a multi-device context adds its parts' shares
+ *   in part order 0 .. n_dev - 1 in fp64 (n_dev = 1: nbody_create's result, bit for bit).  What is wanted about the centre of mass follows
+ *   on the host from the parallel-axis identities — com = mx / mass, v_com = p / mass, L_com = l - com x p,
+ *   second_com[ab] = second[ab] - mx[a] mx[b] / mass, kinetic_com = kinetic - p.p / (2 mass), torque_com = torque - com x force —
+ *   there are no entry points for them.
+ *   Every term is formed in fp64 from the state as it is held — fp32 widened to double on NBODY_PREC_F32 and _F32_KAHAN contexts, the
+ *   doubles themselves on NBODY_PREC_F64 — and summed in fp64.  Positions, velocities and accelerations are the ones nbody_get_particles /
+ *   nbody_get_state_soa would deliver at that moment: the live buffers, whichever the stepping path has left current, bound buffers
+ *   (nbody_bind_device_state) included.  The accelerations are the STORED ones: after nbody_step or nbody_tick that is a(x_n) beside
+ *   x_(n+1) — the field the bodies just felt; for the consistent set — virial, force and torque of the current positions — call
+ *   nbody_compute_forces first.  force and torque vanish to rounding for a pair sum (theta == 0); at theta > 0 they are what the
+ *   reference's monopole walk leaves.  On an unsoftened system (eps == 0) the consistent virial IS the potential energy.
+ *   Tracers are never summed.
+ *   Reproducibility: per-workgroup sums in fixed slots, folded in a fixed order, no atomics; the launch geometry is a function of i_count
+ *   alone (csrc/kernels_moments.hip) — not of the CU count, the precision or the device.  The same context state gives the same bits on
+ *   every call and on any part.
+ *   The call synchronises and changes nothing any getter shows; its device time is NOT counted under NBODY_KERNEL_FORCES / _UPDATE.
+ *   Set out->struct_size = sizeof(nbody_moments) first (as nbody_launch_policy): out == NULL or another size is NBODY_ERR_INVALID; no
+ *   particles set NBODY_ERR_STATE.
+ *
+ * nbody_mass_within: the cumulative mass profile about `centre`.  For each of k radii (1 <= k <= 64, each finite and >= 0, in any order,
+ *   each answered on its own): count[q] = number of owned bodies with d2 <= radii[q] * radii[q], mass[q] = the sum of their masses (fp64,
+ *   the same fixed order).  d2 is computed in fp64 with contraction off: dx = (double)x - centre[0] (dy, dz alike), d2 = (dx*dx + dy*dy)
+ *   + dz*dz; the threshold is one fp64 multiply.  Membership is therefore reproducible in plain C or numpy, and the counts are exact.
+ *   A radius' results depend neither on the other radii nor on their order.  Either output may be NULL, not both.  One pass over the
+ *   positions answers all k radii; Lagrangian radii (a selection) stay with the caller — 64 radii a call make that a few calls.
+ *   Slices, multi-device contexts (counts and masses add in part order), precisions, tracers and side effects: as nbody_get_moments.
+ *   NULL centre / radii, k outside 1 .. 64, a negative or non-finite radius: NBODY_ERR_INVALID.
+ */
+typedef struct nbody_moments {
+  uint32_t struct_size;   /* caller sets sizeof(nbody_moments) before the call */
+  int32_t  reserved;      /* written 0 */
+  int64_t  count;         /* bodies summed: the context's i_count */
+  double mass;            /* sum m */
+  double mx[3];           /* sum m x                       (centre of mass = mx / mass) */
+  double p[3];            /* sum m v                       linear momentum */
+  double l[3];            /* sum m (x cross v)             angular momentum about the origin */
+  double second[6];       /* sum m (xx, yy, zz, xy, xz, yz)  second moments about the origin */
+  double kinetic;         /* sum 1/2 m v.v */
+  double virial;          /* sum m (x . a)   a = the STORED accelerations (Clausius) */
+  double force[3];        /* sum m a         net force of the last force pass */
+  double torque[3];       /* sum m (x cross a) */
+} nbody_moments;          /* 16 + 24 * 8 = 208 bytes */
+NBODY_AMD_API int nbody_get_moments(nbody_ctx *ctx, nbody_moments *out);
+NBODY_AMD_API int nbody_mass_within(nbody_ctx *ctx, const double centre[3], const double *radii, int32_t k, double *mass, int64_t *count);
+
 /* ---- device plumbing (torch / RCCL interop) -------------------------------------------------- */
 
 /* Launch on the caller's HIP stream (hipStream_t as void*); NULL = the context's own stream. */

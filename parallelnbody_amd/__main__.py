@@ -51,6 +51,9 @@ def main(argv=None):
                     help="energy lines come from energy_fast(): the potential energy from the per-body potentials — at theta > 0 the "
                          "walk of the tree of the current positions, about one force pass instead of all pairs (plain f32 only; at "
                          "theta > 0 the stored accelerations become those of the current positions, the trajectory is unchanged)")
+    ap.add_argument("--moments-every", type=int, default=0,
+                    help="print |P|, |L|, the centre of mass, |net force|, |net torque| and the virial every K frames (one O(N) pass on "
+                         "the device; force, torque and virial are those of the accelerations the last step stored)")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -105,7 +108,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -117,6 +120,12 @@ def main(argv=None):
             frame = start + done
             if a.energy_every > 0 and frame % a.energy_every == 0:
                 print(json.dumps({"frame": frame, **energies()}), flush=True)
+            if a.moments_every > 0 and frame % a.moments_every == 0:
+                m = e.moments()
+                norm = lambda v: float(np.sqrt((np.asarray(v) ** 2).sum()))
+                print(json.dumps({"frame": frame, "moments": {"P": norm(m.p), "L": norm(m.l), "com": [float(c) for c in m.com],
+                                                              "net_force": norm(m.force), "net_torque": norm(m.torque),
+                                                              "virial": m.virial}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

@@ -63,6 +63,26 @@ class LaunchPolicy(ctypes.Structure):
     ]
 
 
+class Moments(ctypes.Structure):
+    """struct nbody_moments (include/nbody.h): raw fp64 sums over the owned bodies, about the origin."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_int32),
+        ("count", ctypes.c_int64),
+        ("mass", ctypes.c_double),
+        ("mx", ctypes.c_double * 3),
+        ("p", ctypes.c_double * 3),
+        ("l", ctypes.c_double * 3),
+        ("second", ctypes.c_double * 6),
+        ("kinetic", ctypes.c_double),
+        ("virial", ctypes.c_double),
+        ("force", ctypes.c_double * 3),
+        ("torque", ctypes.c_double * 3),
+    ]
+
+
+MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
+
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 DRAW_POINT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
 DRAW_BOX_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
@@ -142,6 +162,8 @@ def lib():
     sig("nbody_get_state_soa", c_int, vp, fp, fp, fp)
     sig("nbody_get_state_soa_f64", c_int, vp, dp, dp, dp)
     sig("nbody_energy", c_int, vp, dp, dp)
+    sig("nbody_get_moments", c_int, vp, ctypes.POINTER(Moments))
+    sig("nbody_mass_within", c_int, vp, dp, dp, c_i32, dp, ctypes.POINTER(c_i64))
     sig("nbody_set_stream", c_int, vp, vp)
     sig("nbody_device_ptr", c_int, vp, c_i32, ctypes.POINTER(vp), ctypes.POINTER(sz))
     sig("nbody_bind_device_state", c_int, vp, vp, vp, vp)

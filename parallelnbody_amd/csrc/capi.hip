@@ -619,6 +619,8 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->clk) (void)hipFree(c->clk);
   if (c->energy_part) (void)hipFree(c->energy_part);
+  if (c->moments_part) (void)hipFree(c->moments_part);
+  if (c->moments_host) (void)hipHostFree(c->moments_host);
   if (c->h_scratch) (void)hipHostFree(c->h_scratch);
   for (const auto &r : c->pinned) (void)hipHostUnregister(r.first);   // the memory itself stays the caller's
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -945,6 +947,51 @@ int nbody_energy(nbody_ctx *c, double *ke, double *pe) {
   HIP_TRY(c, nbody::launch_energy(c->p.precision, c->posm, c->vel, c->p.n_total, c->p.i_begin, c->p.i_count, c->p.G,
                                   c->p.eps * c->p.eps, (double *)c->energy_part, (double *)c->scratch, c->stream));
   return read_energy(c, ke, pe);
+}
+
+// nbody_get_moments / nbody_mass_within: the slots and results on the device and the results' pinned mirror, on first use
+static int ensure_moments(nbody_ctx *c) {
+  if (!c->moments_part) HIP_TRY(c, hipMalloc(&c->moments_part, nbody::moments_scratch_bytes(c->p.i_count)));
+  if (!c->moments_host) HIP_TRY(c, hipHostMalloc(&c->moments_host, 2 * nbody::kMassWithinMax * 8, hipHostMallocDefault));
+  return NBODY_OK;
+}
+
+int nbody_get_moments(nbody_ctx *c, nbody_moments *out) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (!out || out->struct_size != sizeof(nbody_moments))
+    return fail(c, NBODY_ERR_INVALID, "nbody_get_moments: null output or struct_size != sizeof(nbody_moments)");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (c->multi) return multi_rc(c, nbody::multi_moments(c->multi, out));
+  if ((rc = ensure_moments(c))) return rc;
+  // the buffers the getters read: c->posm is the live one of the one-launch step's two, c->acc holds every path's stored accelerations
+  HIP_TRY(c, nbody::launch_moments(c->p.precision, c->posm, c->vel, c->acc, c->p.i_begin, c->p.i_count, c->moments_part, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->moments_host, c->moments_part, nbody::kMomentValues * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  static_assert(sizeof(nbody_moments) == 16 + nbody::kMomentValues * sizeof(double), "nbody_moments: 24 sums behind the header");
+  out->reserved = 0;
+  out->count = c->p.i_count;
+  memcpy(&out->mass, c->moments_host, nbody::kMomentValues * sizeof(double));
+  return NBODY_OK;
+}
+
+int nbody_mass_within(nbody_ctx *c, const double centre[3], const double *radii, int32_t k, double *mass, int64_t *count) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (!centre || !radii || (!mass && !count)) return fail(c, NBODY_ERR_INVALID, "nbody_mass_within: null centre, radii or outputs");
+  if (k < 1 || k > nbody::kMassWithinMax) return fail(c, NBODY_ERR_INVALID, "nbody_mass_within: k = %d outside 1 .. %d", k, nbody::kMassWithinMax);
+  for (int q = 0; q < k; ++q)
+    if (!(radii[q] >= 0.0) || !std::isfinite(radii[q]))
+      return fail(c, NBODY_ERR_INVALID, "nbody_mass_within: radius %d is negative or not finite", q);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (c->multi) return multi_rc(c, nbody::multi_mass_within(c->multi, centre, radii, k, mass, count));
+  if ((rc = ensure_moments(c))) return rc;
+  HIP_TRY(c, nbody::launch_mass_within(c->p.precision, c->posm, c->p.i_begin, c->p.i_count, centre, radii, k, c->moments_part, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->moments_host, c->moments_part, 2 * nbody::kMassWithinMax * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (mass) memcpy(mass, c->moments_host, (size_t)k * sizeof(double));
+  if (count) memcpy(count, (const char *)c->moments_host + nbody::kMassWithinMax * 8, (size_t)k * sizeof(int64_t));
+  return NBODY_OK;
 }
 
 int nbody_get_positions(nbody_ctx *c, float *xyz, size_t stride, int32_t first, int32_t count) {

@@ -43,6 +43,7 @@ struct nbody_ctx {
   void *scratch = nullptr;     // 64 B device scratch (bounds bits, energy sums)
   void *h_scratch = nullptr;   // pinned mirror
   void *energy_part = nullptr; // nbody_energy: one pair of doubles per workgroup, folded in a fixed order
+  void *moments_part = nullptr, *moments_host = nullptr;   // nbody_get_moments / nbody_mass_within: results + per-workgroup slots (kernels_moments.hip), pinned mirror of the results
   int j_split = 1, j_chunk = 0, ipt = 1, tile = 256;
   int sym_np = 1;                        // register pairs per lane of the symmetric kernel
   std::vector<std::pair<char *, size_t>> pinned;   // caller memory page-locked by nbody_pin_host_buffer

@@ -258,4 +258,19 @@ size_t energy_partials(int n_total, int i_count);
 hipError_t launch_energy(int precision, const void *posm, const void *vel, int n_total, int i_begin, int i_count,
                          double G, double eps2, double *partials, double *out, hipStream_t s);
 
+// O(N) bulk diagnostics of the owned bodies — kernels_moments.hip.  Two launches each: per-workgroup slots, then one workgroup folds them
+// in a fixed order — no atomics, nothing to clear, reproducible bits.  The geometry (slots, bodies per slot) follows from i_count alone.
+// `scratch`: moments_scratch_bytes(i_count) of device memory; the results arrive at its start — launch_moments: kMomentValues doubles
+// in the field order of nbody_moments (mass ... torque[3]); launch_mass_within: kMassWithinMax doubles (the masses of the k radii), then
+// kMassWithinMax int64 (the counts).
+constexpr int kMomentValues = 24;
+constexpr int kMomentSlotCap = 1024;
+constexpr int kMassWithinMax = 64;
+void moments_geometry(int i_count, int *slots, int *per);
+size_t moments_scratch_bytes(int i_count);
+hipError_t launch_moments(int precision, const void *posm, const void *vel, const void *acc, int i_begin, int i_count, void *scratch,
+                          hipStream_t s);
+hipError_t launch_mass_within(int precision, const void *posm, int i_begin, int i_count, const double centre[3], const double *radii,
+                              int k, void *scratch, hipStream_t s);
+
 }  // namespace nbody

@@ -31,6 +31,9 @@ int multi_get_particles(Multi *m, void *aos, size_t stride);
 int multi_get_state_soa(Multi *m, float *posm4, float *vel4, float *acc4);
 int multi_get_state_soa_f64(Multi *m, double *posm4, double *vel4, double *acc4);
 int multi_energy(Multi *m, double *ke, double *pe);
+// the parts' shares added field by field (radius by radius) in part order 0 .. n_dev - 1, in fp64
+int multi_moments(Multi *m, nbody_moments *out);
+int multi_mass_within(Multi *m, const double centre[3], const double *radii, int32_t k, double *mass, int64_t *count);
 int multi_synchronize(Multi *m);
 int multi_kernel_time(Multi *m, int32_t which, double *total_ms, int64_t *launches);   // slowest device's total
 int multi_kernel_time_reset(Multi *m);

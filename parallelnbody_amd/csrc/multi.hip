@@ -7,8 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and enums only: the functions are resolved with dlsym
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -457,6 +459,40 @@ int multi_energy(Multi *m, double *ke, double *pe) {
   }
   if (ke) *ke = k_sum;
   if (pe) *pe = p_sum;
+  return NBODY_OK;
+}
+
+int multi_moments(Multi *m, nbody_moments *out) {
+  { const int rc = wait_gather(m); if (rc) return rc; }
+  constexpr int kSums = (int)((sizeof(nbody_moments) - offsetof(nbody_moments, mass)) / sizeof(double));
+  nbody_moments total;
+  for (int k = 0; k < m->n_dev; ++k) {
+    nbody_moments share;
+    share.struct_size = (uint32_t)sizeof share;
+    PART_TRY(m, k, nbody_get_moments(m->part[(size_t)k], &share), "nbody_get_moments");
+    if (k == 0) { total = share; continue; }                      // (part 0's bits as they are: one part is nbody_create's result)
+    double a[kSums], b[kSums];                                    // the 24 sums, mass ... torque[3], lie one behind the other
+    memcpy(a, &total.mass, sizeof a);
+    memcpy(b, &share.mass, sizeof b);
+    for (int f = 0; f < kSums; ++f) a[f] += b[f];
+    memcpy(&total.mass, a, sizeof a);
+    total.count += share.count;
+  }
+  *out = total;
+  return NBODY_OK;
+}
+
+int multi_mass_within(Multi *m, const double centre[3], const double *radii, int32_t k, double *mass, int64_t *count) {
+  { const int rc = wait_gather(m); if (rc) return rc; }
+  for (int d = 0; d < m->n_dev; ++d) {
+    double ms[64];
+    int64_t cs[64];
+    PART_TRY(m, d, nbody_mass_within(m->part[(size_t)d], centre, radii, k, ms, cs), "nbody_mass_within");
+    for (int q = 0; q < k; ++q) {
+      if (mass) mass[q] = d == 0 ? ms[q] : mass[q] + ms[q];
+      if (count) count[q] = d == 0 ? cs[q] : count[q] + cs[q];
+    }
+  }
   return NBODY_OK;
 }
 

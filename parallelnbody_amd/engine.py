@@ -1,5 +1,6 @@
 """NBodyEngine — Python handle on one nbody_ctx (include/nbody.h).  All arithmetic happens in the HIP
 kernels of libnbody_amd.so; this file only moves numpy buffers across the C-ABI."""
+import collections
 import ctypes
 import os
 
@@ -101,6 +102,22 @@ def sym_plan_even(n_total, bodies_per_iset=2048, n_items=768):
     if rc:
         raise NBodyError(rc, "nbody_sym_plan_describe_even: this system cannot be planned")
     return items, pe.value
+
+
+MOMENT_FIELDS = ("mass", "mx", "p", "l", "second", "kinetic", "virial", "force", "torque")
+
+# NBodyEngine.moments(): the raw sums of struct nbody_moments (floats / float64 arrays, about the origin; `second` = xx, yy, zz, xy, xz,
+# yz), then what the parallel-axis identities give on the host: com = mx / mass, com_velocity = p / mass, l_about_com = l - com x p
+MomentsResult = collections.namedtuple("MomentsResult", ("count",) + MOMENT_FIELDS + ("com", "com_velocity", "l_about_com"))
+
+
+def moments_result(count, sums):
+    """MomentsResult from the bodies' count and the raw sums (a mapping of MOMENT_FIELDS) — also of sums added over ranks or slices."""
+    raw = {k: (float(sums[k]) if k in ("mass", "kinetic", "virial") else np.array(sums[k], np.float64)) for k in MOMENT_FIELDS}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        com = raw["mx"] / raw["mass"]
+        vcom = raw["p"] / raw["mass"]
+    return MomentsResult(count=int(count), **raw, com=com, com_velocity=vcom, l_about_com=raw["l"] - np.cross(com, raw["p"]))
 
 
 def _params(n_total, i_begin=0, i_count=0, device=0, precision="f32", G=REF_G, eps=0.0, tile=0, i_per_thread=0, j_split=0,
@@ -381,6 +398,34 @@ class NBodyEngine:
         ke, pe = ctypes.c_double(), ctypes.c_double()
         self._check(self._L.nbody_energy(self._h, ctypes.byref(ke), ctypes.byref(pe)))
         return ke.value, pe.value
+
+    def moments(self):
+        """Bulk sums over the owned bodies in one O(N) device pass (nbody_get_moments): a MomentsResult — the raw fp64 sums about the
+        origin (they add over slices and ranks) and the derived com, com_velocity, l_about_com.  virial, force and torque use the
+        STORED accelerations: call compute_forces() first for the ones of the current positions."""
+        m = _lib.Moments()
+        m.struct_size = ctypes.sizeof(m)
+        self._check(self._L.nbody_get_moments(self._h, ctypes.byref(m)))
+        return moments_result(m.count, {k: (getattr(m, k) if k in ("mass", "kinetic", "virial") else list(getattr(m, k)))
+                                        for k in MOMENT_FIELDS})
+
+    def mass_within(self, centre, radii):
+        """(mass, count) of the owned bodies within each of `radii` of `centre` (nbody_mass_within; d^2 <= r^2 in fp64): float64 and
+        int64 arrays shaped like radii.  Any number of radii, 64 to a call — one pass over the positions each."""
+        c = np.ascontiguousarray(centre, np.float64)
+        if c.shape != (3,):
+            raise ValueError("mass_within: centre must be 3 numbers")
+        r = np.ascontiguousarray(radii, np.float64)
+        flat = r.reshape(-1)
+        mass = np.zeros(flat.shape[0], np.float64)
+        count = np.zeros(flat.shape[0], np.int64)
+        for lo in range(0, flat.shape[0], _lib.MASS_WITHIN_MAX):
+            part = np.ascontiguousarray(flat[lo:lo + _lib.MASS_WITHIN_MAX])
+            k = part.shape[0]
+            m, n = np.zeros(k, np.float64), np.zeros(k, np.int64)
+            self._check(self._L.nbody_mass_within(self._h, _dp(c), _dp(part), k, _dp(m), n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            mass[lo:lo + k], count[lo:lo + k] = m, n
+        return mass.reshape(r.shape), count.reshape(r.shape)
 
     # -- state out --
     def positions(self, first=0, count=None, out=None):

@@ -295,6 +295,39 @@ class ShardedSimulation:
                 ke, pe = float(t[0]), float(t[1])
         return ke, pe
 
+    def _sum_over_ranks(self, values):
+        """float64 array `values` added over the ranks (one all-reduce); itself on a single rank."""
+        values = np.ascontiguousarray(values, np.float64)
+        if self.world_size == 1:
+            return values
+        with self._on_stream():
+            t = self.torch.from_numpy(values).to(self.device)
+            self.torch.distributed.all_reduce(t, group=self.group)
+            return t.cpu().numpy()
+
+    def moments(self):
+        """The system's bulk sums (NBodyEngine.moments of every rank's share, added field by field in one fp64 all-reduce)."""
+        from .engine import MOMENT_FIELDS, moments_result
+        self.wait_for_positions()
+        m = self.engine.moments()
+        flat = np.concatenate([[float(m.count)]] + [np.atleast_1d(getattr(m, k)) for k in MOMENT_FIELDS])
+        flat = self._sum_over_ranks(flat)
+        sums, at = {}, 1
+        for k in MOMENT_FIELDS:
+            w = np.atleast_1d(getattr(m, k)).shape[0]
+            sums[k] = flat[at] if w == 1 else flat[at:at + w]
+            at += w
+        return moments_result(int(flat[0]), sums)
+
+    def mass_within(self, centre, radii):
+        """(mass, count) of the whole system's bodies within each radius of `centre` (the ranks' shares, one fp64 all-reduce; counts
+        are exact below 2^53)."""
+        self.wait_for_positions()
+        mass, count = self.engine.mass_within(centre, radii)
+        flat = self._sum_over_ranks(np.concatenate([mass.reshape(-1), count.reshape(-1).astype(np.float64)]))
+        k = mass.size
+        return flat[:k].reshape(mass.shape), np.rint(flat[k:]).astype(np.int64).reshape(count.shape)
+
     def close(self):
         if self.gather_stream is not None:
             if self.gather_work is not None:
