@@ -12,7 +12,11 @@
 //     per-lane ds_read_b128 from a doubled subtile image — and the body's running j-side sum travels with it from lane
 //     to lane (v_mov_b32_dpp wave_ror:1; ds_add_f32 on LDS was measured ~190 cycles per wave instruction and is not
 //     used).  After 64 steps the sums are home; the four waves' sums are added in wave order into the item's j-side
-//     segment;
+//     segment.  Guided plans (but the general form at eight register pairs) take two bodies per step instead,
+//     (l - k) & 63 and (l - k - 32) & 63, read as pairs (x_A, x_B), ... with one ds_read2_b32 per component, in two packed
+//     passes per register pair — (a A, b B), then (a B, b A) through op_sel — so that the travelling register pair holds the
+//     sums of two DIFFERENT bodies and moves once per double step: 32 double steps, half the v_mov_b32_dpp per pair
+//     evaluated; every body's sum comes home in two copies (lanes l and l ^ 32), added once per subtile;
 //   * strips inside the i-set's own block: the register pairs above the subtile's own pair meet it symmetrically (their
 //     bodies are other bodies of the block), its own pair one-sided (every ordered pair of its 512 bodies from both
 //     ends, d == 0 skipped), the pairs below are idle — they met these bodies when their own subtiles came up;
@@ -22,6 +26,7 @@
 #include "kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/nbody.h"
 #include "pk_common.h"
@@ -40,6 +45,9 @@ namespace {
 #ifndef NBODY_SYM_UNROLL4
 #define NBODY_SYM_UNROLL4 2   // four and more register pairs per lane: two steps in flight, not four
 #endif
+#ifndef NBODY_SYM_PAIR_STEPS
+#define NBODY_SYM_PAIR_STEPS 1   // guided plans walk a subtile in 32 double steps (sym_subtile); 0 (A/B builds): 64 single steps, as the even-share plans
+#endif
 
 // BARE = symmetric strips without any d == 0 handling (two packed ops per register pair cheaper than Z_CLAMP).  A
 // symmetric strip never contains a self pair (i-set and strip are disjoint), so d == 0 there means two DIFFERENT
@@ -53,10 +61,52 @@ namespace {
 // sums after every subtile (Acc3pk<true>::fold), the four waves' j-side sums are added in double, and reduce_j_kernel /
 // update_sym_kernel add the segments with compensation.  Each travelling sum is a register PAIR (lo: what the
 // lanes' first bodies contributed, hi: the second bodies'), fed by three v_pk_fma_f32 per register pair and folded
-// once, after the 64 steps: six v_mov_b32_dpp per step shared by the lane's NP register pairs.
+// once, after the 64 steps: six v_mov_b32_dpp per step shared by the lane's NP register pairs.  (Double steps: the pair is
+// two bodies' sums, six moves per DOUBLE step; a body's two copies are plain chains of 32 * 2 * NP terms each — the length
+// of lo and hi above — and are added once, plain, when they come home.)
 // waves per SIMD: packed ops are 4-cycle, two waves keep a SIMD within 2 % of four.
+// Which kernels walk double steps (sym_subtile_double): the guided plans' — all but the general form at eight register pairs.
+// That one has no registers for a fourth pair of j values: with double steps it measured SLOWER (N = 2^20, distinct masses:
+// 166.0 -> 168.4 ms a step, profiles/sym_pair_steps_full_bench_rows.txt) and keeps the single steps, as do the even-share plans.
+constexpr bool sym_pair_steps(int np, bool uni, bool even) { return !even && NBODY_SYM_PAIR_STEPS != 0 && (uni || np < 8); }
+
 constexpr int sym_waves(int np, bool kahan) {
   return np == 8 ? 2 : (np == 4 ? (kahan ? 2 : 3) : (kahan && np == 2 ? 3 : 4));
+}
+
+// The bodies of one double step, A = entry[32] and B = entry[0] behind byte address `addr` + 4 D of the doubled subtile image,
+// as three (four with the masses) even-aligned register pairs (x_A, x_B), (y_A, y_B), (z_A, z_B), (Gm_A, Gm_B): one
+// ds_read2_b32 each, two dwords 128 apart, straight from the DMA'd (x, y, z, G m) quads — hipcc reads the two quads whole and
+// then builds the pairs with v_mov_b32.  The compiler does not count the LDS reads of an asm statement: the statement waits
+// for them itself.
+template <int D, bool MASS>
+__device__ __forceinline__ void lds_body_pair(unsigned int addr, f2 &jx, f2 &jy, f2 &jz, f2 &jm) {
+  static_assert(D >= 0 && D + 131 <= 255, "ds_read2_b32 offsets are eight bits, in dwords");
+  constexpr int kA = 128, kB = 0;                                 // dword offsets of A's and B's quads
+  if constexpr (MASS)
+    asm volatile("ds_read2_b32 %0, %4 offset0:%5 offset1:%6\n\t"
+                 "ds_read2_b32 %1, %4 offset0:%7 offset1:%8\n\t"
+                 "ds_read2_b32 %2, %4 offset0:%9 offset1:%10\n\t"
+                 "ds_read2_b32 %3, %4 offset0:%11 offset1:%12\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(jx), "=&v"(jy), "=&v"(jz), "=&v"(jm)
+                 : "v"(addr), "n"(D + kA), "n"(D + kB), "n"(D + kA + 1), "n"(D + kB + 1), "n"(D + kA + 2), "n"(D + kB + 2), "n"(D + kA + 3),
+                   "n"(D + kB + 3)
+                 : "memory");
+  else
+    asm volatile("ds_read2_b32 %0, %3 offset0:%4 offset1:%5\n\t"
+                 "ds_read2_b32 %1, %3 offset0:%6 offset1:%7\n\t"
+                 "ds_read2_b32 %2, %3 offset0:%8 offset1:%9\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(jx), "=&v"(jy), "=&v"(jz)
+                 : "v"(addr), "n"(D + kA), "n"(D + kB), "n"(D + kA + 1), "n"(D + kB + 1), "n"(D + kA + 2), "n"(D + kB + 2)
+                 : "memory");
+}
+
+// v[lane ^ 32]: the other half of the wave (ds_bpermute_b32: through the LDS crossbar, no LDS memory touched)
+__device__ __forceinline__ float other_half(float v) {
+  const int peer = (int)((__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) ^ 32u) << 2);
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(peer, __builtin_bit_cast(int, v)));
 }
 
 // One 64-body subtile against the lane's register pairs P0 .. NP-1.  At step k lane l meets body (l - k) & 63 of the
@@ -75,7 +125,7 @@ constexpr int sym_waves(int np, bool kahan) {
 //   another item's).  A sum that starts at step ka in lane l is body (l - ka)'s; after step kb - 1 and its move, lane l
 //   holds body (l - kb)'s sum — the caller stores it there.
 template <int NP, int P0, bool ONE, int ZMODE, bool BARE, bool UNI, bool EVEN = false>
-__device__ __forceinline__ void sym_subtile(const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], const f2 (&nmi)[NP],
+__device__ __forceinline__ void sym_subtile_single(const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], const f2 (&nmi)[NP],
                                             Acc3pk<false> (&acc)[NP], const float4 *sp, f2 zp2, f2 one2, float &ox, float &oy,
                                             float &oz, int ka = 0, int kb = 64) {
   constexpr int NA = NP - P0;                                     // active register pairs
@@ -156,6 +206,118 @@ __device__ __forceinline__ void sym_subtile(const f2 (&xi)[NP], const f2 (&yi)[N
   if (UNI) { ox = -ox; oy = -oy; oz = -oz; }
 }
 
+// The same subtile in 32 DOUBLE steps (guided plans, sym_pair_steps): two bodies per step, half the moves.  Same pairs, same
+// outputs (ox, oy, oz: body `lane`'s sums) as sym_subtile_single above, whose comment explains P0, ONE and UNI.
+template <int NP, int P0, bool ONE, int ZMODE, bool BARE, bool UNI>
+__device__ __forceinline__ void sym_subtile_double(const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], const f2 (&nmi)[NP],
+                                                   Acc3pk<false> (&acc)[NP], const float4 *sp, f2 zp2, f2 one2, float &ox, float &oy,
+                                                   float &oz) {
+  constexpr int NA = NP - P0;                                     // active register pairs
+  // Guided plans: 32 DOUBLE steps.  At double step k lane l meets TWO bodies, A = (l - k) & 63 and B = (l - k - 32) & 63
+  // — entries sp[-k] and sp[-k - 32] of the doubled image, read as pairs (x_A, x_B), ... (lds_body_pair) —, in two
+  // packed passes per register pair (a, b): pass 1 evaluates (a A, b B), pass 2 (a B, b A) — B and A swapped through
+  // op_sel, for free.  The i-side sums take both passes as they are.  The travelling pair is (S_A, S_B), the j-side sums
+  // of two DIFFERENT bodies: pass 1 adds its products as they stand, pass 2 with the halves swapped (op_sel again), and
+  // the pair moves on once per double step — six v_mov_b32_dpp per two steps' worth of pairs.  Lanes l and l + 32 meet the
+  // same two bodies with the halves swapped, so every body's sum exists in two copies of 32 * 2 * NP terms; after the 32
+  // moves lane l holds body l's copy in the high half and body (l + 32) & 63's in the low half, and body l's sum is
+  // (high half of lane l) + (low half of lane l ^ 32), in that order: one exchange per component and subtile.
+  constexpr int kPairs = ONE ? 1 : (NA >= 4 ? 1 : 2);           // double steps in flight (two passes each)
+  f2 qx = splat2(0.f), qy = splat2(0.f), qz = splat2(0.f);      // (S_A, S_B)
+  // one packed pass over the active pairs A0 .. A1 - 1 (PART: 0 all, 1 the first half, 2 the second half); SW: pass 2, (B, A) by op_sel
+  auto pass = [&](auto second, auto part, f2 jx, f2 jy, f2 jz, f2 jm) __attribute__((always_inline)) {
+    constexpr int PART = decltype(part)::value, A0 = PART == 2 ? NA / 2 : 0, A1 = PART == 1 ? NA / 2 : NA;
+    constexpr bool SW = decltype(second)::value;                // pass 2: the products go to the other half of (S_A, S_B)
+    f2 dx[NA], dy[NA], dz[NA], w[NA], u[NA];
+#pragma unroll
+    for (int a = A0; a < A1; ++a) {
+      if (SW) { dx[a] = jx.yx - xi[P0 + a]; dy[a] = jy.yx - yi[P0 + a]; dz[a] = jz.yx - zi[P0 + a]; }
+      else    { dx[a] = jx - xi[P0 + a]; dy[a] = jy - yi[P0 + a]; dz[a] = jz - zi[P0 + a]; }
+    }
+#pragma unroll
+    for (int a = A0; a < A1; ++a) {
+      if (ZMODE == Z_SOFT) w[a] = fma2(dz[a], dz[a], zp2);
+      else                 w[a] = dz[a] * dz[a];
+      w[a] = fma2(dy[a], dy[a], w[a]);
+      w[a] = fma2(dx[a], dx[a], w[a]);
+    }
+    if (ZMODE == Z_CLAMP) {
+#pragma unroll
+      for (int a = A0; a < A1; ++a)
+        if (!BARE || (ONE && a == 0)) {                         // the one-sided pair holds the self pair: always guarded
+          f2 nf;
+          asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nf) : "v"(w[a]), "v"(zp2), "v"(one2));
+          w[a] = w[a] + nf;
+        }
+    }
+#pragma unroll
+    for (int a = A0; a < A1; ++a) u[a] = f2{rsq_dev(w[a].x), rsq_dev(w[a].y)};
+#pragma unroll
+    for (int a = A0; a < A1; ++a) {
+      w[a] = u[a] * u[a];
+      w[a] = w[a] * u[a];                                       // |d|^-3
+      if (!UNI) {
+        if (!(ONE && a == 0)) u[a] = w[a] * nmi[P0 + a];        // -G m_i |d|^-3
+        w[a] = SW ? w[a] * jm.yx : w[a] * jm;                   //  G m_j |d|^-3
+      }
+    }
+#pragma unroll
+    for (int a = A0; a < A1; ++a) {
+      acc[P0 + a].add(w[a], dx[a], dy[a], dz[a]);
+      if (!(ONE && a == 0)) {
+        const f2 sj = UNI ? w[a] : u[a];
+        if (SW) { qx = fma2(sj.yx, dx[a].yx, qx); qy = fma2(sj.yx, dy[a].yx, qy); qz = fma2(sj.yx, dz[a].yx, qz); }
+        else    { qx = fma2(sj, dx[a], qx); qy = fma2(sj, dy[a], qy); qz = fma2(sj, dz[a], qz); }
+      }
+    }
+  };
+  // the group's lowest entry, B of its last double step: sp[-32 - k - (kPairs - 1)] — down to sp[-63], the image's entry lane + 1
+  unsigned int addr = (unsigned int)(size_t)(const __attribute__((address_space(3))) float4 *)sp - 16u * (32 + kPairs - 1);
+#pragma unroll 1
+  for (int k = 0; k < 32; k += kPairs) {
+    auto dstep = [&](auto uc) __attribute__((always_inline)) {
+      constexpr int U = decltype(uc)::value;
+      f2 jx = splat2(0.f), jy = splat2(0.f), jz = splat2(0.f), jm = splat2(0.f);
+      lds_body_pair<4 * (kPairs - 1 - U), !UNI>(addr, jx, jy, jz, jm);
+      constexpr std::integral_constant<int, 0> all{};
+      constexpr std::integral_constant<int, 1> first{};
+      constexpr std::integral_constant<int, 2> rest{};
+      if constexpr (ONE && NA >= 5) {
+        // own-block subtiles with many active pairs (a small share of the work): half the pairs of one pass in flight, so that
+        // they never raise the kernel's register need (the single-step loop keeps one step in flight there)
+        pass(std::false_type{}, first, jx, jy, jz, jm);
+        __builtin_amdgcn_sched_barrier(0);
+        pass(std::false_type{}, rest, jx, jy, jz, jm);
+        __builtin_amdgcn_sched_barrier(0);
+        pass(std::true_type{}, first, jx, jy, jz, jm);
+        __builtin_amdgcn_sched_barrier(0);
+        pass(std::true_type{}, rest, jx, jy, jz, jm);
+      } else {
+        pass(std::false_type{}, all, jx, jy, jz, jm);
+        pass(std::true_type{}, all, jx, jy, jz, jm);
+      }
+      if (NA > (ONE ? 1 : 0)) {                                 // the sums move on with their bodies
+        qx = f2{wave_ror1(qx.x), wave_ror1(qx.y)}; qy = f2{wave_ror1(qy.x), wave_ror1(qy.y)};
+        qz = f2{wave_ror1(qz.x), wave_ror1(qz.y)};
+      }
+    };
+    dstep(std::integral_constant<int, 0>{});
+    if constexpr (kPairs == 2) dstep(std::integral_constant<int, 1>{});
+    addr -= 16u * kPairs;
+  }
+  ox = qx.y + other_half(qx.x); oy = qy.y + other_half(qy.x); oz = qz.y + other_half(qz.x);
+  if (UNI) { ox = -ox; oy = -oy; oz = -oz; }
+}
+
+// the subtile in the steps of its kernel (sym_pair_steps)
+template <int NP, int P0, bool ONE, int ZMODE, bool BARE, bool UNI, bool EVEN = false>
+__device__ __forceinline__ void sym_subtile(const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], const f2 (&nmi)[NP],
+                                            Acc3pk<false> (&acc)[NP], const float4 *sp, f2 zp2, f2 one2, float &ox, float &oy,
+                                            float &oz, int ka = 0, int kb = 64) {
+  if constexpr (sym_pair_steps(NP, UNI, EVEN)) sym_subtile_double<NP, P0, ONE, ZMODE, BARE, UNI>(xi, yi, zi, nmi, acc, sp, zp2, one2, ox, oy, oz);
+  else sym_subtile_single<NP, P0, ONE, ZMODE, BARE, UNI, EVEN>(xi, yi, zi, nmi, acc, sp, zp2, one2, ox, oy, oz, ka, kb);
+}
+
 // own-block subtile in register pair pc's slots: pick the instantiation (pc is wave-uniform)
 template <int NP, int PC, int ZMODE, bool BARE, bool UNI, bool EVEN = false>
 __device__ __forceinline__ void own_block_subtile(int pc, const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP],
@@ -184,6 +346,7 @@ __attribute__((amdgpu_waves_per_eu(sym_waves(NP, KAHAN), sym_waves(NP, KAHAN))))
 void forces_sym_pk_kernel(const float4 *__restrict__ posg, float4 *__restrict__ pool, const SymItem *__restrict__ items,
                           float zp, const int *__restrict__ dup_flag, int run_if_dup, const int *__restrict__ general,
                           int run_if_general, unsigned long long *__restrict__ clk, int wrap = 0) {
+  constexpr bool kPairSteps = sym_pair_steps(NP, UNI, EVEN);     // sym_subtile walks double steps
   constexpr bool kCanMerge = BARE && (NP <= 4 || UNI || EVEN);   // the general form at NP = 8 would spill (52 B of scratch); EVEN: see launch_forces_sym
   const bool merged = kCanMerge && run_if_dup < 0;
   if (!merged && dup_flag != nullptr && ((*dup_flag != 0) ? 1 : 0) != run_if_dup) return;
@@ -235,6 +398,9 @@ void forces_sym_pk_kernel(const float4 *__restrict__ posg, float4 *__restrict__ 
     asm volatile("" ::"v"(xi[p]), "v"(yi[p]), "v"(zi[p]));
     if (!UNI) asm volatile("" ::"v"(nmi[p]));
   }
+  // (double steps read the image in asm statements, which the compiler's wait counting does not see: the wave waits for its
+  // own DMA here, in front of the barrier)
+  if constexpr (kPairSteps) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                                               // tile 0 has landed (the barrier waits for the DMA)
 
   for (int c = 0; c < n_tiles; ++c) {
@@ -275,6 +441,7 @@ void forces_sym_pk_kernel(const float4 *__restrict__ posg, float4 *__restrict__ 
       const int home = EVEN ? sub * 64 + ((lane - kto) & 63) : sub * 64 + lane;
       sh_acc[wave][0][home] = ox; sh_acc[wave][1][home] = oy; sh_acc[wave][2][home] = oz;
     }
+    if constexpr (kPairSteps) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // the four waves' tile sums are complete; the next tile has landed
     {
       // thread e adds body e's sums (waves in fixed order) and stores them in the item's j-side segment
