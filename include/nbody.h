@@ -357,6 +357,55 @@ NBODY_AMD_API int nbody_potential_at(nbody_ctx *ctx, const float *xyz, size_t st
 NBODY_AMD_API int nbody_get_potentials(nbody_ctx *ctx, float *phi, size_t stride);
 NBODY_AMD_API int nbody_energy_fast(nbody_ctx *ctx, double *ke, double *pe);
 
+/*
+ * The tidal tensor T_ab = d a_a / d x_b, the second derivative of the potential (build-defined, like the potential), on the contexts that
+ * answer nbody_potential_at: plain fp32, one device, owning all bodies; Kahan, fp64, slice and nbody_create_multi contexts report
+ * NBODY_ERR_UNSUPPORTED.  Sign and softening are the pair law's own: with d = x_j - x and s^2 = |d|^2 + eps^2,
+ *     T_ab(x) = sum_j G m_j [ 3 d_a d_b / s^5 - delta_ab / s^3 ].
+ * Six components, in the order of nbody_moments.second: xx, yy, zz, xy, xz, yz.  At eps == 0 the trace is 0; at eps > 0 it is
+ * -3 sum G m eps^2 / s^5 (the Plummer density).
+ *
+ * nbody_tidal_at: T at n caller-given points — xyz: 3 floats each, `stride` bytes apart (>= 12); t: 6 floats each, `t_stride` bytes apart
+ * (>= 24).
+ *   theta == 0: the sum over all n_total bodies at their current positions.  With eps == 0 a pair at distance exactly 0 contributes
+ *     nothing, whatever zero_mode the context has (the potential's rule: no NBODY_ZERO_FLOOR eps floor, and for the same reason); with
+ *     eps > 0 a point exactly on a body feels that body's -G m / eps^3 on the diagonal.  The pair term is fp32 on the potential's distance
+ *     term (a 1-ulp reciprocal square root t = 1 / s): S_ab += (3 G m t^3)(d_a t)(d_b t) and Q += G m t^3 — no s^-5 is formed, so a pair
+ *     is finite wherever 3 G m / s^3 is.  A chunk's seven sums are each one chain of fused multiply-adds in body order; the chunks —
+ *     those of nbody_field_at, a function of n_total alone — are added in chunk order in fp64, T_aa = S_aa - Q is formed there, and each
+ *     component is rounded once.  A point's bits depend neither on the other points of the call, nor on n, nor on the strides, nor on
+ *     the device.
+ *   theta > 0: the walk of Octree::ComputeForces (OctreeSearch.h:99-108) over THE LAST TREE BUILT, with nbody_potential_at's rules.  An
+ *     accepted node (CoM c, mass M) adds, every operation one correctly rounded operation (plain C with contraction off reproduces it):
+ *         e_a = p_a - c_a (fp32, the differences d^2 was made of);  ds = sqrtf(d^2 [+ eps^2]) (fp32; the add one fp32 add)
+ *         u = 1.0 / (double)ds;  u2 = u * u;  gm = G * (double)M;  q3 = (gm * u) * u2;  h = (3.0 * q3) * u2
+ *         hx = h * ex;  hy = h * ey;  hz = h * ez                       (the doubles of the fp32 e)
+ *         Sxx += hx * ex;  Sxy += hx * ey;  Sxz += hx * ez;  Syy += hy * ey;  Syz += hy * ez;  Szz += hz * ez;  Q += q3
+ *     to seven fp64 sums in walk order; the result is (float)(Sxx - Q), (float)(Syy - Q), (float)(Szz - Q), (float)Sxy, (float)Sxz,
+ *     (float)Syz.  Consequences of the reference's rule, as for the potential: a point exactly on the root's CoM gets zeros, and from a
+ *     body's own position its own leaf adds nothing.  Without a valid last tree NBODY_ERR_STATE, after a tree deeper than 42 levels
+ *     NBODY_ERR_UNSUPPORTED, as nbody_field_at reports them.
+ *   n == 0 is a no-op; NULL pointers, n < 0, stride < 12 and t_stride < 24 are NBODY_ERR_INVALID.  The call synchronises and changes
+ *   nothing a getter of the state shows; its device time counts as one pass under NBODY_KERNEL_FORCES.
+ *
+ * nbody_get_tidal: every body's tensor from all OTHER bodies at the CURRENT positions — n_total x 6 floats, `stride` bytes apart (>= 24).
+ *   theta == 0: the sum above with the body itself left out BY INDEX; other bodies on the same point are skipped when eps == 0.  Changes
+ *     nothing a getter shows.
+ *   theta > 0: first exactly what nbody_compute_forces runs, then the walk of that tree from every body, as nbody_get_potentials: the same
+ *     side effects, and a refused frame returns that frame's error and no tensors.
+ *
+ * nbody_tidal_time: the tidal time scale t = ||T||_F^(-1/2) — a time that depends neither on velocities, nor on the frame, nor on a
+ *   softening length — minimised over the bodies: what a host needs to choose a dt the current state can bear.  Per body
+ *   n2 = ||T_i||_F^2 = (Txx^2 + Tyy^2) + Tzz^2 + 2 ((Txy^2 + Txz^2) + Tyz^2) in fp64 with contraction off, from the UNROUNDED fp64 tensors
+ *   of nbody_get_tidal (the fp64 fold at theta == 0, the fp64 walk sums at theta > 0); the largest n2 and the lowest body index that
+ *   attains it come from a fixed-order reduction without atomics: the same bits and the same body every run.  *t_min =
+ *   1 / sqrt(sqrt(max n2)); +inf when the maximum is 0 (a single body), 0 when it is not finite.  Synchronises; side effects as
+ *   nbody_get_tidal.  Either output may be NULL, not both (NBODY_ERR_INVALID).
+ */
+NBODY_AMD_API int nbody_tidal_at(nbody_ctx *ctx, const float *xyz, size_t stride, int32_t n, float *t, size_t t_stride);
+NBODY_AMD_API int nbody_get_tidal(nbody_ctx *ctx, float *t, size_t stride);
+NBODY_AMD_API int nbody_tidal_time(nbody_ctx *ctx, double *t_min, int32_t *body);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -4,7 +4,7 @@
 //   kernels_bh_sort.hip    the larger systems' path keys and their order: the sort from the previous frame's order, the cold sorts
 //   kernels_bh_build.hip   shared digits + node numbering, node words and leaves, ComputeMass (chunks + top, or a launch per level)
 //   kernels_bh_walk.hip    Octree::ComputeForces: the walks (wave / sixteen lanes / one lane per body), the Tick's update behind them
-//   kernels_bh_pot.hip     the walk of the last tree from a point, written once: the field (bh_probe_walk_kernel), the potential
+//   kernels_bh_pot.hip     the walk of the last tree from a point, written once: the field (bh_probe_walk_kernel), the tidal tensor (bh_tidal_walk_kernel), the potential
 //   bh_frame.hip           the host side: BhState, one frame queued on the stream (bh_frame), the verdict (bh_collect)
 // Here: the constants and the compact tree (SmallTree) the kernels and the host agree on, the device helpers more than one file
 // uses — each a restatement of a line of the reference, cited where it stands — and the kernels' declarations.
@@ -552,6 +552,10 @@ __global__ __launch_bounds__(kB) void bh_probe_walk_kernel(SmallTree T, float4 *
 template <bool HOP, bool SOFT, bool BODY>
 __global__ __launch_bounds__(kB) void bh_pot_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ phi64,
                                                          float *__restrict__ phif, int m, double G, float eps2);
+// the tidal tensor from the same walk (six values per point: xx, yy, zz, xy, xz, yz)
+template <bool HOP, bool SOFT, bool BODY>
+__global__ __launch_bounds__(kB) void bh_tidal_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ t64,
+                                                           float *__restrict__ tf, int m, double G, float eps2);
 
 }  // namespace bh
 }  // namespace nbody

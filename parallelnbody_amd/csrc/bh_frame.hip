@@ -550,6 +550,19 @@ hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *ph
   return hipGetLastError();
 }
 
+// The tidal tensor from the walk of the last tree (bh_tidal_walk_kernel): from m points, or — pts == nullptr — from the b->n bodies themselves.
+hipError_t bh_tidal_walk(BhState *b, const void *posm, const void *pts, double *t64, float *tf, int m, double G, float eps2, hipStream_t s) {
+  if (m <= 0 || !posm || (!t64 && !tf) || b->last_deep) return hipErrorInvalidValue;
+  if (pts == nullptr && m != b->n) return hipErrorInvalidValue;
+  if (pts != nullptr)
+    launch_point_walk(b, m, eps2, s, [](auto hop, auto soft) { return bh_tidal_walk_kernel<decltype(hop)::value, decltype(soft)::value, false>; },
+                      (const float4 *)pts, t64, tf, m, G, eps2);
+  else
+    launch_point_walk(b, m, eps2, s, [](auto hop, auto soft) { return bh_tidal_walk_kernel<decltype(hop)::value, decltype(soft)::value, true>; },
+                      (const float4 *)posm, t64, tf, m, G, eps2);
+  return hipGetLastError();
+}
+
 void bh_set_div_mode(BhState *b, int div_mode) { b->div_mode = div_mode ? 1 : 0; }
 
 // The deepest tree the context answers (42 .. kDeepMaxLevels; nbody_set_bh_max_depth).  Above 42 the deep frames' buffers are made

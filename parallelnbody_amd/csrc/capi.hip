@@ -115,8 +115,8 @@ int ensure_floor(nbody_ctx *c) {
 }
 
 // the partial rows of a slab of `m` points (kernels_probe.hip), grown on demand; freed at nbody_destroy
-int ensure_probe_part(nbody_ctx *c, int m) {
-  const size_t need = nbody::probe_part_elems(c->p.n_total, m);
+int ensure_probe_part(nbody_ctx *c, int m, int width = 1) {
+  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
   if (need <= c->probe_part_elems) return NBODY_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));                      // (a tracer pass may still be reading the old one)
   if (c->probe_part) (void)hipFree(c->probe_part);
@@ -613,7 +613,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1353,20 +1353,22 @@ int probes_supported(nbody_ctx *c, const char *who) {
   return NBODY_OK;
 }
 
-// the queries' staging: [2][probe_cap] float4 on the device and its pinned mirror, grown on demand
-int ensure_probe_staging(nbody_ctx *c, int n) {
-  if ((size_t)n <= c->probe_cap) return NBODY_OK;
+// the queries' staging: n points as float4 and `out_floats` floats each behind them, on the device and its pinned mirror, grown on demand
+// (probe_cap: in units of 32 bytes)
+int ensure_probe_staging(nbody_ctx *c, int n_points, size_t out_floats) {
+  const size_t n = ((size_t)n_points * (16 + 4 * out_floats) + 31) / 32;
+  if (n <= c->probe_cap) return NBODY_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->probe_dev) (void)hipFree(c->probe_dev);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   c->probe_dev = c->probe_host = nullptr; c->probe_cap = 0;
-  HIP_TRY(c, hipMalloc(&c->probe_dev, (size_t)n * 32));
-  HIP_TRY(c, hipHostMalloc(&c->probe_host, (size_t)n * 32, hipHostMallocDefault));
-  c->probe_cap = (size_t)n;
+  HIP_TRY(c, hipMalloc(&c->probe_dev, n * 32));
+  HIP_TRY(c, hipHostMalloc(&c->probe_host, n * 32, hipHostMallocDefault));
+  c->probe_cap = n;
   return NBODY_OK;
 }
 
-// theta > 0: is there a tree a query may walk?  (`what`: "field", "potential")
+// theta > 0: is there a tree a query may walk?  (`what`: "field", "potential", "tidal tensor")
 int probe_tree_ready(nbody_ctx *c, const char *who, const char *what) {
   if (!c->bh || !c->bh_tree_valid || c->bh_tree_theta != c->theta)
     return fail(c, NBODY_ERR_STATE, "%s: theta > 0 walks the last tree built, and there is none for this opening angle "
@@ -1406,13 +1408,42 @@ int queue_body_potentials(nbody_ctx *c, const char *who, double *phi64, float *p
   return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return queue_pot(c, nullptr, n, phi64, phif); });
 }
 
+// theta == 0: the tidal tensor of the bodies at their CURRENT positions at m points, queued (G and eps the context's; eps == 0: the
+// potential's d == 0 rule, whatever the zero_mode).  probe == nullptr: at the bodies themselves (m == n_total).
+int queue_tidal(nbody_ctx *c, const void *probe, int m, double *t64, float *tf) {
+  nbody::TidalLaunch L;
+  L.posm = c->posm; L.probe = probe; L.part = c->probe_part; L.t64 = t64; L.tf = tf;
+  L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps; L.clk = c->clk;
+  HIP_TRY(c, nbody::launch_tidal(L, c->stream));
+  return NBODY_OK;
+}
+
+// The bodies' tidal tensors at their CURRENT positions, queued as one pass under NBODY_KERNEL_FORCES: t64 ([n_total][6] double, device)
+// and / or tf ([n_total][6] float, device).  theta > 0: first exactly what nbody_compute_forces runs, as queue_body_potentials.
+int queue_body_tidal(nbody_ctx *c, const char *who, double *t64, float *tf) {
+  int rc;
+  const int n = c->p.n_total;
+  if (c->theta > 0.0f) {
+    if ((rc = run_forces(c, true, 0, 0.0f))) return rc;            // (a refused frame: its error, no tensors)
+    if ((rc = run_update(c, 0.0f))) return rc;
+    if ((rc = probe_tree_ready(c, who, "tidal tensor"))) return rc;
+    return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+      HIP_TRY(c, nbody::bh_tidal_walk(c->bh, c->posm, nullptr, t64, tf, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
+      return NBODY_OK;
+    });
+  }
+  if ((rc = ensure_probe_part(c, n, 2))) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return queue_tidal(c, nullptr, n, t64, tf); });
+}
+
 // One query at points that are not bodies: n points from (xyz, stride) in, `width` floats each out to (out, out_stride) — the
 // arguments' checks (`bad_args`: the message of a bad one), the tree or the partial rows the launch needs, the points as float4
 // through the pinned staging, launch(d_pts, d_out) timed as a pass under NBODY_KERNEL_FORCES, the values back (d_out: a float4 per
-// point for width 3, a float for width 1).  floor: the query follows the context's NBODY_ZERO_FLOOR.
+// point for width 3, `width` floats otherwise).  floor: the query follows the context's NBODY_ZERO_FLOOR.  part_width: the float4 of a
+// point in a chunk's partial row (theta == 0).
 template <class Launch>
 int query_points(nbody_ctx *c, const char *who, const char *what, const char *bad_args, bool floor, const float *xyz, size_t stride,
-                 int32_t n, float *out, size_t out_stride, int width, Launch launch) {
+                 int32_t n, float *out, size_t out_stride, int width, int part_width, Launch launch) {
   if (c && c->multi) return multi_unsupported(c, who);
   int rc = check_ready(c);
   if (rc) return rc;
@@ -1423,10 +1454,10 @@ int query_points(nbody_ctx *c, const char *who, const char *what, const char *ba
     if ((rc = probe_tree_ready(c, who, what))) return rc;
   } else {
     if (floor && (rc = ensure_floor(c))) return rc;
-    if ((rc = ensure_probe_part(c, n))) return rc;
+    if ((rc = ensure_probe_part(c, n, part_width))) return rc;
   }
-  if ((rc = ensure_probe_staging(c, n))) return rc;
-  const size_t out_floats = width == 3 ? 4 : 1;
+  const size_t out_floats = width == 3 ? 4 : (size_t)width;
+  if ((rc = ensure_probe_staging(c, n, out_floats))) return rc;
   float *h_pts = (float *)c->probe_host, *h_out = h_pts + 4 * (size_t)n;
   float *d_pts = (float *)c->probe_dev, *d_out = d_pts + 4 * (size_t)n;
   for (size_t k = 0; k < (size_t)n; ++k) {
@@ -1446,7 +1477,7 @@ extern "C" {
 
 int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *acc, size_t acc_stride) {
   return query_points(c, "nbody_field_at", "field", "null buffer, n < 0 or a stride < 12", true, xyz, stride, n, acc, acc_stride, 3,
-                      [&](float *d_pts, float *d_acc) -> int {
+                      1, [&](float *d_pts, float *d_acc) -> int {
     if (!(c->theta > 0.0f)) return queue_probe(c, d_pts, nullptr, d_acc, n, 0.0f);
     HIP_TRY(c, nbody::bh_probe_walk(c->bh, d_pts, nullptr, d_acc, n, c->p.G, (float)(c->p.eps * c->p.eps), 0.0f, c->stream));
     return NBODY_OK;
@@ -1456,7 +1487,7 @@ int nbody_field_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, flo
 // (no ensure_floor: the potential's d == 0 rule is the same under every zero_mode)
 int nbody_potential_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *phi, size_t phi_stride) {
   return query_points(c, "nbody_potential_at", "potential", "null buffer, n < 0, a point stride < 12 or a potential stride < 4", false, xyz,
-                      stride, n, phi, phi_stride, 1, [&](float *d_pts, float *d_phi) -> int {
+                      stride, n, phi, phi_stride, 1, 1, [&](float *d_pts, float *d_phi) -> int {
     if (!(c->theta > 0.0f)) return queue_pot(c, d_pts, n, nullptr, d_phi);
     HIP_TRY(c, nbody::bh_pot_walk(c->bh, c->posm, d_pts, nullptr, d_phi, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
     return NBODY_OK;
@@ -1489,6 +1520,49 @@ int nbody_energy_fast(nbody_ctx *c, double *ke, double *pe) {
   if ((rc = queue_body_potentials(c, "nbody_energy_fast", phi64, nullptr))) return rc;
   HIP_TRY(c, nbody::launch_energy_fast(c->posm, c->vel, phi64, n, partials, (double *)c->scratch, c->stream));
   return read_energy(c, ke, pe);
+}
+
+int nbody_tidal_at(nbody_ctx *c, const float *xyz, size_t stride, int32_t n, float *t, size_t t_stride) {
+  return query_points(c, "nbody_tidal_at", "tidal tensor", "null buffer, n < 0, a point stride < 12 or a tensor stride < 24", false, xyz,
+                      stride, n, t, t_stride, 6, 2, [&](float *d_pts, float *d_t) -> int {
+    if (!(c->theta > 0.0f)) return queue_tidal(c, d_pts, n, nullptr, d_t);
+    HIP_TRY(c, nbody::bh_tidal_walk(c->bh, c->posm, d_pts, nullptr, d_t, n, c->p.G, (float)(c->p.eps * c->p.eps), c->stream));
+    return NBODY_OK;
+  });
+}
+
+int nbody_get_tidal(nbody_ctx *c, float *t, size_t stride) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_get_tidal");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_get_tidal"))) return rc;
+  if (!t || stride < 24) return fail(c, NBODY_ERR_INVALID, "nbody_get_tidal: null buffer or stride < 24");
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * 24))) return rc;
+  if ((rc = queue_body_tidal(c, "nbody_get_tidal", nullptr, (float *)c->d_stage))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * 24, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  scatter_records(t, stride, c->h_stage, 24, n);
+  return NBODY_OK;
+}
+
+int nbody_tidal_time(nbody_ctx *c, double *t_min, int32_t *body) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_tidal_time");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = probes_supported(c, "nbody_tidal_time"))) return rc;
+  if (!t_min && !body) return fail(c, NBODY_ERR_INVALID, "nbody_tidal_time: both outputs are null");
+  const int n = c->p.n_total;
+  if (!c->tidal64) HIP_TRY(c, hipMalloc(&c->tidal64, (6 * (size_t)n + 2 * (size_t)nbody::energy_fast_slots(n)) * sizeof(double)));
+  double *t64 = (double *)c->tidal64, *partials = t64 + 6 * (size_t)n;
+  if ((rc = queue_body_tidal(c, "nbody_tidal_time", t64, nullptr))) return rc;
+  HIP_TRY(c, nbody::launch_tidal_time(t64, n, partials, (double *)c->scratch, c->stream));
+  double n2 = 0.0, at = 0.0;
+  if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
+  // t = ||T||_F^(-1/2) = n2^(-1/4)
+  if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);
+  if (body) *body = (int32_t)at;
+  return NBODY_OK;
 }
 
 int nbody_set_tracers(nbody_ctx *c, const float *pos4, const float *vel4, int32_t n) {

@@ -92,8 +92,9 @@ struct nbody_ctx {
   void *tr_pos = nullptr, *tr_vel = nullptr, *tr_acc = nullptr;   // [tr_n] float4 each
   void *probe_part = nullptr;  // the j chunks' partial rows of one slab of points (theta == 0), shared by tracers and queries
   size_t probe_part_elems = 0;
-  void *probe_dev = nullptr, *probe_host = nullptr;   // nbody_field_at: [2][probe_cap] float4 — the points, their accelerations — on the device, and its pinned mirror
+  void *probe_dev = nullptr, *probe_host = nullptr;   // the point queries: probe_cap units of 32 bytes — the points as float4, behind them their results — on the device, and its pinned mirror
   size_t probe_cap = 0;
+  void *tidal64 = nullptr;     // nbody_tidal_time: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;

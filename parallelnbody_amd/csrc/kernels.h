@@ -89,12 +89,13 @@ struct ProbeLaunch {
   void *clk = nullptr;          // two device uint64 the workgroups add their clock intervals to (pk_common.h)
 };
 void probe_geometry(int n_total, int *j_split, int *j_chunk);
-size_t probe_slab_points(int n_total);                        // points whose partial rows fit kProbePartBytes (a multiple of 1024)
-inline size_t probe_part_elems(int n_total, int m) {            // float4 elements `part` must hold for a launch of m points
+// width: the float4 a point has in a chunk's partial row at most (1: the field, the potential; 2: the tidal tensor)
+size_t probe_slab_points(int n_total, int width = 1);         // points whose partial rows fit kProbePartBytes (a multiple of 1024)
+inline size_t probe_part_elems(int n_total, int m, int width = 1) {   // float4 elements `part` must hold for a launch of m points
   int js, jc;
   probe_geometry(n_total, &js, &jc);
-  const size_t slab = probe_slab_points(n_total);
-  return (size_t)js * ((size_t)m < slab ? (size_t)m : slab);
+  const size_t slab = probe_slab_points(n_total, width);
+  return (size_t)js * ((size_t)m < slab ? (size_t)m : slab) * (size_t)width;
 }
 hipError_t launch_probe(const ProbeLaunch &L, hipStream_t s);
 
@@ -118,6 +119,28 @@ hipError_t launch_pot(const PotLaunch &L, hipStream_t s);
 constexpr int kEnergyFastSlots = 1024;
 int energy_fast_slots(int n);
 hipError_t launch_energy_fast(const void *posm, const void *vel, const double *phi64, int n, double *partials, double *out, hipStream_t s);
+
+// The bodies' tidal tensor at theta = 0 — kernels_probe.hip: T_ab(x) = sum_j G m_j [3 d_a d_b / s^5 - delta_ab / s^3], d = x_j - x,
+// s^2 = |d|^2 + eps2, over all n_total bodies.  Seven fp32 sums per point and chunk of probe_geometry — S_ab = sum (3 G m / s^3)(d_a / s)
+// (d_b / s), Q = sum G m / s^3, no s^-5 anywhere —, each one fused chain in body order; a partial row is two float4 per point
+// (probe_slab_points(n_total, 2)).  The chunks' rows are added in chunk order in fp64, T_aa = S_aa - Q there: t64 gets the six doubles
+// (xx, yy, zz, xy, xz, yz), tf the same rounded once; either may be null.  With eps2 == 0 a pair at distance 0 adds nothing.
+// probe == nullptr: the points are the bodies themselves (m == n_total) and every body leaves itself out by index.
+struct TidalLaunch {
+  const void *posm = nullptr;   // [n_total] float4: x, y, z, m
+  const void *probe = nullptr;  // [m] float4: x, y, z, unused; nullptr: posm
+  void *part = nullptr;         // [probe_part_elems(n_total, m, 2)] float4
+  double *t64 = nullptr;        // [m][6]
+  float *tf = nullptr;          // [m][6]
+  int n_total = 0, m = 0;
+  double G = 0.0, eps2 = 0.0;
+  void *clk = nullptr;
+};
+hipError_t launch_tidal(const TidalLaunch &L, hipStream_t s);
+// out[0] = max over the n bodies of n2 = (Txx^2 + Tyy^2) + Tzz^2 + 2 ((Txy^2 + Txz^2) + Tyz^2) from t64 (a value that is not finite counts
+// as +inf), out[1] = the lowest index that attains it, as a double: per-workgroup pairs into `partials` (2 * energy_fast_slots(n) doubles),
+// then one workgroup folds them — a fixed order, no atomics.
+hipError_t launch_tidal_time(const double *t64, int n, double *partials, double *out, hipStream_t s);
 
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
@@ -235,6 +258,9 @@ hipError_t bh_probe_walk(BhState *b, void *pts, void *vel, void *acc, int m, dou
 // phi = -(the fp64 sum in walk order) to phi64 and, rounded, to phif (either may be null).  pts == nullptr: the points are the bodies
 // (posm, n of them), walked in key order and written at the body's index — a body meets its own leaf at d == 0, which adds nothing.
 hipError_t bh_pot_walk(BhState *b, const void *posm, const void *pts, double *phi64, float *phif, int m, double G, float eps2, hipStream_t s);
+// The tidal tensor from the same walk: seven fp64 sums in walk order (kernels_bh_pot.hip: tidal_term), T_aa = S_aa - Q; six doubles per
+// point to t64 and, rounded, six floats to tf (either may be null).  pts == nullptr: the bodies, as bh_pot_walk takes them.
+hipError_t bh_tidal_walk(BhState *b, const void *posm, const void *pts, double *t64, float *tf, int m, double G, float eps2, hipStream_t s);
 bool bh_last_deep(const BhState *b);                          // the last frame queued was built by the deep path
 hipError_t bh_get_root_com(BhState *b, float out[3], hipStream_t s);
 hipError_t bh_set_root_com(BhState *b, const float in[3], hipStream_t s);

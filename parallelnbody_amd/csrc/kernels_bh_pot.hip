@@ -3,6 +3,8 @@
 //   bh_probe_walk_kernel  <- the force's term (force_term): nbody_field_at's points and the tracers of nbody_set_tracers at theta > 0
 //   bh_pot_walk_kernel    <- the potential's term (pot_term): nbody_potential_at, nbody_get_potentials, nbody_energy_fast at theta > 0
 //                            (build-defined: the reference computes no potential)
+//   bh_tidal_walk_kernel  <- the tidal tensor's term (tidal_term): nbody_tidal_at, nbody_get_tidal, nbody_tidal_time at theta > 0
+//                            (build-defined as well)
 #include "bh_common.h"
 #include "bh_force_term.h"
 #include "tracer_update.h"
@@ -136,10 +138,53 @@ __global__ __launch_bounds__(kB) void bh_pot_walk_kernel(SmallTree T, const floa
   if (phif != nullptr) phif[at] = (float)phi;
 }
 
+// The tidal tensor T_ab = d a_a / d x_b: one lane per point or per body, as bh_pot_walk_kernel.  An accepted node (CoM c, mass M) adds, every
+// operation one correctly rounded operation (contraction off):
+//   e = p - c (fp32, the differences d2 was made of); ds = sqrtf(d2 [+ eps2]); u = 1.0 / (double)ds — pot_term with the numerator
+//   1.0 (G = 1, M = 1: exactly that division; its preconditions on ds are the potential's own) —; u2 = u * u; gm = G * (double)M;
+//   q3 = (gm * u) * u2; h = (3.0 * q3) * u2; hx = h * ex, ...; Sxx += hx * ex, Sxy += hx * ey, Sxz += hx * ez, Syy += hy * ey,
+//   Syz += hy * ez, Szz += hz * ez; Q += q3
+// to seven fp64 sums in walk order.  T = (Sxx - Q, Syy - Q, Szz - Q, Sxy, Sxz, Syz): six doubles to t64, rounded once to tf.
+template <bool HOP, bool SOFT, bool BODY>
+__global__ __launch_bounds__(kB) void bh_tidal_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ t64,
+                                                           float *__restrict__ tf, int m, double G, float eps2) {
+#pragma clang fp contract(off)
+  const int k = (BODY ? xcd_run_block() : (int)blockIdx.x) * kB + threadIdx.x;
+  const bool valid = k < m;
+  const int status = T.hdr[3], nodes_all = T.hdr[0];
+  if (status != 0) return;
+  const int at = BODY ? (valid ? (int)T.sidx[k] : 0) : (valid ? k : 0);
+  const float4 p = pts[at];
+  double sxx = 0.0, syy = 0.0, szz = 0.0, sxy = 0.0, sxz = 0.0, syz = 0.0, q = 0.0;
+  walk_from_point<HOP>(T, p, valid ? nodes_all : 0, [&](const float4 &cm, float d2) {
+#pragma clang fp contract(off)
+    const double ex = (double)(p.x - cm.x), ey = (double)(p.y - cm.y), ez = (double)(p.z - cm.z);
+    const double u = pot_term<SOFT>(d2, 1.0f, 1.0, eps2);
+    const double u2 = u * u, gm = G * (double)cm.w;
+    const double q3 = (gm * u) * u2;
+    const double h = (3.0 * q3) * u2;
+    const double hx = h * ex, hy = h * ey, hz = h * ez;
+    sxx = sxx + hx * ex; sxy = sxy + hx * ey; sxz = sxz + hx * ez;
+    syy = syy + hy * ey; syz = syz + hy * ez;
+    szz = szz + hz * ez;
+    q = q + q3;
+  });
+  if (!valid) return;
+  const double t[6] = {sxx - q, syy - q, szz - q, sxy, sxz, syz};
+  const size_t o = (size_t)at * 6;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    if (t64 != nullptr) t64[o + c] = t[c];
+    if (tf != nullptr) tf[o + c] = (float)t[c];
+  }
+}
+
 #define BH_POINT_WALK_KERNELS(HOP, SOFT)                                                                                           \
   template __global__ void bh_probe_walk_kernel<HOP, SOFT>(SmallTree, float4 *, float4 *, float4 *, int, double, float, float);    \
   template __global__ void bh_pot_walk_kernel<HOP, SOFT, false>(SmallTree, const float4 *, double *, float *, int, double, float); \
-  template __global__ void bh_pot_walk_kernel<HOP, SOFT, true>(SmallTree, const float4 *, double *, float *, int, double, float);
+  template __global__ void bh_pot_walk_kernel<HOP, SOFT, true>(SmallTree, const float4 *, double *, float *, int, double, float);  \
+  template __global__ void bh_tidal_walk_kernel<HOP, SOFT, false>(SmallTree, const float4 *, double *, float *, int, double, float); \
+  template __global__ void bh_tidal_walk_kernel<HOP, SOFT, true>(SmallTree, const float4 *, double *, float *, int, double, float);
 BH_POINT_WALK_KERNELS(false, false)
 BH_POINT_WALK_KERNELS(false, true)
 BH_POINT_WALK_KERNELS(true, false)

@@ -1,6 +1,6 @@
 // The theta = 0 point queries: the bodies' field and potential at points (nbody_field_at and the tracers of nbody_set_tracers;
-// nbody_potential_at, nbody_get_potentials, nbody_energy_fast — the potential is build-defined: the reference computes none).
-// One tile loop (point_tile.h), two pair terms:
+// nbody_potential_at, nbody_get_potentials, nbody_energy_fast — the potential is build-defined: the reference computes none — and the
+// tidal tensor, build-defined as well).  One tile loop (point_tile.h), three pair terms:
 //   probe_tile_pk_kernel   <- the pair law OctreeSearch.h:101-104 of a massless point against every body, i.e. the loop
 //                             OctreeSearch.cpp:83-86 with the i side taken from another array
 //   probe_fold_kernel      <- the chunks' partial rows added in chunk order and, for tracers, OctreeSearch.cpp:29-30 (v += dt*a; x += dt*v)
@@ -8,7 +8,12 @@
 //                             points are the bodies themselves, j == i dropped by index
 //   pot_fold_kernel        <- the chunks' partial rows added in chunk order in fp64, negated, rounded once
 //   energy_fast_*_kernel   <- 1/2 m v^2 and 1/2 m phi from the unrounded potentials, reduced in a fixed order
-// The theta > 0 counterparts — the walk of the last tree from a point — are bh_probe_walk_kernel and bh_pot_walk_kernel (kernels_bh_pot.hip).
+//   probe_tidal_pk_kernel  <- T_ab(x) = sum_j G m_j [3 d_a d_b / s^5 - delta_ab / s^3] (nbody_tidal_at, nbody_get_tidal, nbody_tidal_time):
+//                             seven accumulators, the potential's distance term, no s^-5; SELF as the potential's
+//   tidal_fold_kernel      <- the chunks' rows added in chunk order in fp64, T_aa = S_aa - Q there, rounded once
+//   tidal_time_*_kernel    <- the largest squared Frobenius norm of the unrounded tensors and its body, reduced in a fixed order
+// The theta > 0 counterparts — the walk of the last tree from a point — are bh_probe_walk_kernel, bh_pot_walk_kernel and
+// bh_tidal_walk_kernel (kernels_bh_pot.hip).
 #include "kernels.h"
 
 #include <algorithm>
@@ -204,14 +209,167 @@ __global__ __launch_bounds__(kBlock) void energy_fast_fold_kernel(const double *
   }
 }
 
-// Points in slabs whose partial rows fit the staging area (probe_slab_points(n_total) x j_split float4; the potential's rows are a
-// quarter of the field's): run(NP, first, m, grid, j_split, j_chunk) per slab.  Which slab a point falls into, and which workgroup
+// The tidal tensor's pair term, stage by stage like pot_group_pk, whose distance term it takes as it is (Z_SOFT / Z_CLAMP, the same rsq,
+// GUARD by index): t = 1 / s, or 0 for a pair that adds nothing.  Then, all of them the compiler's own operations,
+//   g = G m_j * t;  g2 = g * t;  n_a = d_a * t (the unit vector: |n_a| <= 1);  h = (3 g2) * t = 3 G m / s^3;  h_a = h * n_a
+//   S_ab = fma(h_a, n_b, S_ab) for the six pairs a <= b;  Q = fma(g2, t, Q)
+// — one chain of fused multiply-adds per sum, in body order.  No s^-5 is formed: every value on the way is at most 3 G m / s^3 in
+// magnitude, so a pair is finite wherever that is.  T_aa = S_aa - Q is the fold's.
+struct Acc7pk {
+  f2 xx = splat2(0.f), yy = splat2(0.f), zz = splat2(0.f), xy = splat2(0.f), xz = splat2(0.f), yz = splat2(0.f), q = splat2(0.f);
+};
+template <int NP, int JB, int ZMODE, bool GUARD>
+__device__ __forceinline__ void tidal_group_pk(const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], const float4 (&pj)[JB], f2 zp2,
+                                               f2 one2, f2 three2, Acc7pk (&a)[NP], int rel) {
+  f2 dx[JB][NP], dy[JB][NP], dz[JB][NP], w[JB][NP], nf[JB][NP], u[JB][NP];
+#pragma unroll
+  for (int b = 0; b < JB; ++b)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      dx[b][p] = splat2(pj[b].x) - xi[p]; dy[b][p] = splat2(pj[b].y) - yi[p]; dz[b][p] = splat2(pj[b].z) - zi[p];
+      if (ZMODE == Z_SOFT) w[b][p] = fma2(dz[b][p], dz[b][p], zp2);
+      else                 w[b][p] = dz[b][p] * dz[b][p];
+      w[b][p] = fma2(dy[b][p], dy[b][p], w[b][p]);
+      w[b][p] = fma2(dx[b][p], dx[b][p], w[b][p]);
+    }
+  if (ZMODE == Z_CLAMP) {
+#pragma unroll
+    for (int b = 0; b < JB; ++b)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nf[b][p]) : "v"(w[b][p]), "v"(zp2), "v"(one2));
+        w[b][p] = w[b][p] + nf[b][p];
+      }
+  }
+#pragma unroll
+  for (int b = 0; b < JB; ++b)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) u[b][p] = f2{rsq_dev(w[b][p].x), rsq_dev(w[b][p].y)};
+#pragma unroll
+  for (int b = 0; b < JB; ++b)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      f2 t = u[b][p];
+      if (ZMODE == Z_CLAMP) t = t - nf[b][p];
+      if (GUARD) {
+        t.x = (rel + b == (2 * p) * kBlock) ? 0.0f : t.x;
+        t.y = (rel + b == (2 * p + 1) * kBlock) ? 0.0f : t.y;
+      }
+      const f2 g = splat2(pj[b].w) * t;
+      const f2 g2 = g * t;
+      const f2 nx = dx[b][p] * t, ny = dy[b][p] * t, nz = dz[b][p] * t;
+      const f2 h = (g2 * three2) * t;
+      const f2 hx = h * nx, hy = h * ny, hz = h * nz;
+      a[p].xx = fma2(hx, nx, a[p].xx); a[p].xy = fma2(hx, ny, a[p].xy); a[p].xz = fma2(hx, nz, a[p].xz);
+      a[p].yy = fma2(hy, ny, a[p].yy); a[p].yz = fma2(hy, nz, a[p].yz);
+      a[p].zz = fma2(hz, nz, a[p].zz);
+      a[p].q = fma2(g2, t, a[p].q);
+    }
+}
+
+// The tidal tensor: two float4 per point in a chunk's row — (Sxx, Syy, Szz, Sxy), (Sxz, Syz, Q, 0); the padding adds 0 * finite terms.
+// SELF as in probe_pot_pk_kernel.
+template <int NP, int TILE, int ZMODE, bool SELF>
+__global__ __launch_bounds__(kBlock) void probe_tidal_pk_kernel(const float4 *__restrict__ posm, const float4 *__restrict__ probe,
+                                                                float4 *__restrict__ part, int n_total, int m, int i_first, int j_chunk,
+                                                                float gscale, float zp, unsigned long long *__restrict__ clk) {
+  constexpr int JB = point_group(NP);
+  const ClockStamp stamp = clock_begin(clk);
+  Acc7pk a[NP];
+  f2 three2 = splat2(3.0f);
+  asm volatile("" : "+v"(three2));
+  const int own0 = i_first + blockIdx.x * (kBlock * 2 * NP), own1 = own0 + kBlock * 2 * NP;
+  point_tile_loop<NP, TILE>(posm, probe, n_total, m, j_chunk, gscale, zp,
+                            [&](int jt, const float4 *tile, const f2 (&xi)[NP], const f2 (&yi)[NP], const f2 (&zi)[NP], f2 zp2, f2 one2) {
+    if (SELF && jt < own1 && jt + TILE > own0) {               // (uniform over the workgroup)
+      const int rel0 = jt - (own0 + (int)threadIdx.x);
+      tile_groups<NP, TILE>(tile, [&](int jj, const float4 (&pj)[JB]) {
+        tidal_group_pk<NP, JB, ZMODE, true>(xi, yi, zi, pj, zp2, one2, three2, a, rel0 + jj);
+      });
+    } else {
+      tile_groups<NP, TILE>(tile, [&](int, const float4 (&pj)[JB]) {
+        tidal_group_pk<NP, JB, ZMODE, false>(xi, yi, zi, pj, zp2, one2, three2, a, 0);
+      });
+    }
+  });
+  point_write_out<NP>(m, [&, part](int p, int h, size_t at) {
+    part[2 * at] = make_float4(a[p].xx[h], a[p].yy[h], a[p].zz[h], a[p].xy[h]);
+    part[2 * at + 1] = make_float4(a[p].xz[h], a[p].yz[h], a[p].q[h], 0.f);
+  });
+  clock_end(clk, stamp);
+}
+
+// T[k] from the chunks' rows: the seven sums added in chunk order in fp64 (no atomics: the same bits every time), T_aa = S_aa - Q in fp64;
+// t64 gets the six doubles as they are (nbody_tidal_time), tf rounded once (the getters).  Either may be null.
+__global__ __launch_bounds__(kBlock) void tidal_fold_kernel(const float4 *__restrict__ part, int m, int j_split, double *__restrict__ t64,
+                                                            float *__restrict__ tf) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= m) return;
+  double xx = 0.0, yy = 0.0, zz = 0.0, xy = 0.0, xz = 0.0, yz = 0.0, q = 0.0;
+#pragma unroll 4
+  for (int c = 0; c < j_split; ++c) {
+    const float4 r0 = part[2 * ((size_t)c * m + k)], r1 = part[2 * ((size_t)c * m + k) + 1];
+    xx = xx + (double)r0.x; yy = yy + (double)r0.y; zz = zz + (double)r0.z; xy = xy + (double)r0.w;
+    xz = xz + (double)r1.x; yz = yz + (double)r1.y; q = q + (double)r1.z;
+  }
+  const double t[6] = {xx - q, yy - q, zz - q, xy, xz, yz};
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    if (t64 != nullptr) t64[(size_t)k * 6 + c] = t[c];
+    if (tf != nullptr) tf[(size_t)k * 6 + c] = (float)t[c];
+  }
+}
+
+// nbody_tidal_time's reduction, shaped like energy_fast_*_kernel: two launches, no atomics, the same bits and the same body every run.
+// A candidate is (n2, body); the larger n2 wins, equal ones the lower index; a value that is not finite counts as +inf.
+struct TidalMax { double v; int i; };
+__device__ __forceinline__ void tidal_max_take(TidalMax &a, double v, int i) {
+  if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
+}
+__device__ __forceinline__ TidalMax tidal_max_workgroup(TidalMax a, TidalMax (&red)[kBlock / 64]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double v = __shfl_xor(a.v, off, 64);
+    const int i = __shfl_xor(a.i, off, 64);
+    tidal_max_take(a, v, i);
+  }
+  if ((t & 63) == 0) red[t >> 6] = a;
+  __syncthreads();
+  TidalMax r = red[0];
+  for (int w = 1; w < kBlock / 64; ++w) tidal_max_take(r, red[w].v, red[w].i);
+  return r;
+}
+__global__ __launch_bounds__(kBlock) void tidal_time_parts_kernel(const double *__restrict__ t64, int n, double *__restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ TidalMax red[kBlock / 64];
+  TidalMax a{-1.0, 0x7fffffff};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const double *t = t64 + (size_t)i * 6;
+    const double xx = t[0], yy = t[1], zz = t[2], xy = t[3], xz = t[4], yz = t[5];
+    double n2 = (xx * xx + yy * yy) + zz * zz + 2.0 * ((xy * xy + xz * xz) + yz * yz);
+    if (!(n2 <= 0x1.fffffffffffffp1023)) n2 = __builtin_inf();
+    tidal_max_take(a, n2, i);
+  }
+  const TidalMax r = tidal_max_workgroup(a, red);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
+}
+__global__ __launch_bounds__(kBlock) void tidal_time_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
+  __shared__ TidalMax red[kBlock / 64];
+  TidalMax a{-1.0, 0x7fffffff};
+  for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(a, part[2 * q], (int)part[2 * q + 1]);
+  const TidalMax r = tidal_max_workgroup(a, red);
+  if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
+}
+
+// Points in slabs whose partial rows fit the staging area (probe_slab_points(n_total, width) x j_split x width float4; the potential's
+// rows are a quarter of the field's, the tidal tensor's twice the field's: width 2): run(NP, first, m, grid, j_split, j_chunk) per slab.  Which slab a point falls into, and which workgroup
 // shape its slab gets, changes nothing it is summed from.
 template <class Run>
-void for_point_slabs(int n_total, int m_all, Run run) {
+void for_point_slabs(int n_total, int m_all, int width, Run run) {
   int j_split, j_chunk;
   probe_geometry(n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(n_total);
+  const size_t slab = probe_slab_points(n_total, width);
   for (size_t first = 0; first < (size_t)m_all; first += slab) {
     const int m = (int)std::min(slab, (size_t)m_all - first);
     // few points: half the points per workgroup, twice the workgroups (the same sums either way)
@@ -233,10 +391,10 @@ void probe_geometry(int n_total, int *j_split, int *j_chunk) {
   *j_split = (n_total + chunk - 1) / chunk;
 }
 
-size_t probe_slab_points(int n_total) {
+size_t probe_slab_points(int n_total, int width) {
   int js, jc;
   probe_geometry(n_total, &js, &jc);
-  const size_t pts = kProbePartBytes / ((size_t)js * sizeof(float4));
+  const size_t pts = kProbePartBytes / ((size_t)js * sizeof(float4) * (size_t)width);
   return std::max<size_t>(1024, pts / 1024 * 1024);
 }
 
@@ -245,7 +403,7 @@ hipError_t launch_probe(const ProbeLaunch &L, hipStream_t s) {
   const int integrate = L.dt > 0.0f ? 1 : 0;
   if (integrate && (!L.vel || !L.pos_out)) return hipErrorInvalidValue;
   const bool soft = L.eps2 > 0.0;
-  for_point_slabs(L.n_total, L.m, [&](auto np, size_t first, int m, dim3 grid, int j_split, int j_chunk) {
+  for_point_slabs(L.n_total, L.m, 1, [&](auto np, size_t first, int m, dim3 grid, int j_split, int j_chunk) {
     constexpr int NP = decltype(np)::value;
     hipLaunchKernelGGL((soft ? probe_tile_pk_kernel<NP, kProbeTile, Z_SOFT> : probe_tile_pk_kernel<NP, kProbeTile, Z_CLAMP>), grid,
                        dim3(kBlock), 0, s, (const float4 *)L.posm, (const float4 *)L.probe + first, (float4 *)L.part, L.n_total, m, j_chunk,
@@ -263,7 +421,7 @@ hipError_t launch_pot(const PotLaunch &L, hipStream_t s) {
   if (self && L.m != L.n_total) return hipErrorInvalidValue;
   // eps == 0: the exact d == 0 rule whatever the context's zero_mode is (an eps floor would add G m / 1e-10 for a point on a body)
   const bool soft = L.eps2 > 0.0;
-  for_point_slabs(L.n_total, L.m, [&](auto np, size_t first, int m, dim3 grid, int j_split, int j_chunk) {
+  for_point_slabs(L.n_total, L.m, 1, [&](auto np, size_t first, int m, dim3 grid, int j_split, int j_chunk) {
     constexpr int NP = decltype(np)::value;
     const auto kernel = self ? (soft ? probe_pot_pk_kernel<NP, kProbeTile, Z_SOFT, true> : probe_pot_pk_kernel<NP, kProbeTile, Z_CLAMP, true>)
                              : (soft ? probe_pot_pk_kernel<NP, kProbeTile, Z_SOFT, false> : probe_pot_pk_kernel<NP, kProbeTile, Z_CLAMP, false>);
@@ -273,6 +431,32 @@ hipError_t launch_pot(const PotLaunch &L, hipStream_t s) {
     hipLaunchKernelGGL(pot_fold_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const float *)L.part, m, j_split,
                        L.phi64 ? (double *)L.phi64 + first : nullptr, L.phif ? (float *)L.phif + first : nullptr);
   });
+  return hipGetLastError();
+}
+
+hipError_t launch_tidal(const TidalLaunch &L, hipStream_t s) {
+  if (L.m <= 0 || L.n_total <= 0 || !L.posm || !L.part || (!L.t64 && !L.tf)) return hipErrorInvalidValue;
+  const bool self = L.probe == nullptr;
+  if (self && L.m != L.n_total) return hipErrorInvalidValue;
+  const bool soft = L.eps2 > 0.0;                              // eps == 0: the exact d == 0 rule, as the potential
+  for_point_slabs(L.n_total, L.m, 2, [&](auto np, size_t first, int m, dim3 grid, int j_split, int j_chunk) {
+    constexpr int NP = decltype(np)::value;
+    const auto kernel = self ? (soft ? probe_tidal_pk_kernel<NP, kProbeTile, Z_SOFT, true> : probe_tidal_pk_kernel<NP, kProbeTile, Z_CLAMP, true>)
+                             : (soft ? probe_tidal_pk_kernel<NP, kProbeTile, Z_SOFT, false> : probe_tidal_pk_kernel<NP, kProbeTile, Z_CLAMP, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const float4 *)L.posm, (const float4 *)(self ? L.posm : L.probe) + first,
+                       (float4 *)L.part, L.n_total, m, self ? (int)first : 0, j_chunk, (float)L.G, soft ? (float)L.eps2 : -0x1p126f,
+                       (unsigned long long *)L.clk);
+    hipLaunchKernelGGL(tidal_fold_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const float4 *)L.part, m, j_split,
+                       L.t64 ? L.t64 + 6 * first : nullptr, L.tf ? L.tf + 6 * first : nullptr);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_tidal_time(const double *t64, int n, double *partials, double *out, hipStream_t s) {
+  if (n <= 0 || !t64 || !partials || !out) return hipErrorInvalidValue;
+  const int slots = energy_fast_slots(n);
+  hipLaunchKernelGGL(tidal_time_parts_kernel, dim3(slots), dim3(kBlock), 0, s, t64, n, partials);
+  hipLaunchKernelGGL(tidal_time_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)partials, slots, out);
   return hipGetLastError();
 }
 

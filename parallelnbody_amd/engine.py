@@ -355,6 +355,34 @@ class NBodyEngine:
         self._check(self._L.nbody_energy_fast(self._h, ctypes.byref(ke), ctypes.byref(pe)))
         return ke.value, pe.value
 
+    # -- the tidal tensor --
+    def tidal_at(self, points):
+        """The bodies' tidal tensor T_ab = d a_a / d x_b at every row of `points` (nbody_tidal_at): [n,6] float32 — xx, yy, zz, xy, xz,
+        yz.  points: as for field_at.  theta > 0: the walk of the last tree built (include/nbody.h)."""
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] < 3:
+            raise ValueError("tidal_at: points must be [n, >= 3]")
+        p = p[:, :3]
+        if p.dtype != np.float32 or p.shape[0] < 2 or p.strides[1] != 4 or p.strides[0] < 12:
+            p = np.ascontiguousarray(p, np.float32)
+        out = np.empty((p.shape[0], 6), np.float32)
+        self._check(self._L.nbody_tidal_at(self._h, p.ctypes.data, max(p.strides[0], 12), p.shape[0], out.ctypes.data, 24))
+        return out
+
+    def tidal(self):
+        """Every body's tidal tensor from all other bodies at the current positions (nbody_get_tidal): [n_total,6] float32.
+        theta > 0: builds the tree of the current positions first — side effects as after compute_forces()."""
+        out = np.empty((self.n_total, 6), np.float32)
+        self._check(self._L.nbody_get_tidal(self._h, out.ctypes.data, 24))
+        return out
+
+    def tidal_time(self):
+        """(t_min, body): the smallest tidal time scale ||T_i||_F^(-1/2) over the bodies and the body that attains it
+        (nbody_tidal_time).  Side effects as tidal()."""
+        t, body = ctypes.c_double(), ctypes.c_int32()
+        self._check(self._L.nbody_tidal_time(self._h, ctypes.byref(t), ctypes.byref(body)))
+        return t.value, body.value
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
