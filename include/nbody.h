@@ -406,6 +406,59 @@ NBODY_AMD_API int nbody_tidal_at(nbody_ctx *ctx, const float *xyz, size_t stride
 NBODY_AMD_API int nbody_get_tidal(nbody_ctx *ctx, float *t, size_t stride);
 NBODY_AMD_API int nbody_tidal_time(nbody_ctx *ctx, double *t_min, int32_t *body);
 
+/*
+ * The jerk j = da/dt of the pair law beside the acceleration a (build-defined, like the potential) — the one per-body quantity that
+ * depends on the VELOCITIES.  With d = x_j - x, w = v_j - v and s^2 = |d|^2 + eps^2,
+ *     a(x) = sum_j G m_j d / s^3        j(x, v) = sum_j G m_j [ w / s^3 - 3 (d . w) d / s^5 ]
+ * with the context's G and eps.  Positions, masses and velocities are those nbody_get_particles / nbody_get_state_soa would deliver at
+ * that moment — the live buffers, whichever the stepping path has left current, bound buffers included (as nbody_get_moments reads them).
+ * After nbody_step the stored velocity is the STAGGERED one (v_(n+1/2) beside x_(n+1), OctreeSearch.cpp:29-30): a host that wants the
+ * synchronised jerk synchronises the velocities itself.
+ *
+ * At EVERY theta both sums are the pair sum over all n_total bodies: the tree holds no node velocities (nbody_energy sets the precedent:
+ * all pairs at theta > 0 too).  So these calls need no tree, build none, work whether or not a last tree exists, and change nothing a
+ * getter shows at any theta — state, stored accelerations, tracers, steps done, root centre, last tree.  The acceleration they return
+ * is the pair sum's: at theta > 0 that is NOT the monopole walk's that nbody_compute_forces stores.
+ *
+ * Contexts: one device, owning all bodies — slice contexts (i_count < n_total) and nbody_create_multi contexts report
+ * NBODY_ERR_UNSUPPORTED from all four calls.  nbody_get_jerk, nbody_get_jerk_f64 and nbody_jerk_time answer on all three precisions;
+ * nbody_jerk_at on those whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN) — an fp64 context reports NBODY_ERR_UNSUPPORTED
+ * there, as its points would have to be doubles.  No particles set: NBODY_ERR_STATE.  All four synchronise; their device time counts as
+ * one pass under NBODY_KERNEL_FORCES (the kernels do not enter nbody_kernel_clock's average).
+ *
+ * The d == 0 rule is the potential's: with eps == 0 a pair at distance exactly 0 is dropped from BOTH sums, whatever zero_mode the context
+ * has (no NBODY_ZERO_FLOOR eps floor); with eps > 0 a point exactly on a body feels G m w / eps^3 from it in the jerk and nothing in
+ * the acceleration.
+ *
+ * Arithmetic, fp32 state (a Kahan context runs the same kernel on its fp32 state: bit-equal to a plain fp32 context holding that state):
+ *   the potential's distance term (a 1-ulp reciprocal square root t = 1 / s, or 0 for a pair that adds nothing), then in fp32
+ *       g = G m t;  g2 = g t;  q = g2 t;  n_a = d_a t (|n| <= 1);  k = n . w (a product and two fused multiply-adds in z, y, x order)
+ *       u_a = fma(-3 k, n_a, w_a);  A_a = fma(q, d_a, A_a);  J_a = fma(q, u_a, J_a)
+ *   — no s^-5 is formed: a pair is finite wherever 4 G m |w| / s^3 is.  A chunk's six sums are each one chain of fused multiply-adds in
+ *   body order; the chunks — those of nbody_field_at, a function of n_total alone — are added in chunk order in fp64, and each component
+ *   is rounded once.  A point's bits depend neither on the other points of the call, nor on n, nor on the strides, nor on the device.
+ * Arithmetic, fp64 state: t = 1 / s as the fp64 force kernels form it (0 where s^2 == 0 and for j == i), then q = G m t^3,
+ *   k = (d . w) t^2, A += q d, J += q (w - 3 k d): chains of fused multiply-adds in body order per chunk, the chunks added in chunk order.
+ *
+ * nbody_jerk_at: a and j at n massless points — xyz and vel: 3 floats each, `stride` / `vel_stride` bytes apart (>= 12); vel == NULL
+ *   means at rest and gives the bits an array of zeros gives.  acc and jerk: 3 floats each, >= 12 bytes apart; either may be NULL, not
+ *   both.  n == 0 is a no-op; NULL points, n < 0, both outputs NULL or a stride too small are NBODY_ERR_INVALID.
+ * nbody_get_jerk / nbody_get_jerk_f64: every body's a and j from all OTHER bodies — the body itself left out BY INDEX; other bodies on
+ *   the same point are skipped when eps == 0 and felt when eps > 0.  n_total x 3 floats (strides >= 12) or doubles (strides >= 24);
+ *   either output may be NULL, not both (NBODY_ERR_INVALID).  _f64 delivers the UNROUNDED fp64 results — the fp64 fold on fp32-state
+ *   contexts, the fp64 sums on fp64 contexts —, the float form the same rounded once per component.
+ * nbody_jerk_time: the step-size criterion |a| / |j|, minimised over the bodies.  Per body k_i = |j_i|^2 / |a_i|^2 from those unrounded
+ *   fp64 vectors, each squared norm (x x + y y) + z z in fp64 with contraction off; 0 / 0 counts as 0, x / 0 with x > 0 as +inf, and a
+ *   value that is not finite as +inf.  The largest k and the lowest body index that attains it come from nbody_tidal_time's fixed-order
+ *   reduction: the same bits and the same body every run.  *t_min = 1 / sqrt(max k); +inf when the maximum is 0 (a single body), 0 when
+ *   it is not finite.  Either output may be NULL, not both (NBODY_ERR_INVALID).
+ */
+NBODY_AMD_API int nbody_jerk_at(nbody_ctx *ctx, const float *xyz, size_t stride, const float *vel, size_t vel_stride, int32_t n,
+                                float *acc, size_t acc_stride, float *jerk, size_t jerk_stride);
+NBODY_AMD_API int nbody_get_jerk(nbody_ctx *ctx, float *acc, size_t acc_stride, float *jerk, size_t jerk_stride);
+NBODY_AMD_API int nbody_get_jerk_f64(nbody_ctx *ctx, double *acc, size_t acc_stride, double *jerk, size_t jerk_stride);
+NBODY_AMD_API int nbody_jerk_time(nbody_ctx *ctx, double *t_min, int32_t *body);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -153,6 +153,10 @@ def lib():
     sig("nbody_tidal_at", c_int, vp, vp, sz, c_i32, vp, sz)
     sig("nbody_get_tidal", c_int, vp, vp, sz)
     sig("nbody_tidal_time", c_int, vp, dp, ctypes.POINTER(c_i32))
+    sig("nbody_jerk_at", c_int, vp, vp, sz, vp, sz, c_i32, vp, sz, vp, sz)
+    sig("nbody_get_jerk", c_int, vp, vp, sz, vp, sz)
+    sig("nbody_get_jerk_f64", c_int, vp, vp, sz, vp, sz)
+    sig("nbody_jerk_time", c_int, vp, dp, ctypes.POINTER(c_i32))
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

@@ -613,7 +613,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1441,34 +1441,54 @@ int queue_body_tidal(nbody_ctx *c, const char *who, double *t64, float *tf) {
 // through the pinned staging, launch(d_pts, d_out) timed as a pass under NBODY_KERNEL_FORCES, the values back (d_out: a float4 per
 // point for width 3, `width` floats otherwise).  floor: the query follows the context's NBODY_ZERO_FLOOR.  part_width: the float4 of a
 // point in a chunk's partial row (theta == 0).
+// `pair` (the jerk): a second input array — 3 floats per point, staged as float4 behind the points (d_pts + 4 n); NULL: zeros — and a
+// second output of `width` floats behind the first in the point's device record (2 * width floats, packed); either output may be NULL,
+// not both.  Such a query is a pair sum at every theta (no tree is asked for) and is served where jerk_supported says.
+struct PointPair { const float *in; size_t in_stride; float *out; size_t out_stride; };
+int jerk_supported(nbody_ctx *c, const char *who, bool points);
 template <class Launch>
 int query_points(nbody_ctx *c, const char *who, const char *what, const char *bad_args, bool floor, const float *xyz, size_t stride,
-                 int32_t n, float *out, size_t out_stride, int width, int part_width, Launch launch) {
+                 int32_t n, float *out, size_t out_stride, int width, int part_width, Launch launch, const PointPair *pair = nullptr) {
   if (c && c->multi) return multi_unsupported(c, who);
   int rc = check_ready(c);
   if (rc) return rc;
-  if ((rc = probes_supported(c, who))) return rc;
-  if (n < 0 || !xyz || !out || stride < 12 || out_stride < 4 * (size_t)width) return fail(c, NBODY_ERR_INVALID, "%s: %s", who, bad_args);
+  if ((rc = pair ? jerk_supported(c, who, true) : probes_supported(c, who))) return rc;
+  const size_t out_min = 4 * (size_t)width;
+  bool bad = n < 0 || !xyz || stride < 12;
+  if (pair) bad = bad || (pair->in && pair->in_stride < 12) || (!out && !pair->out) || (out && out_stride < out_min) ||
+                  (pair->out && pair->out_stride < out_min);
+  else      bad = bad || !out || out_stride < out_min;
+  if (bad) return fail(c, NBODY_ERR_INVALID, "%s: %s", who, bad_args);
   if (n == 0) return NBODY_OK;
-  if (c->theta > 0.0f) {
+  if (c->theta > 0.0f && !pair) {
     if ((rc = probe_tree_ready(c, who, what))) return rc;
   } else {
     if (floor && (rc = ensure_floor(c))) return rc;
     if ((rc = ensure_probe_part(c, n, part_width))) return rc;
   }
-  const size_t out_floats = width == 3 ? 4 : (size_t)width;
-  if ((rc = ensure_probe_staging(c, n, out_floats))) return rc;
-  float *h_pts = (float *)c->probe_host, *h_out = h_pts + 4 * (size_t)n;
-  float *d_pts = (float *)c->probe_dev, *d_out = d_pts + 4 * (size_t)n;
+  const size_t out_floats = pair ? 2 * (size_t)width : (width == 3 ? 4 : (size_t)width);
+  const size_t in_floats = pair ? 8 : 4;
+  if ((rc = ensure_probe_staging(c, n, in_floats - 4 + out_floats))) return rc;
+  float *h_pts = (float *)c->probe_host, *h_out = h_pts + in_floats * (size_t)n;
+  float *d_pts = (float *)c->probe_dev, *d_out = d_pts + in_floats * (size_t)n;
   for (size_t k = 0; k < (size_t)n; ++k) {
     memcpy(h_pts + 4 * k, (const char *)xyz + k * stride, 12);
     h_pts[4 * k + 3] = 0.0f;
   }
-  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  if (pair) {
+    float *h_in2 = h_pts + 4 * (size_t)n;
+    for (size_t k = 0; k < (size_t)n; ++k) {
+      if (pair->in) memcpy(h_in2 + 4 * k, (const char *)pair->in + k * pair->in_stride, 12);
+      else          h_in2[4 * k] = h_in2[4 * k + 1] = h_in2[4 * k + 2] = 0.0f;
+      h_in2[4 * k + 3] = 0.0f;
+    }
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_pts, h_pts, (size_t)n * in_floats * 4, hipMemcpyHostToDevice, c->stream));
   if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return launch(d_pts, d_out); }))) return rc;
   HIP_TRY(c, hipMemcpyAsync(h_out, d_out, (size_t)n * out_floats * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  scatter_records(out, out_stride, h_out, 4 * (size_t)width, (size_t)n, 4 * out_floats);
+  if (out) scatter_records(out, out_stride, h_out, out_min, (size_t)n, 4 * out_floats);
+  if (pair && pair->out) scatter_records(pair->out, pair->out_stride, h_out + width, out_min, (size_t)n, 4 * out_floats);
   return NBODY_OK;
 }
 }  // namespace
@@ -1561,6 +1581,108 @@ int nbody_tidal_time(nbody_ctx *c, double *t_min, int32_t *body) {
   if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
   // t = ||T||_F^(-1/2) = n2^(-1/4)
   if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);
+  if (body) *body = (int32_t)at;
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- the jerk: a pair sum over all bodies at every theta, on every precision (kernels_jerk.hip) ----
+namespace {
+// where it exists: contexts on one device that own all bodies; at caller-given points (float arrays) those whose state is fp32 as well
+int jerk_supported(nbody_ctx *c, const char *who, bool points) {
+  if (c->p.i_count != c->p.n_total)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
+  if (points && c->p.precision == NBODY_PREC_F64)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on an fp64 context (its points would have to be doubles); nbody_get_jerk_f64 answers at the bodies", who);
+  return NBODY_OK;
+}
+
+// (a, j) of the bodies' LIVE buffers — c->posm is the current one of the one-launch step's two, c->vel every path's velocities, as
+// nbody_get_moments reads them — at m points, queued (the partial rows are the caller's to provide).  probe == nullptr: at the bodies themselves.
+// eps == 0: the potential's d == 0 rule, whatever the zero_mode.  No tree is read or built.
+int launch_jerk_on(nbody_ctx *c, const void *probe, const void *pvel, int m, double *aj64, float *ajf) {
+  nbody::JerkLaunch L;
+  L.posm = c->posm; L.vel = c->vel; L.probe = probe; L.pvel = pvel; L.part = c->probe_part; L.aj64 = aj64; L.ajf = ajf;
+  L.n_total = c->p.n_total; L.m = m; L.precision = c->p.precision; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+  HIP_TRY(c, nbody::launch_jerk(L, c->stream));
+  return NBODY_OK;
+}
+
+// The bodies' own (a, j), as one pass under NBODY_KERNEL_FORCES; the partial rows in the staging area the point queries use: two
+// float4 per body and chunk, six doubles on fp64 state.
+int queue_body_jerk(nbody_ctx *c, double *aj64, float *ajf) {
+  const int n = c->p.n_total;
+  if (int rc = ensure_probe_part(c, n, c->p.precision == NBODY_PREC_F64 ? 3 : 2)) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return launch_jerk_on(c, nullptr, nullptr, n, aj64, ajf); });
+}
+
+// the bodies' unrounded (a, j), [n_total][6] double, and the reduction's workgroup pairs behind them: allocated at first use
+int ensure_jerk64(nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  if (!c->jerk64) HIP_TRY(c, hipMalloc(&c->jerk64, (6 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
+  return NBODY_OK;
+}
+
+// nbody_get_jerk / nbody_get_jerk_f64: T = float / double
+template <typename T>
+int get_jerk(nbody_ctx *c, const char *who, T *acc, size_t acc_stride, T *jerk, size_t jerk_stride) {
+  if (c && c->multi) return multi_unsupported(c, who);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = jerk_supported(c, who, false))) return rc;
+  if ((!acc && !jerk) || (acc && acc_stride < 3 * sizeof(T)) || (jerk && jerk_stride < 3 * sizeof(T)))
+    return fail(c, NBODY_ERR_INVALID, "%s: both outputs are null, or a stride < %d", who, (int)(3 * sizeof(T)));
+  const size_t n = (size_t)c->p.n_total, rec = 6 * sizeof(T);
+  if ((rc = ensure_stage(c, n * rec))) return rc;
+  if constexpr (sizeof(T) == 8) {
+    if ((rc = ensure_jerk64(c))) return rc;
+    if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->jerk64, n * rec, hipMemcpyDeviceToHost, c->stream));
+  } else {
+    if ((rc = queue_body_jerk(c, nullptr, (float *)c->d_stage))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * rec, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (acc) scatter_records(acc, acc_stride, c->h_stage, rec / 2, n, rec);
+  if (jerk) scatter_records(jerk, jerk_stride, (const char *)c->h_stage + rec / 2, rec / 2, n, rec);
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_jerk_at(nbody_ctx *c, const float *xyz, size_t stride, const float *vel, size_t vel_stride, int32_t n, float *acc,
+                  size_t acc_stride, float *jerk, size_t jerk_stride) {
+  const PointPair pair{vel, vel_stride, jerk, jerk_stride};
+  return query_points(c, "nbody_jerk_at", "jerk", "null points, n < 0, both outputs null, or a stride < 12", false, xyz, stride, n, acc,
+                      acc_stride, 3, 2, [&](float *d_pts, float *d_aj) -> int {
+    return launch_jerk_on(c, d_pts, d_pts + 4 * (size_t)n, n, nullptr, d_aj);
+  }, &pair);
+}
+
+int nbody_get_jerk(nbody_ctx *c, float *acc, size_t acc_stride, float *jerk, size_t jerk_stride) {
+  return get_jerk<float>(c, "nbody_get_jerk", acc, acc_stride, jerk, jerk_stride);
+}
+
+int nbody_get_jerk_f64(nbody_ctx *c, double *acc, size_t acc_stride, double *jerk, size_t jerk_stride) {
+  return get_jerk<double>(c, "nbody_get_jerk_f64", acc, acc_stride, jerk, jerk_stride);
+}
+
+int nbody_jerk_time(nbody_ctx *c, double *t_min, int32_t *body) {
+  if (c && c->multi) return multi_unsupported(c, "nbody_jerk_time");
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = jerk_supported(c, "nbody_jerk_time", false))) return rc;
+  if (!t_min && !body) return fail(c, NBODY_ERR_INVALID, "nbody_jerk_time: both outputs are null");
+  const int n = c->p.n_total;
+  if ((rc = ensure_jerk64(c))) return rc;
+  double *aj64 = (double *)c->jerk64, *partials = aj64 + 6 * (size_t)n;
+  if ((rc = queue_body_jerk(c, aj64, nullptr))) return rc;
+  HIP_TRY(c, nbody::launch_jerk_time(aj64, n, partials, (double *)c->scratch, c->stream));
+  double k = 0.0, at = 0.0;
+  if ((rc = read_energy(c, &k, &at))) return rc;               // (the scratch's two doubles: the largest |j|^2 / |a|^2, its body)
+  if (t_min) *t_min = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
   if (body) *body = (int32_t)at;
   return NBODY_OK;
 }

@@ -95,6 +95,7 @@ struct nbody_ctx {
   void *probe_dev = nullptr, *probe_host = nullptr;   // the point queries: probe_cap units of 32 bytes — the points as float4, behind them their results — on the device, and its pinned mirror
   size_t probe_cap = 0;
   void *tidal64 = nullptr;     // nbody_tidal_time: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
+  void *jerk64 = nullptr;      // nbody_get_jerk_f64 / nbody_jerk_time: [n_total][6] double, the bodies' unrounded (a, j), then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;

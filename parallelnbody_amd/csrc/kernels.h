@@ -89,7 +89,7 @@ struct ProbeLaunch {
   void *clk = nullptr;          // two device uint64 the workgroups add their clock intervals to (pk_common.h)
 };
 void probe_geometry(int n_total, int *j_split, int *j_chunk);
-// width: the float4 a point has in a chunk's partial row at most (1: the field, the potential; 2: the tidal tensor)
+// width: the float4 a point has in a chunk's partial row at most (1: the field, the potential; 2: the tidal tensor, the jerk; 3: the fp64 jerk)
 size_t probe_slab_points(int n_total, int width = 1);         // points whose partial rows fit kProbePartBytes (a multiple of 1024)
 inline size_t probe_part_elems(int n_total, int m, int width = 1) {   // float4 elements `part` must hold for a launch of m points
   int js, jc;
@@ -141,6 +141,32 @@ hipError_t launch_tidal(const TidalLaunch &L, hipStream_t s);
 // as +inf), out[1] = the lowest index that attains it, as a double: per-workgroup pairs into `partials` (2 * energy_fast_slots(n) doubles),
 // then one workgroup folds them — a fixed order, no atomics.
 hipError_t launch_tidal_time(const double *t64, int n, double *partials, double *out, hipStream_t s);
+
+// The jerk j = da/dt beside the acceleration, a pair sum over all n_total bodies at every theta — kernels_jerk.hip: with d = x_j - x,
+// w = v_j - v, s^2 = |d|^2 + eps2:  a = sum_j G m_j d / s^3,  j = sum_j G m_j [w / s^3 - 3 (d . w) d / s^5].  With eps2 == 0 a pair at
+// distance 0 adds nothing to either sum.  probe == nullptr: the points are the bodies themselves (m == n_total, their velocities `vel`)
+// and every body leaves itself out by index.
+//   fp32 state (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): six fp32 sums per point and chunk of probe_geometry, each one fused chain in body
+//     order on the potential's distance term, no s^-5 anywhere; a partial row is two float4 per point (probe_slab_points(n_total, 2)); the
+//     chunks' rows are added in chunk order in fp64.
+//   fp64 state (NBODY_PREC_F64; the bodies only): the same sums in fp64, a partial row six doubles per body (probe_slab_points(n_total, 3)).
+// aj64 gets six doubles per point (ax, ay, az, jx, jy, jz), ajf the same rounded once; either may be null.
+struct JerkLaunch {
+  const void *posm = nullptr;   // [n_total] float4 / double4: x, y, z, m
+  const void *vel = nullptr;    // [n_total] float4 / double4: vx, vy, vz, unused
+  const void *probe = nullptr;  // [m] float4: x, y, z, unused; nullptr: posm
+  const void *pvel = nullptr;   // [m] float4: the points' velocities (probe != nullptr)
+  void *part = nullptr;         // [probe_part_elems(n_total, m, 2)] float4; fp64 state: [probe_part_elems(n_total, m, 3)]
+  double *aj64 = nullptr;       // [m][6]
+  float *ajf = nullptr;         // [m][6]
+  int n_total = 0, m = 0;
+  int precision = 0;            // NBODY_PREC_*
+  double G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_jerk(const JerkLaunch &L, hipStream_t s);
+// out[0] = max over the n bodies of k = |j|^2 / |a|^2 from aj64, each squared norm (x x + y y) + z z (0 / 0 counts as 0, x / 0 and every
+// value that is not finite as +inf), out[1] = the lowest index that attains it, as a double: launch_tidal_time's reduction.
+hipError_t launch_jerk_time(const double *aj64, int n, double *partials, double *out, hipStream_t s);
 
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.

@@ -17,7 +17,6 @@
 #include "kernels.h"
 
 #include <algorithm>
-#include <type_traits>
 
 #include "../../include/nbody.h"
 #include "point_tile.h"
@@ -321,25 +320,7 @@ __global__ __launch_bounds__(kBlock) void tidal_fold_kernel(const float4 *__rest
 }
 
 // nbody_tidal_time's reduction, shaped like energy_fast_*_kernel: two launches, no atomics, the same bits and the same body every run.
-// A candidate is (n2, body); the larger n2 wins, equal ones the lower index; a value that is not finite counts as +inf.
-struct TidalMax { double v; int i; };
-__device__ __forceinline__ void tidal_max_take(TidalMax &a, double v, int i) {
-  if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
-}
-__device__ __forceinline__ TidalMax tidal_max_workgroup(TidalMax a, TidalMax (&red)[kBlock / 64]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double v = __shfl_xor(a.v, off, 64);
-    const int i = __shfl_xor(a.i, off, 64);
-    tidal_max_take(a, v, i);
-  }
-  if ((t & 63) == 0) red[t >> 6] = a;
-  __syncthreads();
-  TidalMax r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) tidal_max_take(r, red[w].v, red[w].i);
-  return r;
-}
+// A candidate is (n2, body) (point_tile.h: tidal_max_*); a value that is not finite counts as +inf.
 __global__ __launch_bounds__(kBlock) void tidal_time_parts_kernel(const double *__restrict__ t64, int n, double *__restrict__ part) {
 #pragma clang fp contract(off)
   __shared__ TidalMax red[kBlock / 64];
@@ -360,23 +341,6 @@ __global__ __launch_bounds__(kBlock) void tidal_time_fold_kernel(const double *_
   for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(a, part[2 * q], (int)part[2 * q + 1]);
   const TidalMax r = tidal_max_workgroup(a, red);
   if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
-}
-
-// Points in slabs whose partial rows fit the staging area (probe_slab_points(n_total, width) x j_split x width float4; the potential's
-// rows are a quarter of the field's, the tidal tensor's twice the field's: width 2): run(NP, first, m, grid, j_split, j_chunk) per slab.  Which slab a point falls into, and which workgroup
-// shape its slab gets, changes nothing it is summed from.
-template <class Run>
-void for_point_slabs(int n_total, int m_all, int width, Run run) {
-  int j_split, j_chunk;
-  probe_geometry(n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(n_total, width);
-  for (size_t first = 0; first < (size_t)m_all; first += slab) {
-    const int m = (int)std::min(slab, (size_t)m_all - first);
-    // few points: half the points per workgroup, twice the workgroups (the same sums either way)
-    const long long wgs2 = (long long)((m + 4 * kBlock - 1) / (4 * kBlock)) * j_split;
-    if (wgs2 < 1024) run(std::integral_constant<int, 1>{}, first, m, dim3((m + 2 * kBlock - 1) / (2 * kBlock), j_split), j_split, j_chunk);
-    else             run(std::integral_constant<int, 2>{}, first, m, dim3((m + 4 * kBlock - 1) / (4 * kBlock), j_split), j_split, j_chunk);
-  }
 }
 
 }  // namespace

@@ -383,6 +383,54 @@ class NBodyEngine:
         self._check(self._L.nbody_tidal_time(self._h, ctypes.byref(t), ctypes.byref(body)))
         return t.value, body.value
 
+    # -- the jerk --
+    def jerk_at(self, points, vel=None):
+        """(acc, jerk): the bodies' acceleration and its time derivative j = da/dt at every row of `points` moving with `vel`
+        (nbody_jerk_at): two [n,3] float32 arrays.  points, vel: as for field_at; vel None = at rest (the bits an array of zeros gives).
+        The pair sum over all bodies at EVERY theta — no tree is read or built, nothing a getter shows changes, and at theta > 0 `acc` is
+        not the monopole walk's.  The bodies' velocities are the stored ones: after step() the staggered v_(n+1/2).  eps == 0: a point
+        exactly on a body drops that pair from both sums; eps > 0: it feels G m w / eps^3 in the jerk, nothing in acc.  fp32-state
+        contexts (f32, f32_kahan) on one device owning all bodies; fp64, slice and multi-device contexts: ERR_UNSUPPORTED."""
+        def rows(a, what):
+            a = np.asarray(a)
+            if a.ndim != 2 or a.shape[1] < 3:
+                raise ValueError(f"jerk_at: {what} must be [n, >= 3]")
+            a = a[:, :3]
+            if a.dtype != np.float32 or a.shape[0] < 2 or a.strides[1] != 4 or a.strides[0] < 12:
+                a = np.ascontiguousarray(a, np.float32)
+            return a
+        p = rows(points, "points")
+        v = None if vel is None else rows(vel, "vel")
+        if v is not None and v.shape != p.shape:
+            raise ValueError("jerk_at: points and vel differ in shape")
+        acc = np.empty((p.shape[0], 3), np.float32)
+        jerk = np.empty((p.shape[0], 3), np.float32)
+        self._check(self._L.nbody_jerk_at(self._h, p.ctypes.data, max(p.strides[0], 12), None if v is None else v.ctypes.data,
+                                          12 if v is None else max(v.strides[0], 12), p.shape[0], acc.ctypes.data, 12, jerk.ctypes.data, 12))
+        return acc, jerk
+
+    def jerk(self, dtype=np.float32):
+        """(acc, jerk): every body's acceleration and jerk from all OTHER bodies (itself left out by index; bodies on the same point are
+        skipped when eps == 0, felt when eps > 0) at the current positions and the stored velocities — after step() the staggered
+        v_(n+1/2) — as two [n_total,3] arrays (nbody_get_jerk / nbody_get_jerk_f64).  dtype np.float64: the unrounded fp64 results (the
+        fp64 fold on fp32-state contexts, the fp64 sums on fp64 contexts); np.float32: those rounded once.  The pair sum at EVERY theta,
+        as jerk_at; all three precisions on one device owning all bodies; slice and multi-device contexts: ERR_UNSUPPORTED."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("jerk: dtype must be float32 or float64")
+        acc = np.empty((self.n_total, 3), dt)
+        jerk = np.empty((self.n_total, 3), dt)
+        f = self._L.nbody_get_jerk if dt.itemsize == 4 else self._L.nbody_get_jerk_f64
+        self._check(f(self._h, acc.ctypes.data, 3 * dt.itemsize, jerk.ctypes.data, 3 * dt.itemsize))
+        return acc, jerk
+
+    def jerk_time(self):
+        """(t_min, body): the smallest |a_i| / |j_i| over the bodies, from the unrounded vectors of jerk(np.float64), and the lowest
+        body index that attains it (nbody_jerk_time); +inf for a single body.  Contexts and side effects (none) as jerk()."""
+        t, body = ctypes.c_double(), ctypes.c_int32()
+        self._check(self._L.nbody_jerk_time(self._h, ctypes.byref(t), ctypes.byref(body)))
+        return t.value, body.value
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
