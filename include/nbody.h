@@ -459,6 +459,66 @@ NBODY_AMD_API int nbody_get_jerk(nbody_ctx *ctx, float *acc, size_t acc_stride, 
 NBODY_AMD_API int nbody_get_jerk_f64(nbody_ctx *ctx, double *acc, size_t acc_stride, double *jerk, size_t jerk_stride);
 NBODY_AMD_API int nbody_jerk_time(nbody_ctx *ctx, double *t_min, int32_t *body);
 
+/*
+ * Fourth-order Hermite stepping (build-defined: the reference has one integrator, the kick-drift of nbody_step, first order in the
+ * position) — Makino & Aarseth's shared-step predict-evaluate-correct scheme P(EC) on the fp64 jerk pass of nbody_get_jerk_f64.  On the
+ * two-body orbit of DESIGN 4.11 one period in 256 steps ends 2.9e-7 of the separation away from its start where nbody_step ends 2.0e-3
+ * away, and halving dt divides the error by 16.
+ *
+ * Contexts: NBODY_PREC_F64, one device, owning all bodies (such contexts are at theta == 0).  NBODY_PREC_F32 and NBODY_PREC_F32_KAHAN
+ * contexts, slice contexts (i_count < n_total) and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED from all five calls, with a
+ * message that says why.  No particles set, or a nbody_step_begin whose nbody_step_end is pending: NBODY_ERR_STATE.
+ *
+ * The stored (x, v) are taken as SYNCHRONISED: v is the velocity at the positions' time.  nbody_step leaves the velocity staggered
+ * (v_(n+1/2) beside x_(n+1)); a host that mixes the two integrators on one context must know what it is doing.  G, eps and the d == 0
+ * rule are the jerk's.
+ *
+ * One step of length dt, per component, every bracket ONE correctly rounded fp64 operation in the order written (the kernels are
+ * compiled with contraction off; plain C or numpy reproduces a step in every bit from nbody_get_jerk_f64's vectors) — the constants
+ * c2 = (dt dt) 0.5, c3 = ((dt dt) dt) / 6, ch = dt 0.5, c12 = (dt dt) / 12, d2 = dt dt, d3 = (dt dt) dt are the host's doubles:
+ *   predict    xp = ((x + dt v) + c2 a0) + c3 j0;   vp = (v + dt a0) + c2 j0            (xp carries the mass, vp.w = 0)
+ *   evaluate   (a1, j1) = what nbody_get_jerk_f64 returns on a context holding (xp, vp): the same kernel, fold and geometry
+ *   correct    v1 = v + (ch (a0 + a1) + c12 (j0 - j1));   x1 = x + (ch (v + v1) + c12 (a0 - a1));   da = a0 - a1
+ *              a2_0 = ((-6 da) - dt ((4 j0) + (2 j1))) / d2;   a3 = ((12 da) + (6 dt) (j0 + j1)) / d3;   a2_1 = a2_0 + dt a3
+ *   store      x := x1, v := v1 (masses and the velocities' fourth component stay), NBODY_BUF_ACC := (a1, 0)
+ *   cache      (a0, j0) := (a1, j1), a2 := a2_1, a3 := a3 — the derivatives at the new time
+ *
+ * The cache — a0, j0, a2, a3 and whether they belong to the stored state — lives on the device, is allocated at first use and is NOT part
+ * of a checkpoint.  While it is valid a step costs ONE jerk pass (one pass under NBODY_KERNEL_FORCES; predictor and corrector together
+ * count as one pass under NBODY_KERNEL_UPDATE); the first step after an invalidation first evaluates (a0, j0) at the stored (x, v): one
+ * more pass.  These calls invalidate it: every upload (nbody_set_particles, nbody_push_particles, nbody_set_state_soa[_f64],
+ * nbody_load_checkpoint), nbody_step / nbody_tick / nbody_step_end with dt > 0, nbody_bind_device_state, nbody_device_ptr and
+ * nbody_hermite_restart.  After a bind or a handed-out pointer the context cannot know who writes the state: from then on every
+ * nbody_hermite_step / _timescale / _advance CALL evaluates anew at entry (once per call, not once per step).  nbody_compute_forces
+ * leaves the cache alone.  Checkpoints stay NBDYCKP2 byte for byte: a resumed run restarts from the corrected state, and the same
+ * trajectory on the context that wrote the file is "nbody_save_checkpoint, nbody_hermite_restart, go on" — equal in every byte.
+ *
+ * nbody_hermite_step: nsteps steps of length dt; steps_done grows by nsteps.  Asynchronous like nbody_step.  dt <= 0 is a no-op that
+ *   returns NBODY_OK, like nbody_step's; a dt that is not finite or nsteps < 0 is NBODY_ERR_INVALID.
+ * nbody_hermite_timescale: the shared step's time scale from the cache, in one pass over it and nbody_jerk_time's fixed-order reduction
+ *   (no atomics: the same bits and the same body every run).  Norms are sqrt((x x + y y) + z z): A = |a0|, J = |j0|, S = |a2|, C = |a3|.
+ *   With derivatives (a step has been taken since the last invalidation) *kind = 1, Aarseth's criterion: k_i = (J C + S S) / (A S + J J),
+ *   0 / 0 counting as 0, x / 0 as +inf and a value that is not finite as +inf; *t_min = 1 / sqrt(max k), *body the lowest index that
+ *   attains the maximum.  Without, *kind = 0: nbody_jerk_time's own value and body from the cached (a0, j0), which the call evaluates
+ *   first if they are invalid.  In both kinds a maximum of 0 gives +inf and one that is not finite 0.  Synchronises; changes nothing a
+ *   getter shows.  Any output may be NULL, not all three (NBODY_ERR_INVALID).
+ * nbody_hermite_advance: shared adaptive steps until t_span has passed or max_steps have been taken.  Per step, with (t, kind) that
+ *   step's nbody_hermite_timescale: dt = min(dt_max, kind == 1 ? sqrt(eta) t : eta_start t); a dt >= t_span - t_acc becomes
+ *   t_span - t_acc, and *t_done then t_span exactly.  The host reads 16 bytes per step.  *t_done = the time covered, *steps = the steps
+ *   taken (either may be NULL).  eta, eta_start and dt_max must be > 0 (dt_max may be +inf), t_span >= 0 and finite, max_steps >= 0:
+ *   anything else is NBODY_ERR_INVALID.  A chosen dt that is 0 or not finite stops the call with NBODY_ERR_STATE and a message that names
+ *   the body; the state, *t_done and *steps are those of the last good step.
+ * nbody_hermite_get: the cache, 12 doubles per body — a0, j0, a2, a3 —, `stride` bytes apart (>= 96, else NBODY_ERR_INVALID).
+ *   NBODY_ERR_STATE while (a0, j0) are invalid; a2 and a3 read as zeros while there are no derivatives.  Synchronises.
+ * nbody_hermite_restart: forgets the cache; the next call starts from the stored (x, v) alone, as a context that loaded them would.
+ */
+NBODY_AMD_API int nbody_hermite_step(nbody_ctx *ctx, double dt, int32_t nsteps);
+NBODY_AMD_API int nbody_hermite_timescale(nbody_ctx *ctx, double *t_min, int32_t *body, int32_t *kind);
+NBODY_AMD_API int nbody_hermite_advance(nbody_ctx *ctx, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps,
+                                        double *t_done, int64_t *steps);
+NBODY_AMD_API int nbody_hermite_get(nbody_ctx *ctx, double *d12, size_t stride);
+NBODY_AMD_API int nbody_hermite_restart(nbody_ctx *ctx);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

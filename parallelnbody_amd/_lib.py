@@ -157,6 +157,11 @@ def lib():
     sig("nbody_get_jerk", c_int, vp, vp, sz, vp, sz)
     sig("nbody_get_jerk_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_jerk_time", c_int, vp, dp, ctypes.POINTER(c_i32))
+    sig("nbody_hermite_step", c_int, vp, c_d, c_i32)
+    sig("nbody_hermite_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
+    sig("nbody_hermite_advance", c_int, vp, c_d, c_d, c_d, c_d, c_i64, dp, ctypes.POINTER(c_i64))
+    sig("nbody_hermite_get", c_int, vp, vp, sz)
+    sig("nbody_hermite_restart", c_int, vp)
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

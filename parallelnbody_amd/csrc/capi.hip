@@ -273,6 +273,7 @@ int upload_soa(nbody_ctx *c, const T *posm4, const T *vel4, bool keep_history = 
   c->have_state = true;
   c->floor_eps2 = -1.0;
   c->sym_posg_valid = false;
+  nbody::hermite_invalidate(c);
   if (c->bh) nbody::bh_positions_changed(c->bh);                   // the next Barnes-Hut frame looks at the positions for its Size
   if (keep_history) return NBODY_OK;
   c->steps_done = 0;
@@ -613,7 +614,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -640,6 +641,8 @@ int nbody_device_ptr(nbody_ctx *c, int32_t which, void **ptr, size_t *bytes) {
   if (c && c->multi) return multi_unsupported(c, "nbody_device_ptr");
   if (!c || !ptr) return NBODY_ERR_INVALID;
   if (int rc = use_device(c)) return rc;
+  c->hm_external = true;                                          // whichever buffer: the caller may write the state from now on
+  nbody::hermite_invalidate(c);
   switch (which) {
     case NBODY_BUF_POSM:
       *ptr = c->posm; if (bytes) *bytes = (size_t)c->p.n_total * c->elem;
@@ -657,6 +660,8 @@ int nbody_bind_device_state(nbody_ctx *c, void *posm, void *vel, void *acc) {
   if (!c) return NBODY_ERR_INVALID;
   if (int rc = use_device(c)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->hm_external = true;
+  nbody::hermite_invalidate(c);
   if (posm) {
     if (int rc = posm_escapes(c)) return rc;
     if (c->own_posm) (void)hipFree(c->posm);
@@ -802,7 +807,7 @@ int nbody_step_end(nbody_ctx *c, float dt) {
   HIP_TRY(c, hipSetDevice(c->p.device));
   c->step_open = false;
   if ((rc = run_update(c, dt > 0.0f ? dt : 0.0f))) return rc;
-  if (dt > 0.0f) c->steps_done += 1;
+  if (dt > 0.0f) { c->steps_done += 1; nbody::hermite_invalidate(c); }
   return NBODY_OK;
 }
 
@@ -888,6 +893,7 @@ int nbody_step(nbody_ctx *c, float dt, int32_t nsteps) {
   if (rc) return rc;
   if (nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_step: nsteps < 0");
   if (!(dt > 0.0f)) return NBODY_OK;   // OctreeSearch.cpp:25: PhDeltaTime <= 0 freezes the physics
+  nbody::hermite_invalidate(c);
   if (c->multi) {
     if (c->theta > 0.0f) {                                        // whole frames on every device, one wait per batch (multi_bh_steps)
       int built = 0;
@@ -1046,6 +1052,7 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
   if ((rc = needs_phases(c, "nbody_tick"))) return rc;
   HIP_TRY(c, hipSetDevice(c->p.device));
   const bool live = dt > 0.0f;                                   // OctreeSearch.cpp:25
+  if (live) nbody::hermite_invalidate(c);
   // the eps floor of NBODY_ZERO_FLOOR is computed through the same 64-byte scratch the bounds travel in: settle it
   // before the bounds are queued, or the first frame would return the largest mass as Size
   if (live && c->theta == 0.0f && (rc = ensure_floor(c))) return rc;
@@ -1232,6 +1239,7 @@ int nbody_load_checkpoint(nbody_ctx *c, const char *path, int64_t *steps_done) t
   HIP_TRY(c, hipMemcpy(c->acc, acc.data(), acc.size(), hipMemcpyHostToDevice));
   { const int rc2 = f64 ? note_masses(c, (const double *)posm.data()) : note_masses(c, (const float *)posm.data()); if (rc2) return rc2; }
   c->have_state = true; c->floor_eps2 = -1.0; c->step_open = false; c->step_local = false; c->sym_posg_valid = false;
+  nbody::hermite_invalidate(c);                                    // (the file holds no derivatives: a resumed run starts from the corrected state)
   if (c->bh) nbody::bh_positions_changed(c->bh);
   c->steps_done = h.steps_done;
   // Barnes-Hut: the opening angle and the root of the next tree (the previous tree's CoM, OctreeSearch.cpp:77-79) are
@@ -1684,6 +1692,182 @@ int nbody_jerk_time(nbody_ctx *c, double *t_min, int32_t *body) {
   if ((rc = read_energy(c, &k, &at))) return rc;               // (the scratch's two doubles: the largest |j|^2 / |a|^2, its body)
   if (t_min) *t_min = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
   if (body) *body = (int32_t)at;
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- fourth-order Hermite stepping of fp64 contexts: predictor, the fp64 jerk pass on the predicted state, corrector (kernels_hermite.hip) ----
+namespace {
+// where it exists — fp64 state, one device, all bodies (such contexts are at theta == 0) — and when: a state set, no step half done
+int hermite_ready(nbody_ctx *c, const char *who) {
+  if (c && c->multi) return multi_unsupported(c, who);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (c->p.precision != NBODY_PREC_F64)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): the corrector's "
+                "differences a0 - a1 need fp64 state; create the context with NBODY_PREC_F64", who);
+  if (c->p.i_count != c->p.n_total)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
+  if (c->theta > 0.0f) return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not at theta > 0 (the jerk is a pair sum)", who);
+  if (c->step_open || c->step_local) return fail(c, NBODY_ERR_STATE, "%s: a step is open (nbody_step_end first)", who);
+  return NBODY_OK;
+}
+
+struct HermiteBufs { double *xp, *vp, *a2, *a3, *aj[2], *partials; };
+HermiteBufs hermite_bufs(const nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  double *b = (double *)c->hermite;
+  return HermiteBufs{b, b + 4 * n, b + 8 * n, b + 12 * n, {b + 16 * n, b + 22 * n}, b + 28 * n};
+}
+
+// the cache and the jerk pass's partial rows, at first use
+int hermite_ensure(nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  if (!c->hermite) HIP_TRY(c, hipMalloc(&c->hermite, (28 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
+  return ensure_probe_part(c, (int)n, 3);
+}
+
+// (a, j) of the bodies at (posm, vel) — the live state or the predicted one — into aj64: nbody_get_jerk_f64's pass and fold with the same
+// geometry, a function of n_total alone, queued as one pass under NBODY_KERNEL_FORCES
+int hermite_evaluate(nbody_ctx *c, const void *posm, const void *vel, double *aj64) {
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::JerkLaunch L;
+    L.posm = posm; L.vel = vel; L.part = c->probe_part; L.aj64 = aj64;
+    L.n_total = c->p.n_total; L.m = c->p.n_total; L.precision = NBODY_PREC_F64; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, nbody::launch_jerk(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// what every call does at entry: once somebody else may write the state, nothing cached is believed; (a0, j0) of the stored (x, v)
+int hermite_enter(nbody_ctx *c) {
+  if (int rc = hermite_ensure(c)) return rc;
+  if (c->hm_external) nbody::hermite_invalidate(c);
+  if (c->hm_valid) return NBODY_OK;
+  if (int rc = hermite_evaluate(c, c->posm, c->vel, hermite_bufs(c).aj[c->hm_cur])) return rc;
+  c->hm_valid = true;
+  return NBODY_OK;
+}
+
+// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE
+int hermite_one_step(nbody_ctx *c, double dt) {
+  const HermiteBufs b = hermite_bufs(c);
+  nbody::HermiteLaunch L;
+  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.aj0 = b.aj[c->hm_cur]; L.aj1 = b.aj[c->hm_cur ^ 1];
+  L.a2 = b.a2; L.a3 = b.a3; L.n = c->p.n_total; L.dt = dt;
+  int rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_predict(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  if ((rc = hermite_evaluate(c, b.xp, b.vp, b.aj[c->hm_cur ^ 1]))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_correct(L, c->stream)); return NBODY_OK; }))) return rc;
+  c->hm_cur ^= 1;                                                  // (a0, j0) := (a1, j1)
+  c->hm_derivs = true;
+  c->sym_posg_valid = false;
+  c->steps_done += 1;
+  return NBODY_OK;
+}
+
+// the time scale of the cached derivatives, waited for: *k the largest criterion value, *body where, *kind which criterion
+int hermite_scale(nbody_ctx *c, double *t, int32_t *body, int32_t *kind) {
+  const HermiteBufs b = hermite_bufs(c);
+  const int n = c->p.n_total;
+  if (c->hm_derivs) HIP_TRY(c, nbody::launch_hermite_time(b.aj[c->hm_cur], b.a2, b.a3, n, b.partials, (double *)c->scratch, c->stream));
+  else              HIP_TRY(c, nbody::launch_jerk_time(b.aj[c->hm_cur], n, b.partials, (double *)c->scratch, c->stream));
+  double k = 0.0, at = 0.0;
+  if (int rc = read_energy(c, &k, &at)) return rc;                // (the scratch's two doubles: the largest k, its body)
+  *t = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
+  *body = (int32_t)at;
+  *kind = c->hm_derivs ? 1 : 0;
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
+  int rc = hermite_ready(c, "nbody_hermite_step");
+  if (rc) return rc;
+  if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_step: dt is not finite, or nsteps < 0");
+  if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
+  if ((rc = hermite_enter(c))) return rc;
+  for (int s = 0; s < nsteps; ++s)
+    if ((rc = hermite_one_step(c, dt))) return rc;
+  return NBODY_OK;
+}
+
+int nbody_hermite_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t *kind) {
+  int rc = hermite_ready(c, "nbody_hermite_timescale");
+  if (rc) return rc;
+  if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_timescale: all three outputs are null");
+  if ((rc = hermite_enter(c))) return rc;
+  double t = 0.0;
+  int32_t at = 0, which = 0;
+  if ((rc = hermite_scale(c, &t, &at, &which))) return rc;
+  if (t_min) *t_min = t;
+  if (body) *body = at;
+  if (kind) *kind = which;
+  return NBODY_OK;
+}
+
+int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps, double *t_done,
+                          int64_t *steps) {
+  int rc = hermite_ready(c, "nbody_hermite_advance");
+  if (rc) return rc;
+  if (!(eta > 0.0) || !(eta_start > 0.0) || !(dt_max > 0.0) || !(t_span >= 0.0) || !std::isfinite(t_span) || max_steps < 0)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_advance: eta, eta_start and dt_max must be > 0, t_span >= 0 and finite, max_steps >= 0");
+  double t_acc = 0.0;
+  int64_t taken = 0;
+  if (t_done) *t_done = 0.0;
+  if (steps) *steps = 0;
+  if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
+  if ((rc = hermite_enter(c))) return rc;
+  const double root_eta = std::sqrt(eta);
+  while (t_acc < t_span && taken < max_steps) {
+    double t = 0.0;
+    int32_t at = 0, which = 0;
+    if ((rc = hermite_scale(c, &t, &at, &which))) return rc;
+    double dt = std::min(dt_max, which == 1 ? root_eta * t : eta_start * t);
+    const double rest = t_span - t_acc;
+    const bool last = dt >= rest;
+    if (last) dt = rest;
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(c, NBODY_ERR_STATE, "nbody_hermite_advance: the time scale of body %d gives dt = %g after %lld steps (t = %.17g); the "
+                  "state is that of the last good step", (int)at, dt, (long long)taken, t_acc);
+    if ((rc = hermite_one_step(c, dt))) return rc;
+    t_acc = last ? t_span : t_acc + dt;
+    taken += 1;
+    if (t_done) *t_done = t_acc;
+    if (steps) *steps = taken;
+  }
+  return NBODY_OK;
+}
+
+int nbody_hermite_get(nbody_ctx *c, double *d12, size_t stride) {
+  int rc = hermite_ready(c, "nbody_hermite_get");
+  if (rc) return rc;
+  if (!d12 || stride < 96) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_get: null buffer or stride < 96");
+  if (!c->hermite || !c->hm_valid)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite_get: no derivatives cached for the stored state (nbody_hermite_step or nbody_hermite_timescale first)");
+  const size_t n = (size_t)c->p.n_total;
+  const HermiteBufs b = hermite_bufs(c);
+  if ((rc = ensure_stage(c, n * 112))) return rc;
+  double *h_aj = (double *)c->h_stage, *h_d = h_aj + 6 * n;       // (a2 and a3 lie side by side: 8 doubles per body in all)
+  HIP_TRY(c, hipMemcpyAsync(h_aj, b.aj[c->hm_cur], n * 48, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_d, b.a2, n * 64, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i) {
+    double rec[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    memcpy(rec, h_aj + 6 * i, 48);
+    if (c->hm_derivs) { memcpy(rec + 6, h_d + 4 * i, 24); memcpy(rec + 9, h_d + 4 * (n + i), 24); }
+    memcpy((char *)d12 + i * stride, rec, 96);
+  }
+  return NBODY_OK;
+}
+
+int nbody_hermite_restart(nbody_ctx *c) {
+  int rc = hermite_ready(c, "nbody_hermite_restart");
+  if (rc) return rc;
+  nbody::hermite_invalidate(c);
   return NBODY_OK;
 }
 

@@ -97,6 +97,14 @@ struct nbody_ctx {
   void *tidal64 = nullptr;     // nbody_tidal_time: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
   void *jerk64 = nullptr;      // nbody_get_jerk_f64 / nbody_jerk_time: [n_total][6] double, the bodies' unrounded (a, j), then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
+  // fourth-order Hermite stepping (nbody_hermite_*, kernels_hermite.hip; fp64 contexts): allocated at first use.  hermite holds, in
+  // doubles, xp, vp, a2, a3 ([n_total] double4 each), two rows of (a, j) ([n_total][6] each: hm_cur is (a0, j0), the other takes the
+  // predicted state's), then the reduction's workgroup pairs
+  void *hermite = nullptr;
+  int hm_cur = 0;
+  bool hm_valid = false;       // (a0, j0) are those of the stored (x, v)
+  bool hm_derivs = false;      // a2, a3 are those a step left at the stored state
+  bool hm_external = false;    // a buffer was bound or a pointer handed out: somebody else may write the state, every call evaluates anew
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
@@ -131,6 +139,10 @@ inline int use_device(nbody_ctx *c) {
   HIP_TRY(c, hipSetDevice(c->p.device));
   return NBODY_OK;
 }
+
+// The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): the
+// cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3.
+inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; }
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
 constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain

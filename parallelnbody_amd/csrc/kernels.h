@@ -168,6 +168,27 @@ hipError_t launch_jerk(const JerkLaunch &L, hipStream_t s);
 // value that is not finite as +inf), out[1] = the lowest index that attains it, as a double: launch_tidal_time's reduction.
 hipError_t launch_jerk_time(const double *aj64, int n, double *partials, double *out, hipStream_t s);
 
+// Fourth-order Hermite stepping of an fp64 state — kernels_hermite.hip: the predictor and the corrector around one launch_jerk on the
+// predicted state (the caller's to queue in between), one lane per body, every operation one correctly rounded fp64 operation.
+//   launch_hermite_predict: xp = ((x + dt v) + c2 a0) + c3 j0, vp = (v + dt a0) + c2 j0 per component; xp.w = m, vp.w = 0
+//   launch_hermite_correct: (x, v) := the corrected state from (a0, j0) and (a1, j1), acc := (a1, 0), (a2, a3) := the second and third
+//     derivative of a at the new time
+// aj0 / aj1 are launch_jerk's rows, six doubles per body (ax, ay, az, jx, jy, jz).
+struct HermiteLaunch {
+  void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state (predict reads posm and vel)
+  void *xp = nullptr, *vp = nullptr;                      // [n] double4 each: the predicted state
+  const double *aj0 = nullptr, *aj1 = nullptr;            // [n][6]: (a, j) at the stored state / at the predicted one
+  void *a2 = nullptr, *a3 = nullptr;                      // [n] double4 each
+  int n = 0;
+  double dt = 0.0;
+};
+hipError_t launch_hermite_predict(const HermiteLaunch &L, hipStream_t s);
+hipError_t launch_hermite_correct(const HermiteLaunch &L, hipStream_t s);
+// out[0] = max over the n bodies of Aarseth's k = (|j| |a3| + |a2|^2) / (|a| |a2| + |j|^2), norms sqrt((x x + y y) + z z) (0 / 0 counts
+// as 0, x / 0 and every value that is not finite as +inf), out[1] = the lowest index that attains it, as a double: launch_jerk_time's
+// reduction and its `partials`.
+hipError_t launch_hermite_time(const double *aj0, const void *a2, const void *a3, int n, double *partials, double *out, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

@@ -431,6 +431,40 @@ class NBodyEngine:
         self._check(self._L.nbody_jerk_time(self._h, ctypes.byref(t), ctypes.byref(body)))
         return t.value, body.value
 
+    # -- fourth-order Hermite stepping (fp64 contexts) --
+    def hermite_step(self, dt, nsteps=1):
+        """nsteps shared steps of length dt of the fourth-order Hermite predictor-corrector (nbody_hermite_step): one fp64 jerk pass
+        per step once the derivatives are cached.  The stored velocities are taken as SYNCHRONISED with the positions — step() leaves
+        them staggered.  precision="f64" contexts on one device owning all bodies; everything else: ERR_UNSUPPORTED.  dt <= 0: no-op."""
+        self._check(self._L.nbody_hermite_step(self._h, float(dt), int(nsteps)))
+
+    def hermite_timescale(self):
+        """(t, body, kind): the shared step's time scale and the body that sets it (nbody_hermite_timescale).  kind 1: Aarseth's
+        criterion from the cached a, j, a2, a3 (a step has been taken); kind 0: jerk_time()'s |a| / |j| (none has)."""
+        t, body, kind = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.nbody_hermite_timescale(self._h, ctypes.byref(t), ctypes.byref(body), ctypes.byref(kind)))
+        return t.value, body.value, kind.value
+
+    def hermite_advance(self, t_span, eta=0.02, eta_start=0.01, dt_max=float("inf"), max_steps=2 ** 31):
+        """(t_done, steps): shared adaptive Hermite steps, dt = min(dt_max, sqrt(eta) t) — eta_start t for a step without cached
+        derivatives —, until t_span has passed (t_done == t_span exactly) or max_steps have been taken (nbody_hermite_advance)."""
+        t, n = ctypes.c_double(), ctypes.c_int64()
+        self._check(self._L.nbody_hermite_advance(self._h, float(t_span), float(eta), float(eta_start), float(dt_max), int(max_steps),
+                                                  ctypes.byref(t), ctypes.byref(n)))
+        return t.value, n.value
+
+    def hermite_state(self):
+        """(a, j, a2, a3): the cached derivatives of the stored state, four [n_total,3] float64 arrays (nbody_hermite_get); a2 and a3
+        are zeros until a step has been taken.  ERR_STATE while nothing is cached for the stored state."""
+        out = np.empty((self.n_total, 12), np.float64)
+        self._check(self._L.nbody_hermite_get(self._h, out.ctypes.data, 96))
+        return tuple(np.ascontiguousarray(out[:, 3 * k:3 * k + 3]) for k in range(4))
+
+    def hermite_restart(self):
+        """Forget the cached derivatives: the next Hermite call starts from the stored (x, v) alone, as a resumed run does
+        (nbody_hermite_restart)."""
+        self._check(self._L.nbody_hermite_restart(self._h))
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
