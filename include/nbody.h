@@ -519,6 +519,77 @@ NBODY_AMD_API int nbody_hermite_advance(nbody_ctx *ctx, double t_span, double et
 NBODY_AMD_API int nbody_hermite_get(nbody_ctx *ctx, double *d12, size_t stride);
 NBODY_AMD_API int nbody_hermite_restart(nbody_ctx *ctx);
 
+/* Hermite BLOCK time steps (build-defined: the reference has one step for all bodies) — the same predictor, evaluation and corrector
+ * with a step per body: a hard binary steps often, the rest of the system seldom, and an evaluation costs (bodies due) x N pairs instead
+ * of N^2.  Where: the contexts that answer nbody_hermite_step (NBODY_PREC_F64, one device, all bodies); fp32 and Kahan contexts, slice
+ * contexts and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED with that call's reasons.  No particles set: NBODY_ERR_STATE.
+ *
+ * Time is counted in integer ticks: tick = ldexp(dt_max, -levels), 0 <= levels <= 40.  Body i holds a time T_i (int64 ticks), a level
+ * k_i in 0 .. levels whose step is 2^(levels - k_i) ticks = dt_max 2^-k_i, (x_i, v_i) AT T_i in the context's state buffers and
+ * (a0, j0, a2, a3)_i at T_i in the Hermite cache.  T_i is always a multiple of the body's step, so every body lands on every multiple
+ * of 2^levels ticks: a FRAME end, where the stored state is synchronised.  In between it is RAGGED: x_i is at T_i.
+ *
+ * One block step — every bracket ONE correctly rounded fp64 operation, contraction off, as in the paragraph above:
+ *   schedule   T_next = min_i (T_i + step_i); the active set = the bodies that attain it, as a list in ascending body index (built by a
+ *              scan: no atomics).  No body's result depends on its place in the list or on the other members.
+ *   predict    EVERY body to T_next: dt_i = (double)(T_next - T_i) * tick (for an active body exactly dt_max 2^-k_i); on the device
+ *              c2 = (dt_i dt_i) 0.5, c3 = ((dt_i dt_i) dt_i) / 6;  xp = ((x + dt_i v) + c2 a0) + c3 j0;  vp = (v + dt_i a0) + c2 j0
+ *   evaluate   (a1, j1) of the ACTIVE bodies against all N predicted bodies: for every active body, in every bit, what
+ *              nbody_get_jerk_f64 returns for that body on a context holding (xp, vp) — the same chunks, pair operations and order
+ *   correct    the active bodies, by the corrector above with the body's own dt_i (ch, c12, d2, d3 formed on the device in that order):
+ *              x, v, NBODY_BUF_ACC := (a1, 0), (a0, j0) := (a1, j1), a2 := a2_1, a3, T_i := T_next.  Inactive bodies keep every byte.
+ *   levels     of the active bodies: k = (J C + S S) / (A S + J J) of nbody_hermite_timescale from the NEW vectors; t = +inf for k == 0,
+ *              0 for a k that is not finite, else 1.0 / sqrt(k); dt_c = sqrt(eta) * t (sqrt(eta) the host's double); the wanted level
+ *              kw = nbody_hermite_block_level(dt_c, dt_max, levels, &hit).  kw > k_i: k_i := kw (a smaller step, by any amount).
+ *              kw < k_i and T_next a multiple of 2^(levels - k_i + 1): k_i := k_i - 1 (one level up at most, and only when aligned).
+ *              Otherwise k_i stays.
+ * nbody_steps_done grows by one per block step; a block step is one pass under NBODY_KERNEL_FORCES and — schedule, predictor and
+ * corrector together — one under NBODY_KERNEL_UPDATE.  The host reads 16 bytes per block step (T_next and the number of active bodies)
+ * to size the evaluation.
+ *
+ * nbody_hermite_block_level (host only, no context): the smallest k in 0 .. levels with ldexp(dt_max, -k) <= dt_c.  If there is none
+ *   (dt_c below the smallest step, 0, or not a number) it returns `levels` and *floor_hit = 1 — the body is CLAMPED to the deepest level,
+ *   not refused, and counted —; otherwise *floor_hit = 0 (floor_hit may be NULL).  levels outside 0 .. 40: -1.
+ * nbody_hermite_block_begin: starts a session at tick 0 from the stored (x, v), taken as synchronised.  (a0, j0) come from the shared
+ *   cache where it is valid (its a2, a3 too, if a step left them) and otherwise from one evaluation at the stored state (one pass; a2 and
+ *   a3 then read as zeros until a body has stepped).  level_in, if not NULL: n_total levels, each 0 .. levels (else NBODY_ERR_INVALID) —
+ *   how a host resumes, checkpoints hold no levels.  NULL: every body gets the level of dt_c = eta_start * t, t from nbody_jerk_time's
+ *   per-body k = |j|^2 / |a|^2 with the same 0 / not-finite rules (a body no level fits is a floor hit here too).  dt_max, eta and
+ *   eta_start must be finite and > 0, levels 0 .. 40 and the tick a normal double: anything else is NBODY_ERR_INVALID.  On a session in
+ *   mid-frame: NBODY_ERR_STATE; at a frame end the old session ends and the new one begins.  Synchronises.  On a context whose
+ *   buffers are bound or whose pointers are out, begin evaluates anew like every Hermite call; the session then trusts the state
+ *   until it ends (a new nbody_device_ptr or bind ends it).
+ * nbody_hermite_block_advance: block steps until T_sys reaches (floor(T_sys / 2^levels) + frames) 2^levels or max_block_steps have been
+ *   taken; frames == 0 takes none.  After a stop in mid-frame the state is ragged; a later call with frames = 1 finishes the frame.
+ *   *out (may be NULL; set out->struct_size = sizeof(nbody_hermite_block_stats) first, another size is NBODY_ERR_INVALID) gets the totals
+ *   since begin.  frames or max_block_steps < 0, or frames whose end passes 2^62 ticks: NBODY_ERR_INVALID.  No session: NBODY_ERR_STATE.
+ * nbody_hermite_block_get: T_i and k_i, n_total values each; either may be NULL.  No session: NBODY_ERR_STATE.  Synchronises.
+ *
+ * What ends a session: everything that invalidates the shared cache (the list above: uploads, nbody_step / nbody_tick / nbody_step_end
+ * with dt > 0, nbody_bind_device_state, nbody_device_ptr) and nbody_hermite_restart — in mid-frame the state then stays ragged, which is
+ * the caller's to know.  nbody_hermite_step / _timescale / _advance report NBODY_ERR_STATE on a session in mid-frame, with a message that
+ * says why; at a frame end they work from the cache and end the session.  nbody_hermite_get works during a session: a body's row belongs
+ * to its own T_i.  Checkpoints stay NBDYCKP2 byte for byte and hold neither cache nor levels: the trajectory a resumed run takes —
+ * load, begin with the saved levels, go on — is "nbody_save_checkpoint, nbody_hermite_restart, nbody_hermite_block_begin with the levels
+ * of nbody_hermite_block_get, go on" on the context that wrote the file, equal in every byte.
+ */
+typedef struct nbody_hermite_block_stats {
+  uint32_t struct_size;   /* caller sets sizeof(nbody_hermite_block_stats) before the call */
+  int32_t synchronised;   /* 1: T_sys is a frame end, every body is at T_sys */
+  int64_t ticks;          /* T_sys */
+  int64_t frames_done;    /* floor(T_sys / 2^levels) */
+  int64_t block_steps;
+  int64_t body_steps;     /* sum of the active sets' sizes m */
+  int64_t pairs;          /* sum of m * n_total */
+  int64_t floor_hits;     /* bodies clamped to the deepest level, begin's included */
+  int32_t level_min, level_max;   /* over the bodies, now */
+} nbody_hermite_block_stats;      /* 64 bytes */
+NBODY_AMD_API int nbody_hermite_block_level(double dt_c, double dt_max, int32_t levels, int32_t *floor_hit);
+NBODY_AMD_API int nbody_hermite_block_begin(nbody_ctx *ctx, double dt_max, int32_t levels, double eta, double eta_start,
+                                            const int32_t *level_in);
+NBODY_AMD_API int nbody_hermite_block_advance(nbody_ctx *ctx, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out);
+NBODY_AMD_API int nbody_hermite_block_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

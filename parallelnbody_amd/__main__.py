@@ -7,6 +7,7 @@
     python -m parallelnbody_amd --n 2000 --theta 1.0 --steps 600 --trajectory run.trj --trajectory-every 10   # as shipped: Barnes-Hut, theta = 1
     python -m parallelnbody_amd --n 2000 --theta 1.0 --eps 5 --steps 600          # Barnes-Hut with every accepted node's term softened
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite --eta 0.02 --dt 0.05 --steps 20 --energy-every 5
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite-block --levels 12 --dt 0.05 --steps 20 --energy-every 5
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -46,10 +47,13 @@ def main(argv=None):
     ap.add_argument("--eps", type=float, default=0.0, help="softening length (reference: 0)")
     ap.add_argument("--G", type=float, default=1.0e4, help="gravitational constant (reference: 1e4)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f32_kahan", "f64"])
-    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite"],
+    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite", "hermite-block"],
                     help="kickdrift: the reference's v += dt a; x += dt v (default).  hermite: the fourth-order Hermite "
                          "predictor-corrector (needs --precision f64, theta = 0): one step of --dt per frame, or with --eta "
-                         "adaptive shared steps that cover --dt per frame")
+                         "adaptive shared steps that cover --dt per frame.  hermite-block: the same scheme with a step per body, "
+                         "--dt 2^-level with level 0 .. --levels chosen by --eta (default 0.02); every frame of --dt ends synchronised")
+    ap.add_argument("--levels", type=int, default=None,
+                    help="--integrator hermite-block: the deepest level, 0 .. 40 (default 12): the smallest step is --dt 2^-levels")
     ap.add_argument("--eta", type=float, default=None,
                     help="--integrator hermite: Aarseth's accuracy parameter; every frame of length --dt is covered by adaptive steps "
                          "dt = sqrt(eta) t (0.01 t for a frame's first step after a restart)")
@@ -83,13 +87,16 @@ def main(argv=None):
 
     if a.trajectory_every < 1:
         ap.error("--trajectory-every must be >= 1")
-    hermite = a.integrator == "hermite"
+    block = a.integrator == "hermite-block"
+    hermite = a.integrator == "hermite" or block
     if hermite and a.precision != "f64":
-        ap.error("--integrator hermite needs --precision f64")
+        ap.error(f"--integrator {a.integrator} needs --precision f64")
     if hermite and (a.theta or a.leapfrog_start or a.sync_energy):
         ap.error("--integrator hermite steps synchronised velocities at theta = 0: not with --theta, --leapfrog-start or --sync-energy")
     if a.eta is not None and not (hermite and a.eta > 0):
-        ap.error("--eta belongs to --integrator hermite and must be > 0")
+        ap.error("--eta belongs to --integrator hermite and hermite-block and must be > 0")
+    if a.levels is not None and not (block and 0 <= a.levels <= 40):
+        ap.error("--levels belongs to --integrator hermite-block and must be 0 .. 40")
     posm, vel = (ic_plummer(a.n, G=a.G, seed=a.seed) if a.plummer else ic_reference_box(a.n, a.size, seed=a.seed))
     with NBodyEngine(a.n, device=a.device, precision=a.precision, G=a.G, eps=a.eps, theta=a.theta or 0.0) as e:
         e.set_state(posm, vel)
@@ -116,9 +123,16 @@ def main(argv=None):
                 vs = v[:, :3] + 0.5 * a.dt * acc[:, :3]
                 out["total_synchronised"] = 0.5 * float((p[:, 3] * (vs ** 2).sum(1)).sum()) + pe
             return out
+        session = []
         def advance(frames):
             if not hermite:
                 e.step(a.dt, frames)
+            elif block:
+                if a.dt > 0 and frames > 0:
+                    if not session:                              # one session for the run: nothing below ends it
+                        e.hermite_block_begin(a.dt, 12 if a.levels is None else a.levels, eta=a.eta or 0.02)
+                        session.append(True)
+                    e.hermite_block_advance(frames)
             elif a.eta is None:
                 e.hermite_step(a.dt, frames)
             else:

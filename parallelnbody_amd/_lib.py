@@ -81,6 +81,22 @@ class Moments(ctypes.Structure):
     ]
 
 
+class HermiteBlockStats(ctypes.Structure):
+    """struct nbody_hermite_block_stats (include/nbody.h): a block session's totals since nbody_hermite_block_begin."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("synchronised", ctypes.c_int32),
+        ("ticks", ctypes.c_int64),
+        ("frames_done", ctypes.c_int64),
+        ("block_steps", ctypes.c_int64),
+        ("body_steps", ctypes.c_int64),
+        ("pairs", ctypes.c_int64),
+        ("floor_hits", ctypes.c_int64),
+        ("level_min", ctypes.c_int32),
+        ("level_max", ctypes.c_int32),
+    ]
+
+
 MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
 
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
@@ -162,6 +178,10 @@ def lib():
     sig("nbody_hermite_advance", c_int, vp, c_d, c_d, c_d, c_d, c_i64, dp, ctypes.POINTER(c_i64))
     sig("nbody_hermite_get", c_int, vp, vp, sz)
     sig("nbody_hermite_restart", c_int, vp)
+    sig("nbody_hermite_block_level", c_int, c_d, c_d, c_i32, ctypes.POINTER(c_i32))
+    sig("nbody_hermite_block_begin", c_int, vp, c_d, c_i32, c_d, c_d, vp)
+    sig("nbody_hermite_block_advance", c_int, vp, c_i64, c_i64, ctypes.POINTER(HermiteBlockStats))
+    sig("nbody_hermite_block_get", c_int, vp, vp, vp)
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

@@ -11,6 +11,7 @@
 
 #include "bh_driver.h"
 #include "ctx.h"
+#include "hermite_block_level.h"
 #include "launch_policy.h"
 
 namespace {
@@ -614,7 +615,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite, c->hblock})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1714,6 +1715,19 @@ int hermite_ready(nbody_ctx *c, const char *who) {
   return NBODY_OK;
 }
 
+// A shared-step call, or a new begin, on a context with a block session: in mid-frame the bodies are at times of their own and nothing
+// but nbody_hermite_block_advance can move them on; at a frame end the stored state is synchronised, the cache is every body's, and the
+// session simply ends.
+int hermite_block_leave(nbody_ctx *c, const char *who) {
+  if (!c->hb.active) return NBODY_OK;
+  if (c->hb.ticks & ((1ll << c->hb.levels) - 1))
+    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is in mid-frame (tick %lld of frames of %lld): the bodies are at times of "
+                "their own; nbody_hermite_block_advance(ctx, 1, ...) finishes the frame, nbody_hermite_restart abandons the session", who,
+                (long long)c->hb.ticks, 1ll << c->hb.levels);
+  c->hb.active = false;
+  return NBODY_OK;
+}
+
 struct HermiteBufs { double *xp, *vp, *a2, *a3, *aj[2], *partials; };
 HermiteBufs hermite_bufs(const nbody_ctx *c) {
   const size_t n = (size_t)c->p.n_total;
@@ -1789,6 +1803,7 @@ int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if (rc) return rc;
   if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_step: dt is not finite, or nsteps < 0");
   if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
+  if ((rc = hermite_block_leave(c, "nbody_hermite_step"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   for (int s = 0; s < nsteps; ++s)
     if ((rc = hermite_one_step(c, dt))) return rc;
@@ -1799,6 +1814,7 @@ int nbody_hermite_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t 
   int rc = hermite_ready(c, "nbody_hermite_timescale");
   if (rc) return rc;
   if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_timescale: all three outputs are null");
+  if ((rc = hermite_block_leave(c, "nbody_hermite_timescale"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   double t = 0.0;
   int32_t at = 0, which = 0;
@@ -1820,6 +1836,7 @@ int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_st
   if (t_done) *t_done = 0.0;
   if (steps) *steps = 0;
   if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
+  if ((rc = hermite_block_leave(c, "nbody_hermite_advance"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   const double root_eta = std::sqrt(eta);
   while (t_acc < t_span && taken < max_steps) {
@@ -1858,7 +1875,7 @@ int nbody_hermite_get(nbody_ctx *c, double *d12, size_t stride) {
   for (size_t i = 0; i < n; ++i) {
     double rec[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     memcpy(rec, h_aj + 6 * i, 48);
-    if (c->hm_derivs) { memcpy(rec + 6, h_d + 4 * i, 24); memcpy(rec + 9, h_d + 4 * (n + i), 24); }
+    if (c->hm_derivs || c->hb.active) { memcpy(rec + 6, h_d + 4 * i, 24); memcpy(rec + 9, h_d + 4 * (n + i), 24); }   // (a session keeps zeros where a body has none)
     memcpy((char *)d12 + i * stride, rec, 96);
   }
   return NBODY_OK;
@@ -1868,6 +1885,158 @@ int nbody_hermite_restart(nbody_ctx *c) {
   int rc = hermite_ready(c, "nbody_hermite_restart");
   if (rc) return rc;
   nbody::hermite_invalidate(c);
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- Hermite block time steps: a session of per-body power-of-two steps on the cache above (kernels_hermite_block.hip) ----
+namespace {
+struct HermiteBlockBufs { long long *T, *seg_min, *record; unsigned long long *floor_hits; int *level, *list, *seg_cnt; };
+HermiteBlockBufs hermite_block_bufs(const nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  int slots;
+  (void)nbody::hermite_block_segment((int)n, &slots);
+  long long *q = (long long *)c->hblock;
+  int *w = (int *)(q + n + slots + 3);
+  return HermiteBlockBufs{q, q + n, q + n + slots, (unsigned long long *)(q + n + slots + 2), w, w + n, w + 2 * n};
+}
+size_t hermite_block_bytes(int n) {
+  int slots;
+  (void)nbody::hermite_block_segment(n, &slots);
+  return ((size_t)n + slots + 3) * 8 + (2 * (size_t)n + slots) * 4;
+}
+
+nbody::HermiteBlockLaunch hermite_block_launch(const nbody_ctx *c) {
+  const HermiteBufs b = hermite_bufs(c);
+  const HermiteBlockBufs q = hermite_block_bufs(c);
+  nbody::HermiteBlockLaunch L;
+  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.aj0 = b.aj[c->hm_cur]; L.a2 = b.a2; L.a3 = b.a3;
+  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = q.record;
+  L.floor_hits = q.floor_hits; L.n = c->p.n_total; L.levels = c->hb.levels; L.tick = c->hb.tick; L.dt_max = c->hb.dt_max;
+  L.root_eta = c->hb.root_eta; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+  return L;
+}
+
+// the totals since begin; the levels' range and the floor hits are read from the device (4 n + 8 bytes): waits for the stream
+int hermite_block_fill(nbody_ctx *c, nbody_hermite_block_stats *out) {
+  const size_t n = (size_t)c->p.n_total;
+  const HermiteBlockBufs q = hermite_block_bufs(c);
+  if (int rc = ensure_stage(c, n * 4 + 8)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.floor_hits, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int64_t floor_hits;
+  memcpy(&floor_hits, c->h_stage, 8);
+  const int32_t *lv = (const int32_t *)((const char *)c->h_stage + 8);
+  out->synchronised = (c->hb.ticks & ((1ll << c->hb.levels) - 1)) == 0 ? 1 : 0;
+  out->ticks = c->hb.ticks; out->frames_done = c->hb.ticks >> c->hb.levels; out->block_steps = c->hb.block_steps;
+  out->body_steps = c->hb.body_steps; out->pairs = c->hb.pairs; out->floor_hits = floor_hits;
+  out->level_min = *std::min_element(lv, lv + n); out->level_max = *std::max_element(lv, lv + n);
+  return NBODY_OK;
+}
+
+// one block step, from the schedule to the stored bodies; the host waits once, for (T_next, m), to size the evaluation
+int hermite_block_one_step(nbody_ctx *c) {
+  const nbody::HermiteBlockLaunch L = hermite_block_launch(c);
+  int rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_schedule(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  long long rec[2];
+  memcpy(rec, c->h_scratch, 16);
+  const long long t_next = rec[0];
+  const int n = c->p.n_total, m = (int)rec[1];
+  if (rec[1] < 1 || rec[1] > n || t_next <= c->hb.ticks)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_advance: the schedule gave T_next = %lld, m = %lld at tick %lld", t_next, rec[1], (long long)c->hb.ticks);
+  const int lanes = nbody::hermite_block_lanes(m, c->hb.lanes);
+  const int slab = (int)std::min<size_t>(nbody::probe_slab_points(n, 3), (size_t)n);   // (the partial rows of ensure_probe_part(n, 3))
+  for (int first = 0; first < m; first += slab) {
+    const int ms = std::min(slab, m - first);
+    const bool last = first + ms == m;
+    if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_evaluate(L, first, ms, lanes, c->stream)); return NBODY_OK; }, last))) return rc;
+    if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_correct(L, first, ms, t_next, c->stream)); return NBODY_OK; }, last))) return rc;
+  }
+  c->hb.ticks = t_next;
+  c->hb.block_steps += 1; c->hb.body_steps += m; c->hb.pairs += (int64_t)m * n;
+  if (c->hb.ticks >= (1ll << c->hb.levels)) c->hm_derivs = true;    // a whole frame: every body has stepped, every a2 and a3 is a step's
+  c->sym_posg_valid = false;
+  c->steps_done += 1;
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_hermite_block_level(double dt_c, double dt_max, int32_t levels, int32_t *floor_hit) {
+  if (levels < 0 || levels > nbody::kHermiteBlockMaxLevels) return -1;
+  int hit = 0;
+  const int k = nbody::hermite_block_level(dt_c, dt_max, levels, &hit);
+  if (floor_hit) *floor_hit = hit;
+  return k;
+}
+
+int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
+  int rc = hermite_ready(c, "nbody_hermite_block_begin");
+  if (rc) return rc;
+  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!positive(dt_max) || !positive(eta) || !positive(eta_start) || levels < 0 || levels > nbody::kHermiteBlockMaxLevels)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: dt_max, eta and eta_start must be finite and > 0, levels 0 .. %d", nbody::kHermiteBlockMaxLevels);
+  const double tick = std::ldexp(dt_max, -levels);
+  if (!std::isnormal(tick))
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: the tick dt_max 2^-levels = %g is not a normal number", tick);
+  const int n = c->p.n_total;
+  if (level_in)
+    for (int i = 0; i < n; ++i)
+      if (level_in[i] < 0 || level_in[i] > levels)
+        return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
+  if ((rc = hermite_block_leave(c, "nbody_hermite_block_begin"))) return rc;
+  if ((rc = hermite_enter(c))) return rc;
+  if (!c->hblock) HIP_TRY(c, hipMalloc(&c->hblock, hermite_block_bytes(n)));
+  c->hb.levels = levels; c->hb.dt_max = dt_max; c->hb.tick = tick; c->hb.root_eta = std::sqrt(eta);
+  c->hb.lanes = nbody::env_int("NBODY_HERMITE_BLOCK_LANES", 0);
+  c->hb.ticks = c->hb.block_steps = c->hb.body_steps = c->hb.pairs = 0;
+  const nbody::HermiteBlockLaunch L = hermite_block_launch(c);
+  if (!c->hm_derivs) HIP_TRY(c, hipMemsetAsync(L.a2, 0, (size_t)n * 64, c->stream));   // a2 and a3 lie side by side: zeros until a body steps
+  HIP_TRY(c, hipMemsetAsync(L.record, 0, 24, c->stream));          // the record and the floor hits
+  if (level_in) HIP_TRY(c, hipMemcpyAsync(L.list, level_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, nbody::launch_hermite_block_init(L, level_in ? L.list : nullptr, eta_start, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's array is its own again
+  c->hb.active = true;
+  return NBODY_OK;
+}
+
+int nbody_hermite_block_advance(nbody_ctx *c, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out) {
+  int rc = hermite_ready(c, "nbody_hermite_block_advance");
+  if (rc) return rc;
+  if (frames < 0 || max_block_steps < 0 || (out && out->struct_size != sizeof(nbody_hermite_block_stats)))
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_advance: frames < 0, max_block_steps < 0, or out->struct_size is not "
+                "sizeof(nbody_hermite_block_stats) = %d", (int)sizeof(nbody_hermite_block_stats));
+  if (!c->hb.active)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_advance: no block session (nbody_hermite_block_begin first; uploads, kick-drift "
+                "steps, handed-out pointers, shared Hermite steps and nbody_hermite_restart end one)");
+  const int64_t frame_now = c->hb.ticks >> c->hb.levels;
+  if (frames >= (1ll << 62 >> c->hb.levels) - frame_now)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_advance: %lld more frames of 2^%d ticks pass 2^62 ticks", (long long)frames, c->hb.levels);
+  const int64_t target = frames == 0 ? c->hb.ticks : (frame_now + frames) << c->hb.levels;
+  for (int64_t taken = 0; c->hb.ticks < target && taken < max_block_steps; ++taken)
+    if ((rc = hermite_block_one_step(c))) return rc;
+  return out ? hermite_block_fill(c, out) : NBODY_OK;
+}
+
+int nbody_hermite_block_get(nbody_ctx *c, int64_t *ticks, int32_t *level) {
+  int rc = hermite_ready(c, "nbody_hermite_block_get");
+  if (rc) return rc;
+  if (!c->hb.active)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_get: no block session (nbody_hermite_block_begin first)");
+  const size_t n = (size_t)c->p.n_total;
+  const HermiteBlockBufs q = hermite_block_bufs(c);
+  if ((rc = ensure_stage(c, n * 12))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.T, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + n * 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (ticks) memcpy(ticks, c->h_stage, n * 8);
+  if (level) memcpy(level, (const char *)c->h_stage + n * 8, n * 4);
   return NBODY_OK;
 }
 

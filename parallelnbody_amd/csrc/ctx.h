@@ -105,6 +105,16 @@ struct nbody_ctx {
   bool hm_valid = false;       // (a0, j0) are those of the stored (x, v)
   bool hm_derivs = false;      // a2, a3 are those a step left at the stored state
   bool hm_external = false;    // a buffer was bound or a pointer handed out: somebody else may write the state, every call evaluates anew
+  // Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip): a session on the cache above.  hblock, allocated at the
+  // first begin: T [n] int64, the scheduler's segment minima [slots] int64, the record (T_next, m) and the floor-hit count (int64 each),
+  // then level [n], list [n] and the segment counts [slots] as int32
+  void *hblock = nullptr;
+  struct {
+    bool active = false;       // between nbody_hermite_block_begin and whatever ends the session
+    int levels = 0, lanes = 0; // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE_BLOCK_LANES (0: by the list's length)
+    double dt_max = 0.0, tick = 0.0, root_eta = 0.0;
+    int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
+  } hb;
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
@@ -141,8 +151,8 @@ inline int use_device(nbody_ctx *c) {
 }
 
 // The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): the
-// cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3.
-inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; }
+// cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3; a block session ends.
+inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; c->hb.active = false; }
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
 constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain

@@ -189,6 +189,37 @@ hipError_t launch_hermite_correct(const HermiteLaunch &L, hipStream_t s);
 // reduction and its `partials`.
 hipError_t launch_hermite_time(const double *aj0, const void *a2, const void *a3, int n, double *partials, double *out, hipStream_t s);
 
+// Hermite block time steps of an fp64 state — kernels_hermite_block.hip: per-body times T (ticks of dt_max 2^-levels) and levels, a
+// scheduler that lists the bodies due next in ascending index and predicts EVERY body to that time, the fp64 jerk pass on the listed
+// bodies alone (jerk_tile64.h: nbody_get_jerk_f64's chunks, pair operations and order), and a corrector for the listed bodies that adds
+// the chunks' rows, steps the body by its own dt and chooses its next level (hermite_block_level.h).
+//   launch_hermite_block_init:      T := 0; level := level_in (device, may be null: the level of eta_start |a| / |j| from aj0)
+//   launch_hermite_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp) = every body at T_next
+//   launch_hermite_block_evaluate:  the rows of list[first .. first + m) into part, m <= probe_slab_points(n, 3); lanes = bodies per lane
+//   launch_hermite_block_correct:   those bodies corrected from part (the rows of that launch), their T, level, cache and state stored
+struct HermiteBlockLaunch {
+  void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state
+  void *xp = nullptr, *vp = nullptr;                      // [n] double4 each: the predicted state
+  double *aj0 = nullptr;                                  // [n][6]: every body's (a, j) at its own time
+  void *a2 = nullptr, *a3 = nullptr;                      // [n] double4 each
+  void *part = nullptr;                                   // [probe_part_elems(n, m, 3)] float4: the evaluation's partial rows
+  long long *T = nullptr;                                 // [n] ticks
+  int *level = nullptr, *list = nullptr;                  // [n] each
+  long long *seg_min = nullptr;                           // [slots of hermite_block_segment]
+  int *seg_cnt = nullptr;                                 // [slots]
+  long long *record = nullptr;                            // [2]: T_next, m
+  unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
+  int n = 0, levels = 0;
+  double tick = 0.0, dt_max = 0.0, root_eta = 0.0, G = 0.0, eps2 = 0.0;
+};
+constexpr int kHermiteBlockOneLaneMax = 1024;   // listed bodies up to which the evaluation holds one body per lane (more workgroups)
+int hermite_block_segment(int n, int *slots);   // bodies per scheduler workgroup (a multiple of 256); *slots = the workgroups
+int hermite_block_lanes(int m, int forced);     // bodies per lane for m listed bodies; forced 1 or 2 overrides (A/B runs, tests)
+hipError_t launch_hermite_block_init(const HermiteBlockLaunch &L, const int *level_in, double eta_start, hipStream_t s);
+hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_t s);
+hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first, int m, int lanes, hipStream_t s);
+hipError_t launch_hermite_block_correct(const HermiteBlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

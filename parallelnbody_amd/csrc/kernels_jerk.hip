@@ -5,7 +5,7 @@
 //   probe_jerk_pk_kernel   <- fp32 state: the tile loop of point_tile.h with the bodies' velocities in a second pair of LDS tiles, the
 //                             potential's distance term, six accumulators, no s^-5; SELF: the points are the bodies, j == i dropped by index
 //   jerk_fold_kernel       <- the chunks' rows added in chunk order in fp64, rounded once
-//   jerk_tile_f64_kernel   <- fp64 state, the bodies only: scalar, shaped like forces_tile_kernel<double> (kernels.hip)
+//   jerk_tile_f64_kernel   <- fp64 state, the bodies only: scalar, shaped like forces_tile_kernel<double> (kernels.hip): the <SOFT, 2, false> form of jerk_tile64.h's template
 //   jerk_fold_f64_kernel   <- its chunks' rows added in chunk order
 //   jerk_time_*_kernel     <- the largest |j_i|^2 / |a_i|^2 of the unrounded vectors and its body, reduced in a fixed order
 #include "kernels.h"
@@ -13,13 +13,12 @@
 #include <algorithm>
 
 #include "../../include/nbody.h"
+#include "jerk_tile64.h"
 #include "point_tile.h"
 
 namespace nbody {
 
 namespace {
-
-constexpr int kJerkTile = 256;
 
 // The jerk's pair term for JB j-bodies against NP register pairs of points, stage by stage like tidal_group_pk (kernels_probe.hip), whose
 // distance term it takes as it is (Z_SOFT / Z_CLAMP, the same rsq, GUARD by index): t = 1 / s, or 0 for a pair that adds nothing.
@@ -145,119 +144,9 @@ __global__ __launch_bounds__(kBlock) void jerk_fold_kernel(const float4 *__restr
 
 // ---- fp64 state ----
 
-// 1 / sqrt(x) as the fp64 force kernels form it (kernels.hip, kernels_sym64.hip): the v_rsq_f64 seed and one third-order step.
-__device__ __forceinline__ double rsq_dev(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = fma(-(x * y), y, 1.0);
-  const double q = e * fma(e, 0.375, 0.5);
-  return fma(y, q, y);
-}
-
 constexpr int kJerk64Ipt = 2;   // bodies per lane
-constexpr int kJerk64Jb = 2;    // j-bodies per staged group
 
-// Every body's a and j from all other bodies on an fp64 context: lane t of workgroup g holds bodies i_first + g * 512 + t (+ 256), the
-// bodies go through double-buffered LDS tiles as (x, y, z, G m) and (vx, vy, vz, -).  Per pair, s2 = fma(dx, dx, fma(dy, dy, dz * dz
-// [+ eps^2])), t = rsq(s2) — 0 where s2 == 0 and for j == i by index —, then
-//   t2 = t * t;  q = (G m * t) * t2;  k3 = -3 * ((d . w) * t2), d . w = fma(dx, wx, fma(dy, wy, dz * wz));  u_a = fma(k3, d_a, w_a)
-//   A_a = fma(q, d_a, A_a);  J_a = fma(q, u_a, J_a)
-// — one chain per sum and chunk of probe_geometry, in body order.  A chunk's row is six doubles per body.
-template <bool SOFT>
-__global__ __launch_bounds__(kBlock) void jerk_tile_f64_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
-                                                               double *__restrict__ part, int n_total, int m, int i_first, int j_chunk,
-                                                               double gscale, double eps2) {
-  constexpr int IPT = kJerk64Ipt, JB = kJerk64Jb, TILE = kJerkTile;
-  static_assert(TILE == kBlock, "a lane stages one body per tile");
-  __shared__ double4 shp[2][TILE], shv[2][TILE];
-
-  const int t = threadIdx.x;
-  const int ibase = blockIdx.x * (kBlock * IPT);
-  const int c = blockIdx.y;
-  const int j0 = c * j_chunk;
-  const int j1 = min(j0 + j_chunk, n_total);
-  const int ntiles = (j1 > j0) ? (j1 - j0 + TILE - 1) / TILE : 0;
-
-  double xi[IPT], yi[IPT], zi[IPT], vxi[IPT], vyi[IPT], vzi[IPT];
-  int self[IPT];
-  double A[IPT][3], J[IPT][3];
-#pragma unroll
-  for (int k = 0; k < IPT; ++k) {
-    self[k] = i_first + min(ibase + t + k * kBlock, m - 1);
-    const double4 p = posm[self[k]], v = vel[self[k]];
-    xi[k] = p.x; yi[k] = p.y; zi[k] = p.z; vxi[k] = v.x; vyi[k] = v.y; vzi[k] = v.z;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { A[k][q] = 0.0; J[k][q] = 0.0; }
-  }
-
-  double4 rp, rv;
-  auto load_tile = [&](int tile) {
-    const int j = j0 + tile * TILE + t;
-    if (j < j1) { rp = posm[j]; rv = vel[j]; }
-    else        { rp = make_double4(0.0, 0.0, 0.0, 0.0); rv = make_double4(0.0, 0.0, 0.0, 0.0); }   // zero-mass padding, at rest
-  };
-  auto store_tile = [&](int buf) {
-    double4 q = rp; q.w *= gscale; shp[buf][t] = q; shv[buf][t] = rv;
-  };
-
-  if (ntiles > 0) { load_tile(0); store_tile(0); }
-  __syncthreads();
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const int buf = tile & 1;
-    const bool more = tile + 1 < ntiles;
-    if (more) load_tile(tile + 1);
-    const int jt = j0 + tile * TILE;
-#pragma unroll 2
-    for (int jj = 0; jj < TILE; jj += JB) {
-      double4 pj[JB], vj[JB];
-#pragma unroll
-      for (int b = 0; b < JB; ++b) { pj[b] = shp[buf][jj + b]; vj[b] = shv[buf][jj + b]; }
-      double dx[JB][IPT], dy[JB][IPT], dz[JB][IPT], s2[JB][IPT], ti[JB][IPT];
-#pragma unroll
-      for (int b = 0; b < JB; ++b)
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-          dx[b][k] = pj[b].x - xi[k]; dy[b][k] = pj[b].y - yi[k]; dz[b][k] = pj[b].z - zi[k];
-          if (SOFT) s2[b][k] = fma(dz[b][k], dz[b][k], eps2);
-          else      s2[b][k] = dz[b][k] * dz[b][k];
-          s2[b][k] = fma(dy[b][k], dy[b][k], s2[b][k]);
-          s2[b][k] = fma(dx[b][k], dx[b][k], s2[b][k]);
-        }
-#pragma unroll
-      for (int b = 0; b < JB; ++b)
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-          const double r = rsq_dev(s2[b][k]);
-          ti[b][k] = (s2[b][k] > 0.0 && jt + jj + b != self[k]) ? r : 0.0;
-        }
-#pragma unroll
-      for (int b = 0; b < JB; ++b)
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-          const double wx = vj[b].x - vxi[k], wy = vj[b].y - vyi[k], wz = vj[b].z - vzi[k];
-          const double t2 = ti[b][k] * ti[b][k];
-          const double q = (pj[b].w * ti[b][k]) * t2;
-          double dw = dz[b][k] * wz;
-          dw = fma(dy[b][k], wy, dw);
-          dw = fma(dx[b][k], wx, dw);
-          const double k3 = -3.0 * (dw * t2);
-          const double ux = fma(k3, dx[b][k], wx), uy = fma(k3, dy[b][k], wy), uz = fma(k3, dz[b][k], wz);
-          A[k][0] = fma(q, dx[b][k], A[k][0]); A[k][1] = fma(q, dy[b][k], A[k][1]); A[k][2] = fma(q, dz[b][k], A[k][2]);
-          J[k][0] = fma(q, ux, J[k][0]); J[k][1] = fma(q, uy, J[k][1]); J[k][2] = fma(q, uz, J[k][2]);
-        }
-    }
-    if (more) store_tile(buf ^ 1);
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int k = 0; k < IPT; ++k) {
-    const int il = ibase + t + k * kBlock;
-    if (il < m) {
-      double *row = part + ((size_t)c * m + il) * 6;
-      row[0] = A[k][0]; row[1] = A[k][1]; row[2] = A[k][2]; row[3] = J[k][0]; row[4] = J[k][1]; row[5] = J[k][2];
-    }
-  }
-}
+// (jerk_tile_f64_kernel<SOFT, IPT, LIST>: jerk_tile64.h, shared with the active-set evaluation of kernels_hermite_block.hip)
 
 __global__ __launch_bounds__(kBlock) void jerk_fold_f64_kernel(const double *__restrict__ part, int m, int j_split, double *__restrict__ aj64,
                                                                float *__restrict__ ajf) {
@@ -317,8 +206,9 @@ hipError_t launch_jerk(const JerkLaunch &L, hipStream_t s) {
     for (size_t first = 0; first < (size_t)L.m; first += slab) {
       const int m = (int)std::min(slab, (size_t)L.m - first);
       const dim3 grid((m + kBlock * kJerk64Ipt - 1) / (kBlock * kJerk64Ipt), j_split);
-      hipLaunchKernelGGL((soft ? jerk_tile_f64_kernel<true> : jerk_tile_f64_kernel<false>), grid, dim3(kBlock), 0, s,
-                         (const double4 *)L.posm, (const double4 *)L.vel, (double *)L.part, L.n_total, m, (int)first, j_chunk, L.G, L.eps2);
+      hipLaunchKernelGGL((soft ? jerk_tile_f64_kernel<true, kJerk64Ipt, false> : jerk_tile_f64_kernel<false, kJerk64Ipt, false>), grid, dim3(kBlock), 0, s,
+                         (const double4 *)L.posm, (const double4 *)L.vel, (double *)L.part, L.n_total, m, (int)first, j_chunk, L.G, L.eps2,
+                         (const int *)nullptr);
       hipLaunchKernelGGL(jerk_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
                          L.aj64 ? L.aj64 + 6 * first : nullptr, L.ajf ? L.ajf + 6 * first : nullptr);
     }

@@ -8,7 +8,10 @@ that a kernel that has gained a compile-time switch can be checked to be, in its
 encodings, comments and the padding behind a function are dropped; branch offsets are relative, so identical code compares equal
 wherever it was placed.
 
-    python3 tools/isa_compare.py OLD.o NEW.o [--only SUBSTRING]     # exit code 1 if a pair differs or a kernel has no partner
+A kernel whose template arguments changed otherwise is paired by hand: --pair 'nbody::k<false>=nbody::k<false, 2, false>' (old = new,
+names as this tool prints them).
+
+    python3 tools/isa_compare.py OLD.o NEW.o [--only SUBSTRING] [--pair OLD=NEW ...]   # exit code 1 if a pair differs or a kernel has no partner
 """
 import argparse
 import os
@@ -69,14 +72,18 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--only", default="", help="compare the kernels whose name holds this")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW", help="the NEW kernel of this name is the OLD kernel of that name")
     a = ap.parse_args()
+    renamed = {new: old for old, new in (p.split("=", 1) for p in a.pair)}
     with tempfile.TemporaryDirectory() as t_old, tempfile.TemporaryDirectory() as t_new:
         old = {key_old(k): v for k, v in kernels(a.old, t_old).items() if a.only in k}
         new = {}
         for k, v in kernels(a.new, t_new).items():
             if a.only not in k:
                 continue
-            if key_old(k) in old or base(k)[1] is None:          # the same name on both sides: that pair
+            if key_old(k) in renamed:
+                new[renamed[key_old(k)]] = v
+            elif key_old(k) in old or base(k)[1] is None:        # the same name on both sides: that pair
                 new[key_old(k)] = v
             elif key_new(k) is not None:
                 new[key_new(k)] = v
