@@ -590,6 +590,81 @@ NBODY_AMD_API int nbody_hermite_block_begin(nbody_ctx *ctx, double dt_max, int32
 NBODY_AMD_API int nbody_hermite_block_advance(nbody_ctx *ctx, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out);
 NBODY_AMD_API int nbody_hermite_block_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level);
 
+/*
+ * The snap s = d^2 a / dt^2 and sixth-order Hermite stepping (build-defined: the reference computes neither) — Nitadori & Makino's
+ * shared-step P(EC) scheme.  It still costs ONE O(N^2) pass per step, and buys a given accuracy with fewer of them: on the two-body
+ * orbits of DESIGN 4.13 halving dt divides the error by 64, and the e = 0.9 orbit closes to 2.8e-4 of the semi-major axis in 70 adaptive
+ * steps where nbody_hermite_advance needs 242.
+ *
+ * The snap pass.  With d = x_j - x_i, w = v_j - v_i, b = acc_j - acc_i — acc a per-body INPUT acceleration array —, s^2 = |d|^2 + eps^2,
+ * t = 1 / s, al = (d . w) t^2, be = (w . w + d . b) t^2 + al^2, summed over the other bodies j:
+ *     A_ij = G m_j d t^3      J_ij = G m_j w t^3 - 3 al A_ij      S_ij = G m_j b t^3 - 6 al J_ij - 3 be A_ij
+ * The chunks, the fp64 root and the zero rule are nbody_get_jerk_f64's — t = 0 where s^2 == 0 and for j == i BY INDEX, so a dropped pair
+ * adds exactly 0 to all nine sums; with eps > 0 another body on the same point adds G m t^3 w to the jerk and G m t^3 b to the snap — and so
+ * are the per-pair operations up to A and J.  The a and j of a snap pass therefore equal nbody_get_jerk_f64's IN EVERY BIT, whatever the
+ * input accelerations.  Then, per pair, g_a = fma(-3 be, d_a, fma(2 k3, u_a, b_a)) with the jerk's k3 = -3 al and u_a = fma(k3, d_a, w_a),
+ * and S_a = fma(q, g_a, S_a): one fused chain per sum and chunk in body order, the chunks added from 0.0 in chunk order.
+ *
+ * nbody_get_snap_f64: every body's a, j and s.  Contexts: NBODY_PREC_F64, one device, owning all bodies; NBODY_PREC_F32,
+ *   NBODY_PREC_F32_KAHAN, slice and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED with a message that says why; no particles
+ *   set: NBODY_ERR_STATE.  acc_in: n_total x 3 doubles, acc_in_stride >= 24 bytes apart.  acc_in == NULL: the library first runs the fp64
+ *   jerk pass on the live state and feeds its UNROUNDED accelerations (two passes under NBODY_KERNEL_FORCES) — the result is then the
+ *   physical snap of the current state.  acc, jerk, snap: n_total x 3 doubles each, strides >= 24; any may be NULL, not all three; that,
+ *   and a stride too small, is NBODY_ERR_INVALID.  Synchronises; changes nothing a getter shows and leaves both Hermite caches alone.
+ *
+ * Sixth-order stepping.  Contexts, the "stored (x, v) are SYNCHRONISED" rule and NBODY_ERR_STATE for a pending nbody_step_begin are
+ * nbody_hermite_step's.  One step of length dt, per component, every bracket ONE correctly rounded fp64 operation in the order written
+ * (contraction off); the constants are the host's doubles — d2 = dt dt, c2 = d2 0.5, c3 = (d2 dt) / 6, c4 = (d2 d2) / 24,
+ * c5 = ((d2 d2) dt) / 120, ch = dt 0.5, c10 = d2 / 10, c120 = (d2 dt) / 120, d3 = d2 dt, d4 = d2 d2, d5 = d4 dt:
+ *   predict    xp = ((((x + dt v) + c2 a0) + c3 j0) + c4 s0) + c5 a3                  (xp carries the mass)
+ *              vp = (((v + dt a0) + c2 j0) + c3 s0) + c4 a3                           (vp.w = 0)
+ *              ap = ((a0 + dt j0) + c2 s0) + c3 a3
+ *   evaluate   (a1, j1, s1) = what nbody_get_snap_f64 returns on a context holding (xp, vp) given acc_in = ap: the same kernel, fold
+ *              and geometry
+ *   correct    v1 = v + ((ch (a0 + a1) + c10 (j0 - j1)) + c120 (s0 + s1))
+ *              x1 = x + ((ch (v + v1) + c10 (a0 - a1)) + c120 (j0 + j1))
+ *              R1 = ((a1 - a0) - dt j0) - c2 s0;   R2 = dt ((j1 - j0) - dt s0);   R3 = d2 (s1 - s0)
+ *              X = ((60 R1) - (24 R2)) + (3 R3);   Y = ((168 R2) - (360 R1)) - (24 R3);   Z = ((720 R1) - (360 R2)) + (60 R3)
+ *              a3' = ((X + Y) + 0.5 Z) / d3;   a4' = (Y + Z) / d4;   a5' = Z / d5
+ *   store      x := x1, v := v1 (masses and the velocities' fourth component stay), NBODY_BUF_ACC := (a1, 0)
+ *   cache      (a0, j0, s0) := (a1, j1, s1), a3 := a3', a4 := a4', a5 := a5'
+ * X, Y, Z are dt^3, dt^4, dt^5 times the third to fifth derivative of a at the step's start, from the quintic through both ends; a3', a4',
+ * a5' are the derivatives at its end.
+ *
+ * The cache — a0, j0, s0, a3, a4, a5 and whether they belong to the stored state — is a cache of its OWN beside the fourth-order one, on
+ * the device, allocated at first use, NOT part of a checkpoint.  At a start (the cache invalid) one jerk pass gives a and one snap pass
+ * with that a as its input gives (a0, j0, s0): two passes under NBODY_KERNEL_FORCES; a3, a4, a5 read as zeros until a step has been
+ * taken.  A step thereafter costs ONE snap pass; predictor and corrector together count as one pass under NBODY_KERNEL_UPDATE.
+ * Everything that invalidates the fourth-order cache (the list above) invalidates this one, nbody_hermite_restart forgets both, and the
+ * bound-buffer / handed-out-pointer rule is the same: every CALL evaluates anew at entry.  The two schemes forget each other's cache: a
+ * sixth-order step invalidates the fourth-order cache and ends a block session at a frame end — on a session in mid-frame
+ * nbody_hermite6_step / _timescale / _advance report NBODY_ERR_STATE with a message that says why —, and nbody_hermite_step,
+ * nbody_hermite_advance and nbody_hermite_block_begin invalidate the sixth-order cache.  Checkpoints stay NBDYCKP2 byte for byte:
+ * "nbody_save_checkpoint, nbody_hermite_restart, go on" equals "load, go on" in every byte.
+ *
+ * nbody_hermite6_step: nsteps steps of length dt; steps_done grows by nsteps.  Asynchronous like nbody_step.  dt <= 0 is a no-op that
+ *   returns NBODY_OK; a dt that is not finite or nsteps < 0 is NBODY_ERR_INVALID.
+ * nbody_hermite6_timescale: norms are sqrt((x x + y y) + z z), contraction off.  With derivatives *kind = 1, Nitadori & Makino's
+ *   generalisation of Aarseth's criterion: k_i = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2), 0 / 0 counting as 0, x / 0 as +inf and a
+ *   value that is not finite as +inf; the largest k and the lowest index that attains it come from nbody_jerk_time's fixed-order
+ *   reduction (no atomics); *t_min = 1.0 / cbrt(sqrt(max k)) on the host.  Without, *kind = 0: nbody_jerk_time's value and body from the
+ *   cached (a0, j0).  In both kinds a maximum of 0 gives +inf and one that is not finite 0.  Synchronises; changes nothing a getter
+ *   shows.  Any output may be NULL, not all three (NBODY_ERR_INVALID).
+ * nbody_hermite6_advance: nbody_hermite_advance's loop and rules with dt = min(dt_max, kind == 1 ? eta t : eta_start t).  NOTE: eta
+ *   multiplies t DIRECTLY here — there is no square root, following Nitadori & Makino's convention (t already carries the sixth root) —,
+ *   so sensible values are 0.1 .. 1 where nbody_hermite_advance takes 0.01 .. 0.04.  The host reads 16 bytes per step.  *t_done == t_span
+ *   exactly at the end; a chosen dt that is 0 or not finite stops the call with NBODY_ERR_STATE and a message that names the body.
+ * nbody_hermite6_get: the cache, 18 doubles per body — a0, j0, s0, a3, a4, a5 —, `stride` bytes apart (>= 144, else NBODY_ERR_INVALID).
+ *   NBODY_ERR_STATE while (a0, j0, s0) are invalid; a3, a4, a5 read as zeros while there are no derivatives.  Synchronises.
+ */
+NBODY_AMD_API int nbody_get_snap_f64(nbody_ctx *ctx, const double *acc_in, size_t acc_in_stride, double *acc, size_t acc_stride,
+                                     double *jerk, size_t jerk_stride, double *snap, size_t snap_stride);
+NBODY_AMD_API int nbody_hermite6_step(nbody_ctx *ctx, double dt, int32_t nsteps);
+NBODY_AMD_API int nbody_hermite6_timescale(nbody_ctx *ctx, double *t_min, int32_t *body, int32_t *kind);
+NBODY_AMD_API int nbody_hermite6_advance(nbody_ctx *ctx, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps,
+                                         double *t_done, int64_t *steps);
+NBODY_AMD_API int nbody_hermite6_get(nbody_ctx *ctx, double *d18, size_t stride);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -8,6 +8,7 @@
     python -m parallelnbody_amd --n 2000 --theta 1.0 --eps 5 --steps 600          # Barnes-Hut with every accepted node's term softened
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite --eta 0.02 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite-block --levels 12 --dt 0.05 --steps 20 --energy-every 5
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -47,11 +48,14 @@ def main(argv=None):
     ap.add_argument("--eps", type=float, default=0.0, help="softening length (reference: 0)")
     ap.add_argument("--G", type=float, default=1.0e4, help="gravitational constant (reference: 1e4)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f32_kahan", "f64"])
-    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite", "hermite-block"],
+    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite", "hermite-block", "hermite6"],
                     help="kickdrift: the reference's v += dt a; x += dt v (default).  hermite: the fourth-order Hermite "
                          "predictor-corrector (needs --precision f64, theta = 0): one step of --dt per frame, or with --eta "
                          "adaptive shared steps that cover --dt per frame.  hermite-block: the same scheme with a step per body, "
-                         "--dt 2^-level with level 0 .. --levels chosen by --eta (default 0.02); every frame of --dt ends synchronised")
+                         "--dt 2^-level with level 0 .. --levels chosen by --eta (default 0.02); every frame of --dt ends synchronised"
+                         ".  hermite6: the sixth-order Hermite predictor-corrector on the snap pass (--precision f64, theta = 0), "
+                         "driven like hermite: one step of --dt per frame, or with --eta adaptive shared steps dt = eta t — no "
+                         "square root in this criterion: 0.5 does what 0.01 does for hermite (--eta 0 < eta; without it steps are fixed)")
     ap.add_argument("--levels", type=int, default=None,
                     help="--integrator hermite-block: the deepest level, 0 .. 40 (default 12): the smallest step is --dt 2^-levels")
     ap.add_argument("--eta", type=float, default=None,
@@ -89,6 +93,8 @@ def main(argv=None):
         ap.error("--trajectory-every must be >= 1")
     block = a.integrator == "hermite-block"
     hermite = a.integrator == "hermite" or block
+    six = a.integrator == "hermite6"                                 # the same demands and exclusions as hermite
+    hermite = hermite or six
     if hermite and a.precision != "f64":
         ap.error(f"--integrator {a.integrator} needs --precision f64")
     if hermite and (a.theta or a.leapfrog_start or a.sync_energy):
@@ -133,6 +139,11 @@ def main(argv=None):
                         e.hermite_block_begin(a.dt, 12 if a.levels is None else a.levels, eta=a.eta or 0.02)
                         session.append(True)
                     e.hermite_block_advance(frames)
+            elif six and a.eta is None:
+                e.hermite6_step(a.dt, frames)
+            elif six:
+                for _ in range(frames if a.dt > 0 else 0):
+                    e.hermite6_advance(a.dt, eta=a.eta)
             elif a.eta is None:
                 e.hermite_step(a.dt, frames)
             else:

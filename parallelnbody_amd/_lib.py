@@ -182,6 +182,11 @@ def lib():
     sig("nbody_hermite_block_begin", c_int, vp, c_d, c_i32, c_d, c_d, vp)
     sig("nbody_hermite_block_advance", c_int, vp, c_i64, c_i64, ctypes.POINTER(HermiteBlockStats))
     sig("nbody_hermite_block_get", c_int, vp, vp, vp)
+    sig("nbody_get_snap_f64", c_int, vp, vp, sz, vp, sz, vp, sz, vp, sz)
+    sig("nbody_hermite6_step", c_int, vp, c_d, c_i32)
+    sig("nbody_hermite6_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
+    sig("nbody_hermite6_advance", c_int, vp, c_d, c_d, c_d, c_d, c_i64, dp, ctypes.POINTER(c_i64))
+    sig("nbody_hermite6_get", c_int, vp, vp, sz)
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

@@ -275,6 +275,7 @@ int upload_soa(nbody_ctx *c, const T *posm4, const T *vel4, bool keep_history = 
   c->floor_eps2 = -1.0;
   c->sym_posg_valid = false;
   nbody::hermite_invalidate(c);
+  nbody::hermite6_invalidate(c);
   if (c->bh) nbody::bh_positions_changed(c->bh);                   // the next Barnes-Hut frame looks at the positions for its Size
   if (keep_history) return NBODY_OK;
   c->steps_done = 0;
@@ -617,6 +618,8 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite, c->hblock})
     if (q) (void)hipFree(q);
+  for (void *q : {c->hermite6, c->snap64})
+    if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->clk) (void)hipFree(c->clk);
@@ -644,6 +647,7 @@ int nbody_device_ptr(nbody_ctx *c, int32_t which, void **ptr, size_t *bytes) {
   if (int rc = use_device(c)) return rc;
   c->hm_external = true;                                          // whichever buffer: the caller may write the state from now on
   nbody::hermite_invalidate(c);
+  nbody::hermite6_invalidate(c);
   switch (which) {
     case NBODY_BUF_POSM:
       *ptr = c->posm; if (bytes) *bytes = (size_t)c->p.n_total * c->elem;
@@ -663,6 +667,7 @@ int nbody_bind_device_state(nbody_ctx *c, void *posm, void *vel, void *acc) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->hm_external = true;
   nbody::hermite_invalidate(c);
+  nbody::hermite6_invalidate(c);
   if (posm) {
     if (int rc = posm_escapes(c)) return rc;
     if (c->own_posm) (void)hipFree(c->posm);
@@ -809,6 +814,7 @@ int nbody_step_end(nbody_ctx *c, float dt) {
   c->step_open = false;
   if ((rc = run_update(c, dt > 0.0f ? dt : 0.0f))) return rc;
   if (dt > 0.0f) { c->steps_done += 1; nbody::hermite_invalidate(c); }
+  if (dt > 0.0f) nbody::hermite6_invalidate(c);
   return NBODY_OK;
 }
 
@@ -895,6 +901,7 @@ int nbody_step(nbody_ctx *c, float dt, int32_t nsteps) {
   if (nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_step: nsteps < 0");
   if (!(dt > 0.0f)) return NBODY_OK;   // OctreeSearch.cpp:25: PhDeltaTime <= 0 freezes the physics
   nbody::hermite_invalidate(c);
+  nbody::hermite6_invalidate(c);
   if (c->multi) {
     if (c->theta > 0.0f) {                                        // whole frames on every device, one wait per batch (multi_bh_steps)
       int built = 0;
@@ -1054,6 +1061,7 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
   HIP_TRY(c, hipSetDevice(c->p.device));
   const bool live = dt > 0.0f;                                   // OctreeSearch.cpp:25
   if (live) nbody::hermite_invalidate(c);
+  if (live) nbody::hermite6_invalidate(c);
   // the eps floor of NBODY_ZERO_FLOOR is computed through the same 64-byte scratch the bounds travel in: settle it
   // before the bounds are queued, or the first frame would return the largest mass as Size
   if (live && c->theta == 0.0f && (rc = ensure_floor(c))) return rc;
@@ -1241,6 +1249,7 @@ int nbody_load_checkpoint(nbody_ctx *c, const char *path, int64_t *steps_done) t
   { const int rc2 = f64 ? note_masses(c, (const double *)posm.data()) : note_masses(c, (const float *)posm.data()); if (rc2) return rc2; }
   c->have_state = true; c->floor_eps2 = -1.0; c->step_open = false; c->step_local = false; c->sym_posg_valid = false;
   nbody::hermite_invalidate(c);                                    // (the file holds no derivatives: a resumed run starts from the corrected state)
+  nbody::hermite6_invalidate(c);
   if (c->bh) nbody::bh_positions_changed(c->bh);
   c->steps_done = h.steps_done;
   // Barnes-Hut: the opening angle and the root of the next tree (the previous tree's CoM, OctreeSearch.cpp:77-79) are
@@ -1758,6 +1767,7 @@ int hermite_evaluate(nbody_ctx *c, const void *posm, const void *vel, double *aj
 int hermite_enter(nbody_ctx *c) {
   if (int rc = hermite_ensure(c)) return rc;
   if (c->hm_external) nbody::hermite_invalidate(c);
+  if (c->hm_external) nbody::hermite6_invalidate(c);
   if (c->hm_valid) return NBODY_OK;
   if (int rc = hermite_evaluate(c, c->posm, c->vel, hermite_bufs(c).aj[c->hm_cur])) return rc;
   c->hm_valid = true;
@@ -1805,6 +1815,7 @@ int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite_step"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
+  nbody::hermite6_invalidate(c);                                   // (the state moves on without the sixth-order cache)
   for (int s = 0; s < nsteps; ++s)
     if ((rc = hermite_one_step(c, dt))) return rc;
   return NBODY_OK;
@@ -1838,6 +1849,7 @@ int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_st
   if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite_advance"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
+  nbody::hermite6_invalidate(c);
   const double root_eta = std::sqrt(eta);
   while (t_acc < t_span && taken < max_steps) {
     double t = 0.0;
@@ -1885,6 +1897,7 @@ int nbody_hermite_restart(nbody_ctx *c) {
   int rc = hermite_ready(c, "nbody_hermite_restart");
   if (rc) return rc;
   nbody::hermite_invalidate(c);
+  nbody::hermite6_invalidate(c);
   return NBODY_OK;
 }
 
@@ -1992,6 +2005,7 @@ int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, doubl
         return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
   if ((rc = hermite_block_leave(c, "nbody_hermite_block_begin"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
+  nbody::hermite6_invalidate(c);
   if (!c->hblock) HIP_TRY(c, hipMalloc(&c->hblock, hermite_block_bytes(n)));
   c->hb.levels = levels; c->hb.dt_max = dt_max; c->hb.tick = tick; c->hb.root_eta = std::sqrt(eta);
   c->hb.lanes = nbody::env_int("NBODY_HERMITE_BLOCK_LANES", 0);
@@ -2225,6 +2239,220 @@ int nbody_get_launch_config(nbody_ctx *c, int32_t *tile, int32_t *i_per_thread, 
   if (j_split) *j_split = c->j_split;
   if (blocks) *blocks = b;
   if (threads) *threads = t;
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- the snap and sixth-order Hermite stepping of fp64 contexts: predictor, the fp64 snap pass on the predicted state, corrector (kernels_snap.hip) ----
+namespace {
+// where the snap exists: fp64 state, one device, all bodies
+int snap_supported(nbody_ctx *c, const char *who) {
+  if (c->p.precision != NBODY_PREC_F64)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): the snap's pair term "
+                "takes differences of accelerations, which need fp64 state; create the context with NBODY_PREC_F64", who);
+  if (c->p.i_count != c->p.n_total)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
+  return NBODY_OK;
+}
+
+// (a, j, s) of the bodies at (posm, vel) given the input accelerations ain — the live state or the predicted one — into ajs64, queued as
+// one pass under NBODY_KERNEL_FORCES: the kernel, fold and geometry (a function of n_total alone) of nbody_get_snap_f64
+// a pass is never queued into a staging area that does not hold its partial rows
+int probe_part_holds(nbody_ctx *c, int width, const char *what) {
+  const size_t need = nbody::probe_part_elems(c->p.n_total, c->p.n_total, width);
+  if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
+  return fail(c, NBODY_ERR_STATE, "%s: the partial rows need %zu float4, the staging area holds %zu", what, need, c->probe_part_elems);
+}
+
+int snap_evaluate(nbody_ctx *c, const void *posm, const void *vel, const double *ain, int ain_stride, double *ajs64) {
+  if (int rc = probe_part_holds(c, nbody::kSnapRowWidth, "the snap pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::SnapLaunch L;
+    L.posm = posm; L.vel = vel; L.ain = ain; L.ain_stride = ain_stride; L.part = c->probe_part; L.ajs64 = ajs64;
+    L.n_total = c->p.n_total; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, nbody::launch_snap(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+struct Hermite6Bufs { double *xp, *vp, *ap, *a3, *a4, *a5, *ajs[2], *partials; };
+Hermite6Bufs hermite6_bufs(const nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  double *b = (double *)c->hermite6;
+  return Hermite6Bufs{b, b + 4 * n, b + 8 * n, b + 12 * n, b + 16 * n, b + 20 * n, {b + 24 * n, b + 33 * n}, b + 42 * n};
+}
+
+// what every sixth-order call does at entry: the cache and the partial rows at first use; once somebody else may write the state, nothing
+// cached is believed; then (a0, j0, s0) of the stored (x, v) — one jerk pass for a, one snap pass with that a as its input — and zeros
+// for a3, a4, a5
+int hermite6_enter(nbody_ctx *c) {
+  const size_t n = (size_t)c->p.n_total;
+  if (!c->hermite6) HIP_TRY(c, hipMalloc(&c->hermite6, (42 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
+  // the partial rows of BOTH passes a start runs: the staging area only grows, and neither width's need covers the other's (the slabs
+  // are whole multiples of 1024 points: at N = 65536 the jerk pass's rows take 16 515 072 float4, the snap pass's 16 384 000)
+  if (int rc = ensure_probe_part(c, (int)n, 3)) return rc;
+  if (int rc = ensure_probe_part(c, (int)n, nbody::kSnapRowWidth)) return rc;
+  if (c->hm_external) { nbody::hermite_invalidate(c); nbody::hermite6_invalidate(c); }
+  if (c->h6_valid) return NBODY_OK;
+  const Hermite6Bufs b = hermite6_bufs(c);
+  double *aj = b.ajs[c->h6_cur ^ 1];                              // (the jerk pass's six doubles per body, in the row a step overwrites)
+  if (int rc = probe_part_holds(c, 3, "the jerk pass of a sixth-order start")) return rc;
+  if (int rc = hermite_evaluate(c, c->posm, c->vel, aj)) return rc;
+  if (int rc = snap_evaluate(c, c->posm, c->vel, aj, 6, b.ajs[c->h6_cur])) return rc;
+  HIP_TRY(c, hipMemsetAsync(b.a3, 0, 12 * n * sizeof(double), c->stream));
+  c->h6_valid = true;
+  c->h6_derivs = false;
+  return NBODY_OK;
+}
+
+// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE
+int hermite6_one_step(nbody_ctx *c, double dt) {
+  const Hermite6Bufs b = hermite6_bufs(c);
+  nbody::Hermite6Launch L;
+  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.ap = b.ap; L.ajs0 = b.ajs[c->h6_cur]; L.ajs1 = b.ajs[c->h6_cur ^ 1];
+  L.a3 = b.a3; L.a4 = b.a4; L.a5 = b.a5; L.n = c->p.n_total; L.dt = dt;
+  int rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_predict(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  if ((rc = snap_evaluate(c, b.xp, b.vp, b.ap, 4, b.ajs[c->h6_cur ^ 1]))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_correct(L, c->stream)); return NBODY_OK; }))) return rc;
+  c->h6_cur ^= 1;                                                  // (a0, j0, s0) := (a1, j1, s1)
+  c->h6_derivs = true;
+  nbody::hermite_invalidate(c);                                    // the fourth-order cache is not this state's
+  c->sym_posg_valid = false;
+  c->steps_done += 1;
+  return NBODY_OK;
+}
+
+// the time scale of the cached derivatives, waited for: *t from the largest criterion value, *body where, *kind which criterion
+int hermite6_scale(nbody_ctx *c, double *t, int32_t *body, int32_t *kind) {
+  const Hermite6Bufs b = hermite6_bufs(c);
+  HIP_TRY(c, nbody::launch_hermite6_time(b.ajs[c->h6_cur], b.a3, b.a4, b.a5, c->p.n_total, c->h6_derivs, b.partials, (double *)c->scratch, c->stream));
+  double k = 0.0, at = 0.0;
+  if (int rc = read_energy(c, &k, &at)) return rc;                // (the scratch's two doubles: the largest k, its body)
+  if (k == 0.0) *t = HUGE_VAL;
+  else if (!std::isfinite(k)) *t = 0.0;
+  else *t = c->h6_derivs ? 1.0 / std::cbrt(std::sqrt(k)) : 1.0 / std::sqrt(k);
+  *body = (int32_t)at;
+  *kind = c->h6_derivs ? 1 : 0;
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_get_snap_f64(nbody_ctx *c, const double *acc_in, size_t acc_in_stride, double *acc, size_t acc_stride, double *jerk,
+                       size_t jerk_stride, double *snap, size_t snap_stride) {
+  const char *who = "nbody_get_snap_f64";
+  if (c && c->multi) return multi_unsupported(c, who);
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = snap_supported(c, who))) return rc;
+  if ((!acc && !jerk && !snap) || (acc_in && acc_in_stride < 24) || (acc && acc_stride < 24) || (jerk && jerk_stride < 24) || (snap && snap_stride < 24))
+    return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null, or a stride < 24", who);
+  const size_t n = (size_t)c->p.n_total, rec = 9 * sizeof(double);
+  if ((rc = ensure_stage(c, n * rec))) return rc;
+  if (!c->snap64) HIP_TRY(c, hipMalloc(&c->snap64, 13 * n * sizeof(double)));
+  if ((rc = ensure_probe_part(c, (int)n, nbody::kSnapRowWidth))) return rc;
+  double *ajs = (double *)c->snap64, *ain = ajs + 9 * n;
+  int ain_stride = 4;
+  if (acc_in) {
+    double *h = (double *)c->h_stage;
+    for (size_t i = 0; i < n; ++i) { memcpy(h + 4 * i, (const char *)acc_in + i * acc_in_stride, 24); h[4 * i + 3] = 0.0; }
+    HIP_TRY(c, hipMemcpyAsync(ain, h, n * 32, hipMemcpyHostToDevice, c->stream));
+  } else {                                                         // the live state's own accelerations, unrounded: the fp64 jerk pass first
+    if ((rc = ensure_jerk64(c))) return rc;
+    if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
+    ain = (double *)c->jerk64; ain_stride = 6;
+  }
+  if ((rc = snap_evaluate(c, c->posm, c->vel, ain, ain_stride, ajs))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, ajs, n * rec, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (acc) scatter_records(acc, acc_stride, c->h_stage, 24, n, rec);
+  if (jerk) scatter_records(jerk, jerk_stride, (const char *)c->h_stage + 24, 24, n, rec);
+  if (snap) scatter_records(snap, snap_stride, (const char *)c->h_stage + 48, 24, n, rec);
+  return NBODY_OK;
+}
+
+int nbody_hermite6_step(nbody_ctx *c, double dt, int32_t nsteps) {
+  int rc = hermite_ready(c, "nbody_hermite6_step");
+  if (rc) return rc;
+  if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_step: dt is not finite, or nsteps < 0");
+  if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
+  if ((rc = hermite_block_leave(c, "nbody_hermite6_step"))) return rc;
+  if ((rc = hermite6_enter(c))) return rc;
+  for (int s = 0; s < nsteps; ++s)
+    if ((rc = hermite6_one_step(c, dt))) return rc;
+  return NBODY_OK;
+}
+
+int nbody_hermite6_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t *kind) {
+  int rc = hermite_ready(c, "nbody_hermite6_timescale");
+  if (rc) return rc;
+  if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_timescale: all three outputs are null");
+  if ((rc = hermite_block_leave(c, "nbody_hermite6_timescale"))) return rc;
+  if ((rc = hermite6_enter(c))) return rc;
+  double t = 0.0;
+  int32_t at = 0, which = 0;
+  if ((rc = hermite6_scale(c, &t, &at, &which))) return rc;
+  if (t_min) *t_min = t;
+  if (body) *body = at;
+  if (kind) *kind = which;
+  return NBODY_OK;
+}
+
+int nbody_hermite6_advance(nbody_ctx *c, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps, double *t_done,
+                           int64_t *steps) {
+  int rc = hermite_ready(c, "nbody_hermite6_advance");
+  if (rc) return rc;
+  if (!(eta > 0.0) || !(eta_start > 0.0) || !(dt_max > 0.0) || !(t_span >= 0.0) || !std::isfinite(t_span) || max_steps < 0)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_advance: eta, eta_start and dt_max must be > 0, t_span >= 0 and finite, max_steps >= 0");
+  double t_acc = 0.0;
+  int64_t taken = 0;
+  if (t_done) *t_done = 0.0;
+  if (steps) *steps = 0;
+  if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
+  if ((rc = hermite_block_leave(c, "nbody_hermite6_advance"))) return rc;
+  if ((rc = hermite6_enter(c))) return rc;
+  while (t_acc < t_span && taken < max_steps) {
+    double t = 0.0;
+    int32_t at = 0, which = 0;
+    if ((rc = hermite6_scale(c, &t, &at, &which))) return rc;
+    double dt = std::min(dt_max, which == 1 ? eta * t : eta_start * t);   // (eta times t itself: no square root in this criterion)
+    const double rest = t_span - t_acc;
+    const bool last = dt >= rest;
+    if (last) dt = rest;
+    if (!(dt > 0.0) || !std::isfinite(dt))
+      return fail(c, NBODY_ERR_STATE, "nbody_hermite6_advance: the time scale of body %d gives dt = %g after %lld steps (t = %.17g); the "
+                  "state is that of the last good step", (int)at, dt, (long long)taken, t_acc);
+    if ((rc = hermite6_one_step(c, dt))) return rc;
+    t_acc = last ? t_span : t_acc + dt;
+    taken += 1;
+    if (t_done) *t_done = t_acc;
+    if (steps) *steps = taken;
+  }
+  return NBODY_OK;
+}
+
+int nbody_hermite6_get(nbody_ctx *c, double *d18, size_t stride) {
+  int rc = hermite_ready(c, "nbody_hermite6_get");
+  if (rc) return rc;
+  if (!d18 || stride < 144) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_get: null buffer or stride < 144");
+  if (!c->hermite6 || !c->h6_valid)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_get: no derivatives cached for the stored state (nbody_hermite6_step or nbody_hermite6_timescale first)");
+  const size_t n = (size_t)c->p.n_total;
+  const Hermite6Bufs b = hermite6_bufs(c);
+  if ((rc = ensure_stage(c, n * 168))) return rc;
+  double *h_ajs = (double *)c->h_stage, *h_d = h_ajs + 9 * n;     // (a3, a4 and a5 lie side by side: 12 doubles per body in all)
+  HIP_TRY(c, hipMemcpyAsync(h_ajs, b.ajs[c->h6_cur], n * 72, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_d, b.a3, n * 96, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i) {
+    double rec[18];
+    memcpy(rec, h_ajs + 9 * i, 72);
+    for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * n + i), 24);   // (zeros until a step has been taken)
+    memcpy((char *)d18 + i * stride, rec, 144);
+  }
   return NBODY_OK;
 }
 

@@ -105,6 +105,15 @@ struct nbody_ctx {
   bool hm_valid = false;       // (a0, j0) are those of the stored (x, v)
   bool hm_derivs = false;      // a2, a3 are those a step left at the stored state
   bool hm_external = false;    // a buffer was bound or a pointer handed out: somebody else may write the state, every call evaluates anew
+  // sixth-order Hermite stepping (nbody_hermite6_*, kernels_snap.hip; fp64 contexts): a cache of its own, allocated at first use.
+  // hermite6 holds, in doubles, xp, vp, ap, a3, a4, a5 ([n_total] double4 each), two rows of (a, j, s) ([n_total][9] each: h6_cur is
+  // (a0, j0, s0), the other takes the predicted state's — and, at a start, the jerk pass's [n_total][6]), then the reduction's workgroup
+  // pairs.  hm_external rules this cache as it rules the fourth-order one.
+  void *hermite6 = nullptr;
+  int h6_cur = 0;
+  bool h6_valid = false;       // (a0, j0, s0) are those of the stored (x, v)
+  bool h6_derivs = false;      // a3, a4, a5 are those a step left at the stored state (zeros otherwise)
+  void *snap64 = nullptr;      // nbody_get_snap_f64: [n_total][9] double, the bodies' (a, j, s), then [n_total] double4, the input accelerations
   // Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip): a session on the cache above.  hblock, allocated at the
   // first begin: T [n] int64, the scheduler's segment minima [slots] int64, the record (T_next, m) and the floor-hit count (int64 each),
   // then level [n], list [n] and the segment counts [slots] as int32
@@ -153,6 +162,9 @@ inline int use_device(nbody_ctx *c) {
 // The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): the
 // cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3; a block session ends.
 inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; c->hb.active = false; }
+// The same for the sixth-order cache, which every caller of hermite_invalidate forgets as well — and so do the fourth-order calls that
+// step the state (nbody_hermite_step, nbody_hermite_advance, nbody_hermite_block_begin), whose cache a sixth-order step forgets in turn.
+inline void hermite6_invalidate(nbody_ctx *c) { c->h6_valid = false; c->h6_derivs = false; }
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
 constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain

@@ -220,6 +220,47 @@ hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_
 hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first, int m, int lanes, hipStream_t s);
 hipError_t launch_hermite_block_correct(const HermiteBlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
 
+// The snap s = d^2 a / dt^2 beside the acceleration and the jerk of an fp64 state, the bodies only — kernels_snap.hip: with d = x_j - x_i,
+// w = v_j - v_i, b = ain_j - ain_i (ain: a per-body INPUT acceleration), s^2 = |d|^2 + eps2, t = 1 / s, al = (d . w) t^2,
+// be = (w . w + d . b) t^2 + al^2:  A = G m_j d t^3,  J = G m_j w t^3 - 3 al A,  S = G m_j b t^3 - 6 al J - 3 be A, summed over j != i.
+// The chunks, tiles, rsq, zero rule and — up to A and J — the per-pair operations are launch_jerk's on fp64 state, so a body's a and j
+// are launch_jerk's in every bit whatever ain holds.  A partial row is nine doubles per body: probe_slab_points(n_total, kSnapRowWidth).
+constexpr int kSnapRowWidth = 5;   // the float4 that hold nine doubles
+struct SnapLaunch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *vel = nullptr;    // [n_total] double4: vx, vy, vz, unused
+  const double *ain = nullptr;  // body i's input acceleration: ain[i * ain_stride + 0 .. 2]
+  int ain_stride = 0;           // in doubles, >= 3 (4: double4 rows; 6: launch_jerk's aj64)
+  void *part = nullptr;         // [probe_part_elems(n_total, n_total, kSnapRowWidth)] float4
+  double *ajs64 = nullptr;      // [n_total][9]: ax, ay, az, jx, jy, jz, sx, sy, sz
+  int n_total = 0;
+  double G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_snap(const SnapLaunch &L, hipStream_t s);
+
+// Sixth-order Hermite stepping of an fp64 state (Nitadori & Makino) — kernels_snap.hip: the predictor and the corrector around one
+// launch_snap on the predicted state with the predicted accelerations as its input (the caller's to queue in between), one lane per
+// body, every operation one correctly rounded fp64 operation.
+//   launch_hermite6_predict: (xp, vp, ap) = the Taylor series of x, v, a to a3 (fifth, fourth, third order in dt); xp.w = m, vp.w = ap.w = 0
+//   launch_hermite6_correct: (x, v) := the corrected state from (a0, j0, s0) and (a1, j1, s1), acc := (a1, 0), (a3, a4, a5) := the third
+//     to fifth derivative of a at the new time, from the quintic through both ends
+// ajs0 / ajs1 are launch_snap's rows, nine doubles per body.
+struct Hermite6Launch {
+  void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state (predict reads posm and vel)
+  void *xp = nullptr, *vp = nullptr, *ap = nullptr;       // [n] double4 each: the predicted state and its predicted accelerations
+  const double *ajs0 = nullptr, *ajs1 = nullptr;          // [n][9]: (a, j, s) at the stored state / at the predicted one
+  void *a3 = nullptr, *a4 = nullptr, *a5 = nullptr;       // [n] double4 each (predict reads a3)
+  int n = 0;
+  double dt = 0.0;
+};
+hipError_t launch_hermite6_predict(const Hermite6Launch &L, hipStream_t s);
+hipError_t launch_hermite6_correct(const Hermite6Launch &L, hipStream_t s);
+// out[0] = max over the n bodies of k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2), norms sqrt((x x + y y) + z z) — derivs == false:
+// launch_jerk_time's k = |j0|^2 / |a0|^2 — (0 / 0 counts as 0, x / 0 and every value that is not finite as +inf), out[1] = the lowest
+// index that attains it, as a double: launch_jerk_time's reduction and its `partials`.
+hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *a4, const void *a5, int n, bool derivs, double *partials,
+                                double *out, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

@@ -1,0 +1,347 @@
+// The snap s = d^2 a / dt^2 of the pair law beside the acceleration and the jerk, and sixth-order Hermite stepping on it (nbody_get_snap_f64,
+// nbody_hermite6_step, nbody_hermite6_timescale, nbody_hermite6_advance, nbody_hermite6_get; build-defined: the reference computes none).
+// fp64 state, the bodies only.  With d = x_j - x_i, w = v_j - v_i, b = acc_j - acc_i (acc: a per-body INPUT array), s^2 = |d|^2 + eps^2,
+// t = 1 / s, al = (d . w) t^2, be = (w . w + d . b) t^2 + al^2:
+//     A_ij = G m_j d t^3      J_ij = G m_j w t^3 - 3 al A_ij      S_ij = G m_j b t^3 - 6 al J_ij - 3 be A_ij
+//   snap_tile_f64_kernel    <- shaped like jerk_tile_f64_kernel (jerk_tile64.h, which this file neither includes nor changes): its chunks,
+//                              its tiles, its rsq, its zero rule and, up to A and J, its operations in its order — so the A and J of a snap
+//                              pass are nbody_get_jerk_f64's in every bit; a third pair of LDS tiles holds the input accelerations
+//   snap_fold_f64_kernel    <- the chunks' rows, nine doubles per body, added in chunk order
+//   hermite6_predict_kernel <- (xp, vp, ap) from (x, v, a0, j0, s0, a3): the Taylor series to fifth / fourth / third order
+//   hermite6_correct_kernel <- (x, v) from (a0, j0, s0) and the (a1, j1, s1) of the predicted state; the stored acceleration; a3, a4, a5
+//                              at the new time, from the quintic through both ends
+//   hermite6_time_*_kernel  <- k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2) per body — without derivatives |j0|^2 / |a0|^2 —, its
+//                              maximum and that body, folded in a fixed order (point_tile.h: tidal_max_*)
+// Contraction is off for the whole file: every fused multiply-add of the tile loop is written out as fma(), and EVERY operation of the
+// stepping kernels is one correctly rounded fp64 operation in the order the comments write it, so that numpy reproduces a step in
+// every bit from the (a, j, s) of nbody_get_snap_f64 (tests/hermite6_ref.py).  No scratch, no atomics, no grid-wide waits.
+#include "kernels.h"
+
+#include <algorithm>
+
+#include "point_tile.h"
+
+#pragma clang fp contract(off)
+
+namespace nbody {
+
+namespace {
+
+constexpr int kSnapTile = 256;
+constexpr int kSnapJb = 2;      // j-bodies per staged group
+#ifndef NBODY_SNAP_IPT
+#define NBODY_SNAP_IPT 2        // (an A/B build may say 1: make variant NAME=ipt1 EXTRA=-DNBODY_SNAP_IPT=1)
+#endif
+constexpr int kSnapIpt = NBODY_SNAP_IPT;   // bodies per lane (profiles/hermite6_kernel_resources.txt)
+static_assert(kSnapIpt == 1 || kSnapIpt == 2, "one or two bodies per lane");
+
+// 1 / sqrt(x) as every fp64 pair kernel here forms it: the v_rsq_f64 seed and one third-order step
+__device__ __forceinline__ double snap_rsq_dev(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double e = fma(-(x * y), y, 1.0);
+  const double q = e * fma(e, 0.375, 0.5);
+  return fma(y, q, y);
+}
+
+__device__ __forceinline__ double4 load_ain(const double *__restrict__ ain, int stride, int i) {
+  const double *r = ain + (size_t)i * stride;
+  return make_double4(r[0], r[1], r[2], 0.0);
+}
+
+// A, J and S of IPT bodies per lane from all bodies of chunk blockIdx.y: local body il = blockIdx.x * (kBlock * IPT) + t + k * kBlock
+// (the lanes past m repeat body m - 1 and write nothing) is body i_first + il.  The bodies go through double-buffered LDS tiles as
+// (x, y, z, G m), (vx, vy, vz, -) and (ax, ay, az, -): 48 KB.  ain holds body i's input acceleration at ain[i * ain_stride + 0 .. 2].
+// Per pair, s2 = fma(dx, dx, fma(dy, dy, dz * dz [+ eps^2])), t = rsq(s2) — 0 where s2 == 0 and for j == the body itself by index —, then
+//   t2 = t * t;  q = (G m * t) * t2;  dw = fma(dx, wx, fma(dy, wy, dz * wz));  k3 = -3 * (dw * t2);  u_a = fma(k3, d_a, w_a)
+//   A_a = fma(q, d_a, A_a);  J_a = fma(q, u_a, J_a)                                        (the jerk kernel's, in its order)
+//   ww = fma(wx, wx, fma(wy, wy, wz * wz));  db = fma(dx, bx, fma(dy, by, dz * bz));  al = dw * t2;  be = fma(al, al, (ww + db) * t2)
+//   k6 = 2 * k3;  m3 = -3 * be;  g_a = fma(m3, d_a, fma(k6, u_a, b_a));  S_a = fma(q, g_a, S_a)
+// — one chain per sum and chunk of probe_geometry, in body order.  A dropped pair has q = 0 and finite factors: it adds exactly 0 to
+// all nine sums; so does the zero-mass padding (at rest on the origin, unaccelerated).  A chunk's row is nine doubles per local body:
+// part[(c * m + il) * 9].
+template <bool SOFT, int IPT>
+__global__ __launch_bounds__(kBlock) void snap_tile_f64_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
+                                                               const double *__restrict__ ain, int ain_stride,
+                                                               double *__restrict__ part, int n_total, int m, int i_first, int j_chunk,
+                                                               double gscale, double eps2) {
+  constexpr int JB = kSnapJb, TILE = kSnapTile;
+  static_assert(TILE == kBlock, "a lane stages one body per tile");
+  __shared__ double4 shp[2][TILE], shv[2][TILE], sha[2][TILE];
+
+  const int t = threadIdx.x;
+  const int ibase = blockIdx.x * (kBlock * IPT);
+  const int c = blockIdx.y;
+  const int j0 = c * j_chunk;
+  const int j1 = min(j0 + j_chunk, n_total);
+  const int ntiles = (j1 > j0) ? (j1 - j0 + TILE - 1) / TILE : 0;
+
+  double xi[IPT], yi[IPT], zi[IPT], vxi[IPT], vyi[IPT], vzi[IPT], axi[IPT], ayi[IPT], azi[IPT];
+  int self[IPT];
+  double A[IPT][3], J[IPT][3], S[IPT][3];
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    self[k] = i_first + min(ibase + t + k * kBlock, m - 1);
+    const double4 p = posm[self[k]], v = vel[self[k]], a = load_ain(ain, ain_stride, self[k]);
+    xi[k] = p.x; yi[k] = p.y; zi[k] = p.z; vxi[k] = v.x; vyi[k] = v.y; vzi[k] = v.z; axi[k] = a.x; ayi[k] = a.y; azi[k] = a.z;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { A[k][q] = 0.0; J[k][q] = 0.0; S[k][q] = 0.0; }
+  }
+
+  double4 rp, rv, ra;
+  auto load_tile = [&](int tile) {
+    const int j = j0 + tile * TILE + t;
+    if (j < j1) { rp = posm[j]; rv = vel[j]; ra = load_ain(ain, ain_stride, j); }
+    else        { rp = make_double4(0.0, 0.0, 0.0, 0.0); rv = rp; ra = rp; }   // zero-mass padding, at rest, unaccelerated
+  };
+  auto store_tile = [&](int buf) {
+    double4 q = rp; q.w *= gscale; shp[buf][t] = q; shv[buf][t] = rv; sha[buf][t] = ra;
+  };
+
+  if (ntiles > 0) { load_tile(0); store_tile(0); }
+  __syncthreads();
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int buf = tile & 1;
+    const bool more = tile + 1 < ntiles;
+    if (more) load_tile(tile + 1);
+    const int jt = j0 + tile * TILE;
+#pragma unroll 2
+    for (int jj = 0; jj < TILE; jj += JB) {
+      double4 pj[JB], vj[JB], aj[JB];
+#pragma unroll
+      for (int b = 0; b < JB; ++b) { pj[b] = shp[buf][jj + b]; vj[b] = shv[buf][jj + b]; aj[b] = sha[buf][jj + b]; }
+      double dx[JB][IPT], dy[JB][IPT], dz[JB][IPT], s2[JB][IPT], ti[JB][IPT];
+#pragma unroll
+      for (int b = 0; b < JB; ++b)
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+          dx[b][k] = pj[b].x - xi[k]; dy[b][k] = pj[b].y - yi[k]; dz[b][k] = pj[b].z - zi[k];
+          if (SOFT) s2[b][k] = fma(dz[b][k], dz[b][k], eps2);
+          else      s2[b][k] = dz[b][k] * dz[b][k];
+          s2[b][k] = fma(dy[b][k], dy[b][k], s2[b][k]);
+          s2[b][k] = fma(dx[b][k], dx[b][k], s2[b][k]);
+        }
+#pragma unroll
+      for (int b = 0; b < JB; ++b)
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+          const double r = snap_rsq_dev(s2[b][k]);
+          ti[b][k] = (s2[b][k] > 0.0 && jt + jj + b != self[k]) ? r : 0.0;
+        }
+#pragma unroll
+      for (int b = 0; b < JB; ++b)
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+          const double wx = vj[b].x - vxi[k], wy = vj[b].y - vyi[k], wz = vj[b].z - vzi[k];
+          const double t2 = ti[b][k] * ti[b][k];
+          const double q = (pj[b].w * ti[b][k]) * t2;
+          double dw = dz[b][k] * wz;
+          dw = fma(dy[b][k], wy, dw);
+          dw = fma(dx[b][k], wx, dw);
+          const double k3 = -3.0 * (dw * t2);
+          const double ux = fma(k3, dx[b][k], wx), uy = fma(k3, dy[b][k], wy), uz = fma(k3, dz[b][k], wz);
+          A[k][0] = fma(q, dx[b][k], A[k][0]); A[k][1] = fma(q, dy[b][k], A[k][1]); A[k][2] = fma(q, dz[b][k], A[k][2]);
+          J[k][0] = fma(q, ux, J[k][0]); J[k][1] = fma(q, uy, J[k][1]); J[k][2] = fma(q, uz, J[k][2]);
+          const double bx = aj[b].x - axi[k], by = aj[b].y - ayi[k], bz = aj[b].z - azi[k];
+          const double ww = fma(wx, wx, fma(wy, wy, wz * wz));
+          const double db = fma(dx[b][k], bx, fma(dy[b][k], by, dz[b][k] * bz));
+          const double al = dw * t2;
+          const double be = fma(al, al, (ww + db) * t2);
+          const double k6 = 2.0 * k3;
+          const double m3 = -3.0 * be;
+          const double gx = fma(m3, dx[b][k], fma(k6, ux, bx)), gy = fma(m3, dy[b][k], fma(k6, uy, by)),
+                       gz = fma(m3, dz[b][k], fma(k6, uz, bz));
+          S[k][0] = fma(q, gx, S[k][0]); S[k][1] = fma(q, gy, S[k][1]); S[k][2] = fma(q, gz, S[k][2]);
+        }
+    }
+    if (more) store_tile(buf ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int il = ibase + t + k * kBlock;
+    if (il < m) {
+      double *row = part + ((size_t)c * m + il) * 9;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) { row[q] = A[k][q]; row[3 + q] = J[k][q]; row[6 + q] = S[k][q]; }
+    }
+  }
+}
+
+// (a, j, s)[k] from the chunks' rows: the nine sums added from 0.0 in chunk order (no atomics: the same bits every time)
+__global__ __launch_bounds__(kBlock) void snap_fold_f64_kernel(const double *__restrict__ part, int m, int j_split, double *__restrict__ ajs64) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= m) return;
+  double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int c = 0; c < j_split; ++c) {
+    const double *row = part + ((size_t)c * m + k) * 9;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) s[q] = s[q] + row[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 9; ++q) ajs64[(size_t)k * 9 + q] = s[q];
+}
+
+// ---- sixth-order Hermite stepping: one lane per body ----
+
+// a body's (a, j, s) in the snap fold's rows: nine doubles, 72 bytes apart
+struct Ajs { double a[3], j[3], s[3]; };
+__device__ __forceinline__ Ajs load_ajs(const double *__restrict__ ajs, int i) {
+  const double *r = ajs + 9 * (size_t)i;
+  return Ajs{{r[0], r[1], r[2]}, {r[3], r[4], r[5]}, {r[6], r[7], r[8]}};
+}
+
+// per component  xp = ((((x + dt v) + c2 a0) + c3 j0) + c4 s0) + c5 a3;  vp = (((v + dt a0) + c2 j0) + c3 s0) + c4 a3;
+// ap = ((a0 + dt j0) + c2 s0) + c3 a3;  xp.w = m, vp.w = 0, ap.w = 0
+struct Hermite6PredictConsts { double dt, c2, c3, c4, c5; };
+__global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
+                                                                  const double *__restrict__ ajs0, const double4 *__restrict__ a3,
+                                                                  double4 *__restrict__ xp, double4 *__restrict__ vp,
+                                                                  double4 *__restrict__ ap, int n, Hermite6PredictConsts k) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double4 x = posm[i], v = vel[i], d3 = a3[i];
+  const Ajs s = load_ajs(ajs0, i);
+  auto px = [&](double xc, double vc, double a, double j, double sn, double c) {
+    return ((((xc + k.dt * vc) + k.c2 * a) + k.c3 * j) + k.c4 * sn) + k.c5 * c;
+  };
+  auto pv = [&](double vc, double a, double j, double sn, double c) { return (((vc + k.dt * a) + k.c2 * j) + k.c3 * sn) + k.c4 * c; };
+  auto pa = [&](double a, double j, double sn, double c) { return ((a + k.dt * j) + k.c2 * sn) + k.c3 * c; };
+  xp[i] = make_double4(px(x.x, v.x, s.a[0], s.j[0], s.s[0], d3.x), px(x.y, v.y, s.a[1], s.j[1], s.s[1], d3.y),
+                       px(x.z, v.z, s.a[2], s.j[2], s.s[2], d3.z), x.w);
+  vp[i] = make_double4(pv(v.x, s.a[0], s.j[0], s.s[0], d3.x), pv(v.y, s.a[1], s.j[1], s.s[1], d3.y), pv(v.z, s.a[2], s.j[2], s.s[2], d3.z), 0.0);
+  ap[i] = make_double4(pa(s.a[0], s.j[0], s.s[0], d3.x), pa(s.a[1], s.j[1], s.s[1], d3.y), pa(s.a[2], s.j[2], s.s[2], d3.z), 0.0);
+}
+
+// per component, with (a1, j1, s1) the snap pass's answer at (xp, vp) given ap:
+//   v1 = v + ((ch (a0 + a1) + c10 (j0 - j1)) + c120 (s0 + s1));   x1 = x + ((ch (v + v1) + c10 (a0 - a1)) + c120 (j0 + j1))
+//   R1 = ((a1 - a0) - dt j0) - c2 s0;   R2 = dt ((j1 - j0) - dt s0);   R3 = d2 (s1 - s0)
+//   X = ((60 R1) - (24 R2)) + (3 R3);   Y = ((168 R2) - (360 R1)) - (24 R3);   Z = ((720 R1) - (360 R2)) + (60 R3)
+//   a3 = ((X + Y) + 0.5 Z) / d3;   a4 = (Y + Z) / d4;   a5 = Z / d5
+// x := x1 (the mass stays), v := v1 (its fourth component stays), acc := (a1, 0), a3, a4, a5 := (those, 0)
+struct Hermite6Consts { double dt, ch, c2, c10, c120, d2, d3, d4, d5; };
+__global__ __launch_bounds__(kBlock) void hermite6_correct_kernel(double4 *__restrict__ posm, double4 *__restrict__ vel,
+                                                                  double4 *__restrict__ acc, const double *__restrict__ ajs0,
+                                                                  const double *__restrict__ ajs1, double4 *__restrict__ a3,
+                                                                  double4 *__restrict__ a4, double4 *__restrict__ a5, int n,
+                                                                  Hermite6Consts k) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double4 x = posm[i], v = vel[i];
+  const Ajs s0 = load_ajs(ajs0, i), s1 = load_ajs(ajs1, i);
+  const double xc[3] = {x.x, x.y, x.z}, vc[3] = {v.x, v.y, v.z};
+  double x1[3], v1[3], q3[3], q4[3], q5[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    v1[q] = vc[q] + ((k.ch * (s0.a[q] + s1.a[q]) + k.c10 * (s0.j[q] - s1.j[q])) + k.c120 * (s0.s[q] + s1.s[q]));
+    x1[q] = xc[q] + ((k.ch * (vc[q] + v1[q]) + k.c10 * (s0.a[q] - s1.a[q])) + k.c120 * (s0.j[q] + s1.j[q]));
+    const double R1 = ((s1.a[q] - s0.a[q]) - k.dt * s0.j[q]) - k.c2 * s0.s[q];
+    const double R2 = k.dt * ((s1.j[q] - s0.j[q]) - k.dt * s0.s[q]);
+    const double R3 = k.d2 * (s1.s[q] - s0.s[q]);
+    const double X = ((60.0 * R1) - (24.0 * R2)) + (3.0 * R3);
+    const double Y = ((168.0 * R2) - (360.0 * R1)) - (24.0 * R3);
+    const double Z = ((720.0 * R1) - (360.0 * R2)) + (60.0 * R3);
+    q3[q] = ((X + Y) + 0.5 * Z) / k.d3;
+    q4[q] = (Y + Z) / k.d4;
+    q5[q] = Z / k.d5;
+  }
+  posm[i] = make_double4(x1[0], x1[1], x1[2], x.w);
+  vel[i] = make_double4(v1[0], v1[1], v1[2], v.w);
+  acc[i] = make_double4(s1.a[0], s1.a[1], s1.a[2], 0.0);
+  a3[i] = make_double4(q3[0], q3[1], q3[2], 0.0);
+  a4[i] = make_double4(q4[0], q4[1], q4[2], 0.0);
+  a5[i] = make_double4(q5[0], q5[1], q5[2], 0.0);
+}
+
+// nbody_hermite6_timescale's candidates (k, body), reduced as jerk_time_parts_kernel reduces its own.  derivs: norms
+// sqrt((x x + y y) + z z), k = (|a3| |a5| + |a4| |a4|) / (|a0| |s0| + |j0| |j0|); else nbody_jerk_time's k = |j0|^2 / |a0|^2 of the
+// squared norms.  0 / 0 = 0, x / 0 = +inf, and a value that is not finite counts as +inf.
+__device__ __forceinline__ double norm3_dev(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+__global__ __launch_bounds__(kBlock) void hermite6_time_parts_kernel(const double *__restrict__ ajs0, const double4 *__restrict__ a3,
+                                                                     const double4 *__restrict__ a4, const double4 *__restrict__ a5,
+                                                                     int n, int derivs, double *__restrict__ part) {
+  __shared__ TidalMax red[kBlock / 64];
+  TidalMax m{-1.0, 0x7fffffff};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const Ajs s = load_ajs(ajs0, i);
+    double num, den;
+    if (derivs) {
+      const double4 d3 = a3[i], d4 = a4[i], d5 = a5[i];
+      const double A0 = norm3_dev(s.a[0], s.a[1], s.a[2]), J0 = norm3_dev(s.j[0], s.j[1], s.j[2]), S0 = norm3_dev(s.s[0], s.s[1], s.s[2]);
+      const double A3 = norm3_dev(d3.x, d3.y, d3.z), A4 = norm3_dev(d4.x, d4.y, d4.z), A5 = norm3_dev(d5.x, d5.y, d5.z);
+      num = A3 * A5 + A4 * A4;
+      den = A0 * S0 + J0 * J0;
+    } else {
+      num = (s.j[0] * s.j[0] + s.j[1] * s.j[1]) + s.j[2] * s.j[2];
+      den = (s.a[0] * s.a[0] + s.a[1] * s.a[1]) + s.a[2] * s.a[2];
+    }
+    double k = (num == 0.0 && den == 0.0) ? 0.0 : num / den;
+    if (!(k <= 0x1.fffffffffffffp1023)) k = __builtin_inf();
+    tidal_max_take(m, k, i);
+  }
+  const TidalMax r = tidal_max_workgroup(m, red);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
+}
+__global__ __launch_bounds__(kBlock) void hermite6_time_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
+  __shared__ TidalMax red[kBlock / 64];
+  TidalMax m{-1.0, 0x7fffffff};
+  for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(m, part[2 * q], (int)part[2 * q + 1]);
+  const TidalMax r = tidal_max_workgroup(m, red);
+  if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
+}
+
+inline bool bad(const Hermite6Launch &L) {
+  return L.n <= 0 || !L.posm || !L.vel || !L.ajs0 || !L.a3;
+}
+
+}  // namespace
+
+hipError_t launch_snap(const SnapLaunch &L, hipStream_t s) {
+  if (L.n_total <= 0 || !L.posm || !L.vel || !L.ain || L.ain_stride < 3 || !L.part || !L.ajs64) return hipErrorInvalidValue;
+  const bool soft = L.eps2 > 0.0;                              // eps == 0: the exact d == 0 rule, as the jerk
+  int j_split, j_chunk;
+  probe_geometry(L.n_total, &j_split, &j_chunk);
+  const size_t slab = probe_slab_points(L.n_total, kSnapRowWidth);
+  for (size_t first = 0; first < (size_t)L.n_total; first += slab) {
+    const int m = (int)std::min(slab, (size_t)L.n_total - first);
+    const dim3 grid((m + kBlock * kSnapIpt - 1) / (kBlock * kSnapIpt), j_split);
+    hipLaunchKernelGGL((soft ? snap_tile_f64_kernel<true, kSnapIpt> : snap_tile_f64_kernel<false, kSnapIpt>), grid, dim3(kBlock), 0, s,
+                       (const double4 *)L.posm, (const double4 *)L.vel, L.ain, L.ain_stride, (double *)L.part, L.n_total, m, (int)first,
+                       j_chunk, L.G, L.eps2);
+    hipLaunchKernelGGL(snap_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
+                       L.ajs64 + 9 * first);
+  }
+  return hipGetLastError();
+}
+
+// the constants are the host's own doubles — products and one quotient each, in the order written (nothing a host compiler could fuse)
+hipError_t launch_hermite6_predict(const Hermite6Launch &L, hipStream_t s) {
+  if (bad(L) || !L.xp || !L.vp || !L.ap) return hipErrorInvalidValue;
+  const double dt = L.dt, d2 = dt * dt;
+  const Hermite6PredictConsts k{dt, d2 * 0.5, (d2 * dt) / 6.0, (d2 * d2) / 24.0, ((d2 * d2) * dt) / 120.0};
+  hipLaunchKernelGGL(hermite6_predict_kernel, dim3((L.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double4 *)L.posm,
+                     (const double4 *)L.vel, L.ajs0, (const double4 *)L.a3, (double4 *)L.xp, (double4 *)L.vp, (double4 *)L.ap, L.n, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_hermite6_correct(const Hermite6Launch &L, hipStream_t s) {
+  if (bad(L) || !L.acc || !L.ajs1 || !L.a4 || !L.a5) return hipErrorInvalidValue;
+  const double dt = L.dt, d2 = dt * dt, d4 = d2 * d2;
+  const Hermite6Consts k{dt, dt * 0.5, d2 * 0.5, d2 / 10.0, (d2 * dt) / 120.0, d2, d2 * dt, d4, d4 * dt};
+  hipLaunchKernelGGL(hermite6_correct_kernel, dim3((L.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (double4 *)L.posm, (double4 *)L.vel,
+                     (double4 *)L.acc, L.ajs0, L.ajs1, (double4 *)L.a3, (double4 *)L.a4, (double4 *)L.a5, L.n, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *a4, const void *a5, int n, bool derivs, double *partials,
+                                double *out, hipStream_t s) {
+  if (n <= 0 || !ajs0 || !a3 || !a4 || !a5 || !partials || !out) return hipErrorInvalidValue;
+  const int slots = energy_fast_slots(n);
+  hipLaunchKernelGGL(hermite6_time_parts_kernel, dim3(slots), dim3(kBlock), 0, s, ajs0, (const double4 *)a3, (const double4 *)a4,
+                     (const double4 *)a5, n, derivs ? 1 : 0, partials);
+  hipLaunchKernelGGL(hermite6_time_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)partials, slots, out);
+  return hipGetLastError();
+}
+
+}  // namespace nbody

@@ -495,6 +495,51 @@ class NBodyEngine:
         self._check(self._L.nbody_hermite_block_get(self._h, ticks.ctypes.data, level.ctypes.data))
         return ticks, level
 
+    # -- the snap and sixth-order Hermite stepping (fp64 contexts) --
+    def snap(self, acc_in=None):
+        """(acc, jerk, snap): every body's acceleration, jerk and snap s = d^2 a / dt^2 from all OTHER bodies, three [n_total,3] float64
+        arrays (nbody_get_snap_f64).  acc_in: the [n_total,3] accelerations the snap's pair term takes differences of; None: the live
+        state's own unrounded accelerations, from one fp64 jerk pass first — the result is then the physical snap of the stored state.
+        acc and jerk equal jerk(np.float64) in every bit whatever acc_in holds.  precision="f64" contexts on one device owning all bodies;
+        everything else: ERR_UNSUPPORTED.  Changes nothing a getter shows and leaves both Hermite caches alone."""
+        ain = None
+        if acc_in is not None:
+            ain = np.ascontiguousarray(acc_in, np.float64)
+            if ain.shape != (self.n_total, 3):
+                raise ValueError(f"snap: acc_in must be [{self.n_total},3]")
+        out = [np.empty((self.n_total, 3), np.float64) for _ in range(3)]
+        self._check(self._L.nbody_get_snap_f64(self._h, None if ain is None else ain.ctypes.data, 24, out[0].ctypes.data, 24,
+                                               out[1].ctypes.data, 24, out[2].ctypes.data, 24))
+        return tuple(out)
+
+    def hermite6_step(self, dt, nsteps=1):
+        """nsteps shared steps of length dt of the sixth-order Hermite predictor-corrector (nbody_hermite6_step): one fp64 snap pass per
+        step once the derivatives are cached.  Contexts, the synchronised-velocities rule and dt <= 0 as hermite_step()."""
+        self._check(self._L.nbody_hermite6_step(self._h, float(dt), int(nsteps)))
+
+    def hermite6_timescale(self):
+        """(t, body, kind): the sixth-order step's time scale and the body that sets it (nbody_hermite6_timescale).  kind 1: from the
+        cached a, j, s, a3, a4, a5, t = ((|a||s| + |j|^2) / (|a3||a5| + |a4|^2))^(1/6); kind 0: jerk_time()'s |a| / |j| (no step taken)."""
+        t, body, kind = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.nbody_hermite6_timescale(self._h, ctypes.byref(t), ctypes.byref(body), ctypes.byref(kind)))
+        return t.value, body.value, kind.value
+
+    def hermite6_advance(self, t_span, eta=0.5, eta_start=0.01, dt_max=float("inf"), max_steps=2 ** 31):
+        """(t_done, steps): shared adaptive sixth-order steps, dt = min(dt_max, eta t) — eta times t itself, NO square root as in
+        hermite_advance; eta_start t for a step without cached derivatives —, until t_span has passed (t_done == t_span exactly) or
+        max_steps have been taken (nbody_hermite6_advance)."""
+        t, n = ctypes.c_double(), ctypes.c_int64()
+        self._check(self._L.nbody_hermite6_advance(self._h, float(t_span), float(eta), float(eta_start), float(dt_max), int(max_steps),
+                                                   ctypes.byref(t), ctypes.byref(n)))
+        return t.value, n.value
+
+    def hermite6_state(self):
+        """(a, j, s, a3, a4, a5): the sixth-order cache of the stored state, six [n_total,3] float64 arrays (nbody_hermite6_get); a3, a4
+        and a5 are zeros until a step has been taken.  ERR_STATE while nothing is cached for the stored state."""
+        out = np.empty((self.n_total, 18), np.float64)
+        self._check(self._L.nbody_hermite6_get(self._h, out.ctypes.data, 144))
+        return tuple(np.ascontiguousarray(out[:, 3 * k:3 * k + 3]) for k in range(6))
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
