@@ -665,6 +665,69 @@ NBODY_AMD_API int nbody_hermite6_advance(nbody_ctx *ctx, double t_span, double e
                                          double *t_done, int64_t *steps);
 NBODY_AMD_API int nbody_hermite6_get(nbody_ctx *ctx, double *d18, size_t stride);
 
+/* Sixth-order Hermite BLOCK time steps (build-defined) — Nitadori & Makino's scheme with a step per body: the sixth-order predictor,
+ * snap evaluation and corrector above inside the ticks, levels, frames and sessions of nbody_hermite_block_*.  Where: the contexts that
+ * answer nbody_hermite6_step (NBODY_PREC_F64, one device, all bodies); fp32 and Kahan contexts, slice contexts and nbody_create_multi
+ * contexts report NBODY_ERR_UNSUPPORTED with that call's reasons.  No particles set: NBODY_ERR_STATE.
+ *
+ * Time, ticks, levels, frames and the ragged-state rule are those of the fourth-order block steps, word for word: tick =
+ * ldexp(dt_max, -levels), 0 <= levels <= 40, body i at T_i (int64 ticks) with level k_i whose step is dt_max 2^-k_i, T_i always a multiple
+ * of that step, every multiple of 2^levels ticks a FRAME end where the stored state is synchronised.  (x_i, v_i) AT T_i are in the state
+ * buffers, (a0, j0, s0, a3, a4, a5)_i at T_i in the sixth-order cache: the session lives on THAT cache, a session of its own beside the
+ * fourth-order one.  nbody_hermite_block_stats is reused as it is.
+ *
+ * One block step — every bracket ONE correctly rounded fp64 operation, contraction off:
+ *   schedule   T_next = min_i (T_i + step_i); the active set = the bodies that attain it, ascending body index, no atomics
+ *   predict    EVERY body: dt_i = (double)(T_next - T_i) * tick; on the device d2 = dt_i dt_i, c2 = d2 0.5, c3 = (d2 dt_i) / 6,
+ *              c4 = (d2 d2) / 24, c5 = ((d2 d2) dt_i) / 120; then the sixth-order predictor above for xp, vp, ap with these constants
+ *   evaluate   (a1, j1, s1) of the ACTIVE bodies against all N predicted bodies with input accelerations ap: for every active body, in
+ *              every bit, what nbody_get_snap_f64(acc_in = ap) returns for that body on a context holding (xp, vp)
+ *   correct    the active bodies: the chunks' rows added from 0.0 in chunk order, then the sixth-order corrector above with the body's own
+ *              dt_i (d2 = dt_i dt_i, d4 = d2 d2, ch = dt_i 0.5, c2 = d2 0.5, c10 = d2 / 10, c120 = (d2 dt_i) / 120, d3 = d2 dt_i,
+ *              d5 = d4 dt_i, formed on the device); x, v, NBODY_BUF_ACC := (a1, 0), (a0, j0, s0) := (a1, j1, s1), a3, a4, a5,
+ *              T_i := T_next.  Inactive bodies keep every byte.
+ *   levels     kk = nbody_hermite6_timescale's per-body k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2) of the NEW vectors, with its
+ *              0 / 0 -> 0, x / 0 -> +inf, not finite -> +inf rules; kw = nbody_hermite6_block_level(kk, dt_max, levels, eta, &hit);
+ *              then the fourth-order block steps' rule: kw > k_i: k_i := kw; kw < k_i and T_next a multiple of 2^(levels - k_i + 1):
+ *              k_i := k_i - 1; otherwise k_i stays.
+ * nbody_steps_done grows by one per block step; a block step is one pass under NBODY_KERNEL_FORCES and one under NBODY_KERNEL_UPDATE.
+ * The host reads 16 bytes per block step.
+ *
+ * nbody_hermite6_block_level (host only, no context): THE LEVEL RULE HAS NO CUBE ROOT.  The step the criterion asks for is
+ *   eta kk^(-1/6); nbody_hermite6_timescale forms 1 / cbrt(sqrt(k)) on the host, and cbrt is not correctly rounded, so a device and numpy
+ *   could not agree on it in every bit.  The rule compares in the cubed domain instead: r = sqrt(kk), e3 = (eta eta) eta, and the level is
+ *   the smallest k in 0 .. levels with ((h h) h) r <= e3, h = ldexp(dt_max, -k).  h^3 shrinks by exactly 2^-3 per level while normal, so the
+ *   test is monotone in k; kk == 0 gives level 0; kk = +inf or NaN makes every comparison false.  If no k passes it returns `levels` and
+ *   *floor_hit = 1 (clamped and counted), otherwise *floor_hit = 0 (floor_hit may be NULL).  levels outside 0 .. 40: -1.  NOTE: eta
+ *   multiplies the sixth-root time scale DIRECTLY, as in nbody_hermite6_advance: 0.3 .. 1 here plays the part that 0.01 .. 0.04 plays in
+ *   nbody_hermite_block_begin.
+ * nbody_hermite6_block_begin: starts a session at tick 0 from the stored (x, v), taken as synchronised.  (a0, j0, s0) come from the
+ *   sixth-order cache where it is valid (its a3, a4, a5 too, if a step left them) and otherwise from nbody_hermite6_step's start: a jerk
+ *   pass, then a snap pass with that a — two passes under NBODY_KERNEL_FORCES; a3, a4, a5 then read as zeros until a body has stepped.
+ *   level_in, if not NULL: n_total levels, each 0 .. levels (else NBODY_ERR_INVALID).  NULL: nbody_hermite_block_begin's start rule on
+ *   the cached (a0, j0): k = |j|^2 / |a|^2, t = 1 / sqrt(k) with the same zero and not-finite rules, dt_c = eta_start * t, level =
+ *   nbody_hermite_block_level(dt_c, ...) (a body no level fits is a floor hit).  dt_max, eta and eta_start must be finite and > 0,
+ *   levels 0 .. 40, the tick AND (tick tick) tick normal doubles (the level rule cubes the step): anything else is NBODY_ERR_INVALID.
+ *   NBODY_HERMITE6_BLOCK_LANES=1|2, read here, forces the bodies per lane of the evaluation (otherwise one up to 1024 active bodies, two
+ *   beyond); neither choice enters any sum.  Synchronises.
+ * nbody_hermite6_block_advance, nbody_hermite6_block_get: nbody_hermite_block_advance's and _get's semantics and error codes.
+ *
+ * What ends a session: everything that invalidates the sixth-order cache (uploads, nbody_step / nbody_tick / nbody_step_end with dt > 0,
+ * nbody_bind_device_state, nbody_device_ptr, checkpoints loaded) and nbody_hermite_restart.  While a session is IN MID-FRAME,
+ * nbody_hermite6_step / _timescale / _advance, nbody_hermite_step / _timescale / _advance, nbody_hermite_block_begin and a second
+ * nbody_hermite6_block_begin report NBODY_ERR_STATE with a message that says why; AT A FRAME END they end the session and proceed as
+ * they always do — the sixth-order ones from the cache, the fourth-order ones invalidating it.  nbody_hermite6_block_begin meets a
+ * fourth-order block session the same way: NBODY_ERR_STATE in mid-frame, at a frame end that session ends.  nbody_hermite6_get works
+ * during a session: a row belongs to its own T_i.  nbody_get_snap_f64 and nbody_get_jerk_f64 leave the session alone.  Checkpoints stay
+ * NBDYCKP2 byte for byte and hold no levels: "save, nbody_hermite_restart, begin with the levels of nbody_hermite6_block_get, go on"
+ * equals "load, begin with those levels, go on" in every byte.
+ */
+NBODY_AMD_API int nbody_hermite6_block_level(double k, double dt_max, int32_t levels, double eta, int32_t *floor_hit);
+NBODY_AMD_API int nbody_hermite6_block_begin(nbody_ctx *ctx, double dt_max, int32_t levels, double eta, double eta_start,
+                                             const int32_t *level_in);
+NBODY_AMD_API int nbody_hermite6_block_advance(nbody_ctx *ctx, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out);
+NBODY_AMD_API int nbody_hermite6_block_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

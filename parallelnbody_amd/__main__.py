@@ -9,6 +9,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite --eta 0.02 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite-block --levels 12 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6-block --levels 12 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -48,16 +49,18 @@ def main(argv=None):
     ap.add_argument("--eps", type=float, default=0.0, help="softening length (reference: 0)")
     ap.add_argument("--G", type=float, default=1.0e4, help="gravitational constant (reference: 1e4)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f32_kahan", "f64"])
-    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite", "hermite-block", "hermite6"],
+    ap.add_argument("--integrator", default="kickdrift", choices=["kickdrift", "hermite", "hermite-block", "hermite6", "hermite6-block"],
                     help="kickdrift: the reference's v += dt a; x += dt v (default).  hermite: the fourth-order Hermite "
                          "predictor-corrector (needs --precision f64, theta = 0): one step of --dt per frame, or with --eta "
                          "adaptive shared steps that cover --dt per frame.  hermite-block: the same scheme with a step per body, "
                          "--dt 2^-level with level 0 .. --levels chosen by --eta (default 0.02); every frame of --dt ends synchronised"
                          ".  hermite6: the sixth-order Hermite predictor-corrector on the snap pass (--precision f64, theta = 0), "
                          "driven like hermite: one step of --dt per frame, or with --eta adaptive shared steps dt = eta t — no "
-                         "square root in this criterion: 0.5 does what 0.01 does for hermite (--eta 0 < eta; without it steps are fixed)")
+                         "square root in this criterion: 0.5 does what 0.01 does for hermite (--eta 0 < eta; without it steps are fixed).  "
+                         "hermite6-block: the sixth-order scheme with a step per body, driven like hermite-block (--levels, default 12; "
+                         "--eta, default 0.5, multiplies the sixth-root time scale directly)")
     ap.add_argument("--levels", type=int, default=None,
-                    help="--integrator hermite-block: the deepest level, 0 .. 40 (default 12): the smallest step is --dt 2^-levels")
+                    help="--integrator hermite-block and hermite6-block: the deepest level, 0 .. 40 (default 12): the smallest step is --dt 2^-levels")
     ap.add_argument("--eta", type=float, default=None,
                     help="--integrator hermite: Aarseth's accuracy parameter; every frame of length --dt is covered by adaptive steps "
                          "dt = sqrt(eta) t (0.01 t for a frame's first step after a restart)")
@@ -91,7 +94,8 @@ def main(argv=None):
 
     if a.trajectory_every < 1:
         ap.error("--trajectory-every must be >= 1")
-    block = a.integrator == "hermite-block"
+    block6 = a.integrator == "hermite6-block"                        # the same demands and exclusions as hermite-block
+    block = a.integrator == "hermite-block" or block6
     hermite = a.integrator == "hermite" or block
     six = a.integrator == "hermite6"                                 # the same demands and exclusions as hermite
     hermite = hermite or six
@@ -102,7 +106,7 @@ def main(argv=None):
     if a.eta is not None and not (hermite and a.eta > 0):
         ap.error("--eta belongs to --integrator hermite and hermite-block and must be > 0")
     if a.levels is not None and not (block and 0 <= a.levels <= 40):
-        ap.error("--levels belongs to --integrator hermite-block and must be 0 .. 40")
+        ap.error("--levels belongs to --integrator hermite-block and hermite6-block and must be 0 .. 40")
     posm, vel = (ic_plummer(a.n, G=a.G, seed=a.seed) if a.plummer else ic_reference_box(a.n, a.size, seed=a.seed))
     with NBodyEngine(a.n, device=a.device, precision=a.precision, G=a.G, eps=a.eps, theta=a.theta or 0.0) as e:
         e.set_state(posm, vel)
@@ -136,9 +140,12 @@ def main(argv=None):
             elif block:
                 if a.dt > 0 and frames > 0:
                     if not session:                              # one session for the run: nothing below ends it
-                        e.hermite_block_begin(a.dt, 12 if a.levels is None else a.levels, eta=a.eta or 0.02)
+                        if block6:
+                            e.hermite6_block_begin(a.dt, 12 if a.levels is None else a.levels, eta=a.eta or 0.5)
+                        else:
+                            e.hermite_block_begin(a.dt, 12 if a.levels is None else a.levels, eta=a.eta or 0.02)
                         session.append(True)
-                    e.hermite_block_advance(frames)
+                    (e.hermite6_block_advance if block6 else e.hermite_block_advance)(frames)
             elif six and a.eta is None:
                 e.hermite6_step(a.dt, frames)
             elif six:

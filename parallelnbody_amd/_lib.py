@@ -187,6 +187,10 @@ def lib():
     sig("nbody_hermite6_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
     sig("nbody_hermite6_advance", c_int, vp, c_d, c_d, c_d, c_d, c_i64, dp, ctypes.POINTER(c_i64))
     sig("nbody_hermite6_get", c_int, vp, vp, sz)
+    sig("nbody_hermite6_block_level", c_int, c_d, c_d, c_i32, c_d, ctypes.POINTER(c_i32))
+    sig("nbody_hermite6_block_begin", c_int, vp, c_d, c_i32, c_d, c_d, vp)
+    sig("nbody_hermite6_block_advance", c_int, vp, c_i64, c_i64, ctypes.POINTER(HermiteBlockStats))
+    sig("nbody_hermite6_block_get", c_int, vp, vp, vp)
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

@@ -618,7 +618,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite, c->hblock})
     if (q) (void)hipFree(q);
-  for (void *q : {c->hermite6, c->snap64})
+  for (void *q : {c->hermite6, c->snap64, c->h6block})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1737,6 +1737,18 @@ int hermite_block_leave(nbody_ctx *c, const char *who) {
   return NBODY_OK;
 }
 
+// The same for a SIXTH-order block session (nbody_hermite6_block_*), which every shared-step call of either order and every begin meets
+// the same way: refused in mid-frame, ended at a frame end.
+int hermite6_block_leave(nbody_ctx *c, const char *who) {
+  if (!c->h6b.active) return NBODY_OK;
+  if (c->h6b.ticks & ((1ll << c->h6b.levels) - 1))
+    return fail(c, NBODY_ERR_STATE, "%s: a sixth-order Hermite block session is in mid-frame (tick %lld of frames of %lld): the bodies are at "
+                "times of their own; nbody_hermite6_block_advance(ctx, 1, ...) finishes the frame, nbody_hermite_restart abandons the session",
+                who, (long long)c->h6b.ticks, 1ll << c->h6b.levels);
+  c->h6b.active = false;
+  return NBODY_OK;
+}
+
 struct HermiteBufs { double *xp, *vp, *a2, *a3, *aj[2], *partials; };
 HermiteBufs hermite_bufs(const nbody_ctx *c) {
   const size_t n = (size_t)c->p.n_total;
@@ -1814,6 +1826,7 @@ int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_step: dt is not finite, or nsteps < 0");
   if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite_step"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite_step"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   nbody::hermite6_invalidate(c);                                   // (the state moves on without the sixth-order cache)
   for (int s = 0; s < nsteps; ++s)
@@ -1826,6 +1839,7 @@ int nbody_hermite_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t 
   if (rc) return rc;
   if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_timescale: all three outputs are null");
   if ((rc = hermite_block_leave(c, "nbody_hermite_timescale"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite_timescale"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   double t = 0.0;
   int32_t at = 0, which = 0;
@@ -1848,6 +1862,7 @@ int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_st
   if (steps) *steps = 0;
   if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite_advance"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite_advance"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   nbody::hermite6_invalidate(c);
   const double root_eta = std::sqrt(eta);
@@ -1906,14 +1921,14 @@ int nbody_hermite_restart(nbody_ctx *c) {
 // ---- Hermite block time steps: a session of per-body power-of-two steps on the cache above (kernels_hermite_block.hip) ----
 namespace {
 struct HermiteBlockBufs { long long *T, *seg_min, *record; unsigned long long *floor_hits; int *level, *list, *seg_cnt; };
-HermiteBlockBufs hermite_block_bufs(const nbody_ctx *c) {
-  const size_t n = (size_t)c->p.n_total;
+HermiteBlockBufs hermite_block_bufs_at(void *base, size_t n) {
   int slots;
   (void)nbody::hermite_block_segment((int)n, &slots);
-  long long *q = (long long *)c->hblock;
+  long long *q = (long long *)base;
   int *w = (int *)(q + n + slots + 3);
   return HermiteBlockBufs{q, q + n, q + n + slots, (unsigned long long *)(q + n + slots + 2), w, w + n, w + 2 * n};
 }
+HermiteBlockBufs hermite_block_bufs(const nbody_ctx *c) { return hermite_block_bufs_at(c->hblock, (size_t)c->p.n_total); }
 size_t hermite_block_bytes(int n) {
   int slots;
   (void)nbody::hermite_block_segment(n, &slots);
@@ -2004,6 +2019,7 @@ int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, doubl
       if (level_in[i] < 0 || level_in[i] > levels)
         return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
   if ((rc = hermite_block_leave(c, "nbody_hermite_block_begin"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite_block_begin"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
   nbody::hermite6_invalidate(c);
   if (!c->hblock) HIP_TRY(c, hipMalloc(&c->hblock, hermite_block_bytes(n)));
@@ -2380,6 +2396,7 @@ int nbody_hermite6_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_step: dt is not finite, or nsteps < 0");
   if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite6_step"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite6_step"))) return rc;
   if ((rc = hermite6_enter(c))) return rc;
   for (int s = 0; s < nsteps; ++s)
     if ((rc = hermite6_one_step(c, dt))) return rc;
@@ -2391,6 +2408,7 @@ int nbody_hermite6_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t
   if (rc) return rc;
   if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_timescale: all three outputs are null");
   if ((rc = hermite_block_leave(c, "nbody_hermite6_timescale"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite6_timescale"))) return rc;
   if ((rc = hermite6_enter(c))) return rc;
   double t = 0.0;
   int32_t at = 0, which = 0;
@@ -2413,6 +2431,7 @@ int nbody_hermite6_advance(nbody_ctx *c, double t_span, double eta, double eta_s
   if (steps) *steps = 0;
   if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
   if ((rc = hermite_block_leave(c, "nbody_hermite6_advance"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite6_advance"))) return rc;
   if ((rc = hermite6_enter(c))) return rc;
   while (t_acc < t_span && taken < max_steps) {
     double t = 0.0;
@@ -2453,6 +2472,150 @@ int nbody_hermite6_get(nbody_ctx *c, double *d18, size_t stride) {
     for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * n + i), 24);   // (zeros until a step has been taken)
     memcpy((char *)d18 + i * stride, rec, 144);
   }
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- sixth-order Hermite block time steps: a session of per-body power-of-two steps on the sixth-order cache (kernels_hermite6_block.hip) ----
+namespace {
+nbody::Hermite6BlockLaunch hermite6_block_launch(const nbody_ctx *c) {
+  const Hermite6Bufs b = hermite6_bufs(c);
+  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, (size_t)c->p.n_total);
+  nbody::Hermite6BlockLaunch L;
+  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.ap = b.ap; L.ajs0 = b.ajs[c->h6_cur];
+  L.a3 = b.a3; L.a4 = b.a4; L.a5 = b.a5;
+  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = q.record;
+  L.floor_hits = q.floor_hits; L.n = c->p.n_total; L.levels = c->h6b.levels; L.tick = c->h6b.tick; L.dt_max = c->h6b.dt_max;
+  L.eta = c->h6b.eta; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+  return L;
+}
+
+// the totals since begin; the levels' range and the floor hits are read from the device (4 n + 8 bytes): waits for the stream
+int hermite6_block_fill(nbody_ctx *c, nbody_hermite_block_stats *out) {
+  const size_t n = (size_t)c->p.n_total;
+  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, n);
+  if (int rc = ensure_stage(c, n * 4 + 8)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.floor_hits, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int64_t floor_hits;
+  memcpy(&floor_hits, c->h_stage, 8);
+  const int32_t *lv = (const int32_t *)((const char *)c->h_stage + 8);
+  out->synchronised = (c->h6b.ticks & ((1ll << c->h6b.levels) - 1)) == 0 ? 1 : 0;
+  out->ticks = c->h6b.ticks; out->frames_done = c->h6b.ticks >> c->h6b.levels; out->block_steps = c->h6b.block_steps;
+  out->body_steps = c->h6b.body_steps; out->pairs = c->h6b.pairs; out->floor_hits = floor_hits;
+  out->level_min = *std::min_element(lv, lv + n); out->level_max = *std::max_element(lv, lv + n);
+  return NBODY_OK;
+}
+
+// one block step, from the schedule to the stored bodies; the host waits once, for (T_next, m), to size the evaluation.  An active set
+// larger than a slab of partial rows goes through evaluation and corrector slab by slab: the predicted state is in buffers of its own, so
+// a corrected slab changes nothing a later slab's evaluation reads.
+int hermite6_block_one_step(nbody_ctx *c) {
+  const nbody::Hermite6BlockLaunch L = hermite6_block_launch(c);
+  int rc;
+  if ((rc = probe_part_holds(c, nbody::kSnapRowWidth, "the snap pass of a block step"))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_schedule(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  long long rec[2];
+  memcpy(rec, c->h_scratch, 16);
+  const long long t_next = rec[0];
+  const int n = c->p.n_total, m = (int)rec[1];
+  if (rec[1] < 1 || rec[1] > n || t_next <= c->h6b.ticks)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_advance: the schedule gave T_next = %lld, m = %lld at tick %lld", t_next, rec[1], (long long)c->h6b.ticks);
+  const int lanes = nbody::hermite_block_lanes(m, c->h6b.lanes);
+  const int slab = (int)std::min<size_t>(nbody::probe_slab_points(n, nbody::kSnapRowWidth), (size_t)n);
+  for (int first = 0; first < m; first += slab) {
+    const int ms = std::min(slab, m - first);
+    const bool last = first + ms == m;
+    if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_evaluate(L, first, ms, lanes, c->stream)); return NBODY_OK; }, last))) return rc;
+    if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_correct(L, first, ms, t_next, c->stream)); return NBODY_OK; }, last))) return rc;
+  }
+  c->h6b.ticks = t_next;
+  c->h6b.block_steps += 1; c->h6b.body_steps += m; c->h6b.pairs += (int64_t)m * n;
+  if (c->h6b.ticks >= (1ll << c->h6b.levels)) c->h6_derivs = true;   // a whole frame: every body has stepped, every a3, a4, a5 is a step's
+  c->sym_posg_valid = false;
+  c->steps_done += 1;
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_hermite6_block_level(double k, double dt_max, int32_t levels, double eta, int32_t *floor_hit) {
+  if (levels < 0 || levels > nbody::kHermiteBlockMaxLevels) return -1;
+  int hit = 0;
+  const int kw = nbody::hermite6_block_level(k, dt_max, levels, eta, &hit);
+  if (floor_hit) *floor_hit = hit;
+  return kw;
+}
+
+int nbody_hermite6_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
+  int rc = hermite_ready(c, "nbody_hermite6_block_begin");
+  if (rc) return rc;
+  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!positive(dt_max) || !positive(eta) || !positive(eta_start) || levels < 0 || levels > nbody::kHermiteBlockMaxLevels)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: dt_max, eta and eta_start must be finite and > 0, levels 0 .. %d", nbody::kHermiteBlockMaxLevels);
+  const double tick = std::ldexp(dt_max, -levels);
+  if (!std::isnormal(tick) || !std::isnormal((tick * tick) * tick))
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: the tick dt_max 2^-levels = %g or its cube, which the level rule compares, is not "
+                "a normal number", tick);
+  const int n = c->p.n_total;
+  if (level_in)
+    for (int i = 0; i < n; ++i)
+      if (level_in[i] < 0 || level_in[i] > levels)
+        return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
+  if ((rc = hermite_block_leave(c, "nbody_hermite6_block_begin"))) return rc;
+  if ((rc = hermite6_block_leave(c, "nbody_hermite6_block_begin"))) return rc;
+  if ((rc = hermite6_enter(c))) return rc;
+  nbody::hermite_invalidate(c);                                    // (the state moves on without the fourth-order cache)
+  if (!c->h6block) HIP_TRY(c, hipMalloc(&c->h6block, hermite_block_bytes(n)));
+  c->h6b.levels = levels; c->h6b.dt_max = dt_max; c->h6b.tick = tick; c->h6b.eta = eta;
+  c->h6b.lanes = nbody::env_int("NBODY_HERMITE6_BLOCK_LANES", 0);
+  c->h6b.ticks = c->h6b.block_steps = c->h6b.body_steps = c->h6b.pairs = 0;
+  const nbody::Hermite6BlockLaunch L = hermite6_block_launch(c);
+  if (!c->h6_derivs) HIP_TRY(c, hipMemsetAsync(L.a3, 0, (size_t)n * 96, c->stream));   // a3, a4, a5 lie side by side: zeros until a body steps
+  HIP_TRY(c, hipMemsetAsync(L.record, 0, 24, c->stream));          // the record and the floor hits
+  if (level_in) HIP_TRY(c, hipMemcpyAsync(L.list, level_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, nbody::launch_hermite6_block_init(L, level_in ? L.list : nullptr, eta_start, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's array is its own again
+  c->h6b.active = true;
+  return NBODY_OK;
+}
+
+int nbody_hermite6_block_advance(nbody_ctx *c, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out) {
+  int rc = hermite_ready(c, "nbody_hermite6_block_advance");
+  if (rc) return rc;
+  if (frames < 0 || max_block_steps < 0 || (out && out->struct_size != sizeof(nbody_hermite_block_stats)))
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_advance: frames < 0, max_block_steps < 0, or out->struct_size is not "
+                "sizeof(nbody_hermite_block_stats) = %d", (int)sizeof(nbody_hermite_block_stats));
+  if (!c->h6b.active)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_advance: no sixth-order block session (nbody_hermite6_block_begin first; uploads, "
+                "kick-drift steps, handed-out pointers, shared Hermite steps and nbody_hermite_restart end one)");
+  const int64_t frame_now = c->h6b.ticks >> c->h6b.levels;
+  if (frames >= (1ll << 62 >> c->h6b.levels) - frame_now)
+    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_advance: %lld more frames of 2^%d ticks pass 2^62 ticks", (long long)frames, c->h6b.levels);
+  const int64_t target = frames == 0 ? c->h6b.ticks : (frame_now + frames) << c->h6b.levels;
+  for (int64_t taken = 0; c->h6b.ticks < target && taken < max_block_steps; ++taken)
+    if ((rc = hermite6_block_one_step(c))) return rc;
+  return out ? hermite6_block_fill(c, out) : NBODY_OK;
+}
+
+int nbody_hermite6_block_get(nbody_ctx *c, int64_t *ticks, int32_t *level) {
+  int rc = hermite_ready(c, "nbody_hermite6_block_get");
+  if (rc) return rc;
+  if (!c->h6b.active)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_get: no sixth-order block session (nbody_hermite6_block_begin first)");
+  const size_t n = (size_t)c->p.n_total;
+  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, n);
+  if ((rc = ensure_stage(c, n * 12))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.T, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + n * 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (ticks) memcpy(ticks, c->h_stage, n * 8);
+  if (level) memcpy(level, (const char *)c->h_stage + n * 8, n * 4);
   return NBODY_OK;
 }
 

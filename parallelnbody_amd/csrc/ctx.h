@@ -124,6 +124,15 @@ struct nbody_ctx {
     double dt_max = 0.0, tick = 0.0, root_eta = 0.0;
     int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
   } hb;
+  // Sixth-order Hermite block time steps (nbody_hermite6_block_*, kernels_hermite6_block.hip): a session of its own on the sixth-order
+  // cache.  h6block, allocated at the first begin, is laid out like hblock
+  void *h6block = nullptr;
+  struct {
+    bool active = false;       // between nbody_hermite6_block_begin and whatever ends the session
+    int levels = 0, lanes = 0; // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE6_BLOCK_LANES (0: by the list's length)
+    double dt_max = 0.0, tick = 0.0, eta = 0.0;
+    int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
+  } h6b;
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
@@ -164,7 +173,8 @@ inline int use_device(nbody_ctx *c) {
 inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; c->hb.active = false; }
 // The same for the sixth-order cache, which every caller of hermite_invalidate forgets as well — and so do the fourth-order calls that
 // step the state (nbody_hermite_step, nbody_hermite_advance, nbody_hermite_block_begin), whose cache a sixth-order step forgets in turn.
-inline void hermite6_invalidate(nbody_ctx *c) { c->h6_valid = false; c->h6_derivs = false; }
+// A sixth-order block session lives on that cache and ends with it.
+inline void hermite6_invalidate(nbody_ctx *c) { c->h6_valid = false; c->h6_derivs = false; c->h6b.active = false; }
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
 constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain

@@ -1,5 +1,6 @@
-// The level rule of the Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip), one function for the device and
-// the host: the corrector calls it per active body, nbody_hermite_block_level exports it so that the CPU tests pin it without a device.
+// The level rules of the Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip; nbody_hermite6_block_*,
+// kernels_hermite6_block.hip), one function each for the device and the host: the correctors call them per active body,
+// nbody_hermite_block_level and nbody_hermite6_block_level export them so that the CPU tests pin them without a device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,24 @@ __host__ __device__ inline int hermite_block_level(double dt_c, double dt_max, i
   *floor_hit = 0;
   for (int k = 0; k <= levels; ++k)
     if (ldexp(dt_max, -k) <= dt_c) return k;
+  *floor_hit = 1;
+  return levels;
+}
+
+// The sixth-order rule (nbody_hermite6_block_*, kernels_hermite6_block.hip).  kk is nbody_hermite6_timescale's per-body
+// k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2), whose step is eta kk^(-1/6).  A cube root is not correctly rounded, so the device and
+// numpy could not agree on it in every bit; the rule therefore compares in the CUBED domain, where every operation is: r = sqrt(kk),
+// e3 = (eta eta) eta, and the level is the smallest k in 0 .. levels with ((h h) h) r <= e3, h = ldexp(dt_max, -k) — which is
+// h <= eta kk^(-1/6).  h^3 shrinks by exactly 2^-3 per level while it is normal (the session demands a normal tick^3), so the test is
+// monotone in k.  kk == 0 gives level 0; kk = +inf or NaN makes every comparison false.  If no k passes the body is clamped to `levels`
+// and *floor_hit = 1; otherwise *floor_hit = 0.
+__host__ __device__ inline int hermite6_block_level(double kk, double dt_max, int levels, double eta, int *floor_hit) {
+  const double r = sqrt(kk), e3 = (eta * eta) * eta;
+  *floor_hit = 0;
+  for (int k = 0; k <= levels; ++k) {
+    const double h = ldexp(dt_max, -k);
+    if (((h * h) * h) * r <= e3) return k;
+  }
   *floor_hit = 1;
   return levels;
 }

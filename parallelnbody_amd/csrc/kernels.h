@@ -219,6 +219,9 @@ hipError_t launch_hermite_block_init(const HermiteBlockLaunch &L, const int *lev
 hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_t s);
 hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first, int m, int lanes, hipStream_t s);
 hipError_t launch_hermite_block_correct(const HermiteBlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
+// the schedule's first kernel alone — seg_min[q], seg_cnt[q] of every segment q: the smallest T[i] + step_i and how many bodies attain it —,
+// which the sixth-order session queues ahead of a list kernel of its own (integers only: it reads no cache)
+hipError_t launch_hermite_block_next(const long long *T, const int *level, int n, int levels, long long *seg_min, int *seg_cnt, hipStream_t s);
 
 // The snap s = d^2 a / dt^2 beside the acceleration and the jerk of an fp64 state, the bodies only — kernels_snap.hip: with d = x_j - x_i,
 // w = v_j - v_i, b = ain_j - ain_i (ain: a per-body INPUT acceleration), s^2 = |d|^2 + eps2, t = 1 / s, al = (d . w) t^2,
@@ -260,6 +263,33 @@ hipError_t launch_hermite6_correct(const Hermite6Launch &L, hipStream_t s);
 // index that attains it, as a double: launch_jerk_time's reduction and its `partials`.
 hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *a4, const void *a5, int n, bool derivs, double *partials,
                                 double *out, hipStream_t s);
+
+// Sixth-order Hermite block time steps of an fp64 state — kernels_hermite6_block.hip: HermiteBlockLaunch's times, levels, segments and
+// scheduler around the ACTIVE-SET form of the snap pass (snap_tile64.h: nbody_get_snap_f64's chunks, pair operations and order) and the
+// sixth-order predictor and corrector with a dt per body; the level rule is hermite6_block_level (hermite_block_level.h).
+//   launch_hermite6_block_init:      T := 0; level := level_in (device, may be null: the level of eta_start |a0| / |j0| from ajs0)
+//   launch_hermite6_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp, ap) = every body at T_next
+//   launch_hermite6_block_evaluate:  the rows of list[first .. first + m) into part, m <= probe_slab_points(n, kSnapRowWidth)
+//   launch_hermite6_block_correct:   those bodies corrected from part (the rows of that launch), their T, level, cache and state stored
+struct Hermite6BlockLaunch {
+  void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state
+  void *xp = nullptr, *vp = nullptr, *ap = nullptr;       // [n] double4 each: the predicted state and its predicted accelerations
+  double *ajs0 = nullptr;                                 // [n][9]: every body's (a, j, s) at its own time
+  void *a3 = nullptr, *a4 = nullptr, *a5 = nullptr;       // [n] double4 each
+  void *part = nullptr;                                   // [probe_part_elems(n, n, kSnapRowWidth)] float4: the evaluation's partial rows
+  long long *T = nullptr;                                 // [n] ticks
+  int *level = nullptr, *list = nullptr;                  // [n] each
+  long long *seg_min = nullptr;                           // [slots of hermite_block_segment]
+  int *seg_cnt = nullptr;                                 // [slots]
+  long long *record = nullptr;                            // [2]: T_next, m
+  unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
+  int n = 0, levels = 0;
+  double tick = 0.0, dt_max = 0.0, eta = 0.0, G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_hermite6_block_init(const Hermite6BlockLaunch &L, const int *level_in, double eta_start, hipStream_t s);
+hipError_t launch_hermite6_block_schedule(const Hermite6BlockLaunch &L, hipStream_t s);
+hipError_t launch_hermite6_block_evaluate(const Hermite6BlockLaunch &L, int first, int m, int lanes, hipStream_t s);
+hipError_t launch_hermite6_block_correct(const Hermite6BlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
 
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.

@@ -16,38 +16,13 @@
 #include "kernels.h"
 
 #include "hermite_block_level.h"
+#include "hermite_block_sched.h"
 
 #pragma clang fp contract(off)
 
 namespace nbody {
 
 namespace {
-
-constexpr long long kNever = 0x7fffffffffffffffll;
-
-__device__ __forceinline__ long long block_min_workgroup(long long v, long long (&red)[kBlock / 64]) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  __syncthreads();                                                 // (red may still be read from the reduction before)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) r = red[w] < r ? red[w] : r;
-  return r;
-}
-__device__ __forceinline__ int block_sum_workgroup(int v, int (&red)[kBlock / 64]) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) r += red[w];
-  return r;
-}
 
 // segment s = bodies [s seg_len, min(n, (s + 1) seg_len)), seg_len a multiple of kBlock
 __global__ __launch_bounds__(kBlock) void hermite_block_next_kernel(const long long *__restrict__ T, const int *__restrict__ level, int n,
@@ -242,12 +217,20 @@ hipError_t launch_hermite_block_init(const HermiteBlockLaunch &L, const int *lev
   return hipGetLastError();
 }
 
+hipError_t launch_hermite_block_next(const long long *T, const int *level, int n, int levels, long long *seg_min, int *seg_cnt,
+                                     hipStream_t s) {
+  if (n <= 0 || levels < 0 || levels > kHermiteBlockMaxLevels || !T || !level || !seg_min || !seg_cnt) return hipErrorInvalidValue;
+  int slots;
+  const int seg_len = hermite_block_segment(n, &slots);
+  hipLaunchKernelGGL(hermite_block_next_kernel, dim3(slots), dim3(kBlock), 0, s, T, level, n, seg_len, levels, seg_min, seg_cnt);
+  return hipGetLastError();
+}
+
 hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_t s) {
   if (bad(L) || !L.xp || !L.vp) return hipErrorInvalidValue;
   int slots;
   const int seg_len = hermite_block_segment(L.n, &slots);
-  hipLaunchKernelGGL(hermite_block_next_kernel, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level, L.n, seg_len,
-                     L.levels, L.seg_min, L.seg_cnt);
+  if (hipError_t e = launch_hermite_block_next(L.T, L.level, L.n, L.levels, L.seg_min, L.seg_cnt, s)) return e;
   hipLaunchKernelGGL(hermite_block_list_kernel, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
                      (const long long *)L.seg_min, (const int *)L.seg_cnt, slots, L.n, seg_len, L.levels, L.tick, (const double4 *)L.posm,
                      (const double4 *)L.vel, (const double *)L.aj0, (double4 *)L.xp, (double4 *)L.vp, L.list, L.record);

@@ -540,6 +540,35 @@ class NBodyEngine:
         self._check(self._L.nbody_hermite6_get(self._h, out.ctypes.data, 144))
         return tuple(np.ascontiguousarray(out[:, 3 * k:3 * k + 3]) for k in range(6))
 
+    def hermite6_block_begin(self, dt_max, levels, eta=0.5, eta_start=0.01, level_in=None):
+        """Start a session of SIXTH-order Hermite block time steps at tick 0 (nbody_hermite6_block_begin): hermite_block_begin()'s ticks,
+        levels and frames around the sixth-order predictor, snap evaluation and corrector.  eta multiplies the sixth-root time scale
+        directly, as in hermite6_advance(): 0.3 .. 1 here does what 0.01 .. 0.04 does for hermite_block_begin().  level_in: n_total
+        levels to start from; None: from eta_start |a| / |j| per body.  The contexts of hermite6_step(); everything else: ERR_UNSUPPORTED."""
+        lv = None
+        if level_in is not None:
+            lv = np.ascontiguousarray(level_in, np.int32)
+            if lv.shape != (self.n_total,):
+                raise ValueError(f"level_in must hold {self.n_total} levels")
+        self._check(self._L.nbody_hermite6_block_begin(self._h, float(dt_max), int(levels), float(eta), float(eta_start),
+                                                       lv.ctypes.data if lv is not None else None))
+
+    def hermite6_block_advance(self, frames=1, max_block_steps=2 ** 62):
+        """Sixth-order block steps until `frames` more frame ends have been reached or max_block_steps have been taken
+        (nbody_hermite6_block_advance).  Returns the session's totals since begin as hermite_block_advance() does."""
+        st = _lib.HermiteBlockStats()
+        st.struct_size = ctypes.sizeof(st)
+        self._check(self._L.nbody_hermite6_block_advance(self._h, int(frames), int(max_block_steps), ctypes.byref(st)))
+        out = {name: int(getattr(st, name)) for name, _ in st._fields_ if name != "struct_size"}
+        out["synchronised"] = bool(out["synchronised"])
+        return out
+
+    def hermite6_block_state(self):
+        """(ticks [n_total] int64, levels [n_total] int32): every body's own time and level (nbody_hermite6_block_get)."""
+        ticks, level = np.empty(self.n_total, np.int64), np.empty(self.n_total, np.int32)
+        self._check(self._L.nbody_hermite6_block_get(self._h, ticks.ctypes.data, level.ctypes.data))
+        return ticks, level
+
     def set_tracers(self, pos, vel=None):
         """Massless tracers the engine advances with the bodies (nbody_set_tracers).  pos, vel: [n,3] or [n,4] float32 (a 4th column is
         ignored); vel None = at rest; an empty pos removes them.  Replaces any earlier set."""
