@@ -728,6 +728,83 @@ NBODY_AMD_API int nbody_hermite6_block_begin(nbody_ctx *ctx, double dt_max, int3
 NBODY_AMD_API int nbody_hermite6_block_advance(nbody_ctx *ctx, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out);
 NBODY_AMD_API int nbody_hermite6_block_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level);
 
+/*
+ * fp64 point queries and fp64 TRACERS on the shared-step Hermite calls (build-defined: the reference has neither) — what nbody_jerk_at and
+ * nbody_set_tracers are to fp32 contexts, for the contexts that answer nbody_hermite_step: NBODY_PREC_F64, one device, owning all bodies.
+ * NBODY_PREC_F32, NBODY_PREC_F32_KAHAN, slice and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED with a message that says why;
+ * no particles set, or a pending nbody_step_begin: NBODY_ERR_STATE.  nbody_field_at, nbody_potential_at, nbody_tidal_at, nbody_jerk_at,
+ * nbody_set_tracers and nbody_get_tracers stay what they were: fp32 only.
+ *
+ * The pair form.  A point at x moving with v (and, for the snap, with an INPUT acceleration acc) against ALL bodies j: d = x_j - x,
+ * w = v_j - v, b = acc_j - acc, s^2 = |d|^2 + eps^2, t = 1 / s — and then nbody_get_jerk_f64's and nbody_get_snap_f64's per-pair
+ * operations in their order, over their chunks (a function of n_total alone) and tiles, the chunks' rows added from 0.0 in chunk order:
+ *     A = G m_j d t^3      J = G m_j w t^3 - 3 al A      S = G m_j b t^3 - 6 al J - 3 be A      (al, be: as above)
+ * The ONE difference to the bodies' passes: NO pair is dropped by index.  The d == 0 rule is t = (s^2 > 0) ? 1 / s : 0 — with eps == 0 a
+ * point exactly on a body drops that pair from every sum; with eps > 0 that pair adds G m w / eps^3 to the jerk, G m b / eps^3 to the snap
+ * and nothing to a (what nbody_get_snap_f64 documents for coincident bodies).  A point's sums depend on the point and the bodies ALONE —
+ * not on n, the other points, the slab of the staging area the point falls into, the points per lane or the device; a body of mass 0
+ * adds exactly nothing.  So a body asked about at its own (x, v) gets nbody_get_jerk_f64's row IN EVERY BIT, and N bodies with M tracers
+ * equal, in every bit, a context that holds the tracers as M bodies of mass 0 appended behind them (while both have 256-body chunks:
+ * N + M <= 32768) — at N^2 + M N pairs a pass instead of (N + M)^2, and without the tracers entering the shared step.
+ *
+ * nbody_jerk_at_f64: a and j at n moving points from the LIVE (positions, velocities), unrounded fp64 sums.  pos, vel: 3 doubles per
+ *   point, strides >= 24 bytes; vel == NULL: at rest (the bits an array of zeros gives).  acc, jerk: 3 doubles per point, strides >= 24;
+ *   either may be NULL, not both.  n == 0: a no-op.  NULL pos, n < 0 or a stride too small: NBODY_ERR_INVALID.  Synchronises; changes
+ *   nothing a getter shows, leaves both Hermite caches and any block session alone; ONE pass under NBODY_KERNEL_FORCES.
+ *
+ * Tracers.  nbody_set_tracers_f64 replaces any earlier set (vel == NULL: at rest; n == 0 removes them; pos / vel as above); uploads keep
+ * the tracers, checkpoints do NOT store them (NBDYCKP2 stays byte for byte); nbody_get_tracers_f64 (either array may be NULL) followed by
+ * nbody_set_tracers_f64 restores them bit for bit.  Tracers never act on bodies or on each other: a context with tracers advances its
+ * bodies BYTE FOR BYTE as the same context without them — positions, velocities, accelerations, both caches, nbody_hermite_timescale
+ * and the dt nbody_hermite_advance picks.  They do NOT enter the shared step: a host that wants them to limit it reads
+ * nbody_hermite[6]_tracers_timescale and caps dt_max itself.
+ * ONLY nbody_hermite_step, nbody_hermite_advance, nbody_hermite6_step and nbody_hermite6_advance advance the fp64 tracers.  nbody_step,
+ * nbody_tick, nbody_step_begin / _end and nbody_compute_forces leave their state untouched (and, moving the bodies, invalidate their
+ * caches with the bodies').
+ *
+ * Fourth order, inside every step of nbody_hermite_step / nbody_hermite_advance — the tracers keep a cache (a0, j0, a2, a3) of their own:
+ *   predict    the step's dt and nbody_hermite_step's predictor on the tracers' (x, v, a0, j0)
+ *   evaluate   (a1, j1) of the predicted tracers against the bodies' PREDICTED (xp, vp) — the field the bodies' own evaluation uses
+ *   correct    nbody_hermite_step's corrector, every bracket one correctly rounded operation in its written order
+ *   entry      while the tracers' cache is invalid a call first evaluates (a0, j0) of the stored tracers against the stored bodies: one
+ *              pass more; a2 and a3 then read as zeros
+ * Sixth order, the same inside nbody_hermite6_step / _advance with a cache (a0, j0, s0, a3, a4, a5):
+ *   start      behind the bodies' own start, a point jerk pass gives the tracers' a, and ONE point snap pass with that a and the bodies'
+ *              cached a0 as its inputs gives the tracers' (a0, j0, s0): two passes more
+ *   step       the sixth-order predictor gives the tracers' own ap; one point snap pass against the bodies' (xp, vp, ap); the corrector
+ * Invalidation.  Whatever invalidates the bodies' cache of an order invalidates the tracers' cache of that order (the lists above, the
+ * other order's steps included); nbody_set_tracers_f64 invalidates BOTH tracer caches and only those; nbody_hermite_restart forgets all
+ * four; after nbody_bind_device_state or nbody_device_ptr every call evaluates the tracers anew at entry, as it does the bodies.
+ * Timers.  Every tracer evaluation is ONE MORE pass under NBODY_KERNEL_FORCES; the tracers' predictor and corrector add their time to
+ * the step's one pass under NBODY_KERNEL_UPDATE.  Without tracers every count is what it was.
+ *
+ * nbody_hermite_tracers_get / nbody_hermite6_tracers_get: the tracers' cache — 12 doubles (a0, j0, a2, a3; stride >= 96) / 18 doubles
+ *   (a0, j0, s0, a3, a4, a5; stride >= 144) per tracer, else NBODY_ERR_INVALID.  No tracers: a no-op.  NBODY_ERR_STATE while the tracers'
+ *   (a0, j0[, s0]) are invalid; the derivatives read as zeros until a step has been taken.  Synchronises.
+ * nbody_hermite_tracers_timescale / nbody_hermite6_tracers_timescale: nbody_hermite_timescale's / nbody_hermite6_timescale's criterion,
+ *   rules and fixed-order reduction over the TRACERS, by the same kernels: *kind = 1 from the derivatives; *kind = 0 |a| / |j| from
+ *   (a0, j0), which the call evaluates first if they are invalid.  *tracer: the lowest index that attains the maximum.  No tracers:
+ *   NBODY_ERR_STATE.  Any output may be NULL, not all three.  Synchronises; changes no position, velocity or acceleration of a body or
+ *   a tracer.  What it does change is the CACHES: it fills the tracers' cache of its order where that was invalid (one / two passes
+ *   under NBODY_KERNEL_FORCES; nbody_hermite[6]_tracers_get succeeds afterwards), and the SIXTH-order call, whose tracer start reads
+ *   the bodies' a0, first fills the bodies' sixth-order cache like nbody_hermite6_timescale does where that is invalid: two more passes
+ *   under NBODY_KERNEL_FORCES, the allocations of a first sixth-order call, and nbody_hermite6_get succeeds afterwards where it would
+ *   have reported NBODY_ERR_STATE.  The fourth-order call needs and touches nothing of the bodies' caches.
+ *
+ * Block sessions carry no fp64 tracers: nbody_hermite_block_begin and nbody_hermite6_block_begin report NBODY_ERR_UNSUPPORTED on a
+ * context that holds some — nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them —, and nbody_set_tracers_f64 with n > 0 reports
+ * NBODY_ERR_STATE while a block session of either order is active.
+ */
+NBODY_AMD_API int nbody_jerk_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
+                                    double *acc, size_t acc_stride, double *jerk, size_t jerk_stride);
+NBODY_AMD_API int nbody_set_tracers_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n);
+NBODY_AMD_API int nbody_get_tracers_f64(nbody_ctx *ctx, double *pos, size_t pos_stride, double *vel, size_t vel_stride);
+NBODY_AMD_API int nbody_tracer_count_f64(nbody_ctx *ctx, int32_t *n);
+NBODY_AMD_API int nbody_hermite_tracers_get(nbody_ctx *ctx, double *d12, size_t stride);
+NBODY_AMD_API int nbody_hermite6_tracers_get(nbody_ctx *ctx, double *d18, size_t stride);
+NBODY_AMD_API int nbody_hermite_tracers_timescale(nbody_ctx *ctx, double *t_min, int32_t *tracer, int32_t *kind);
+NBODY_AMD_API int nbody_hermite6_tracers_timescale(nbody_ctx *ctx, double *t_min, int32_t *tracer, int32_t *kind);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

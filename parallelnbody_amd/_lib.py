@@ -191,6 +191,14 @@ def lib():
     sig("nbody_hermite6_block_begin", c_int, vp, c_d, c_i32, c_d, c_d, vp)
     sig("nbody_hermite6_block_advance", c_int, vp, c_i64, c_i64, ctypes.POINTER(HermiteBlockStats))
     sig("nbody_hermite6_block_get", c_int, vp, vp, vp)
+    sig("nbody_jerk_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, sz, vp, sz)
+    sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
+    sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
+    sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))
+    sig("nbody_hermite_tracers_get", c_int, vp, vp, sz)
+    sig("nbody_hermite6_tracers_get", c_int, vp, vp, sz)
+    sig("nbody_hermite_tracers_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
+    sig("nbody_hermite6_tracers_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

@@ -618,7 +618,7 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite, c->hblock})
     if (q) (void)hipFree(q);
-  for (void *q : {c->hermite6, c->snap64, c->h6block})
+  for (void *q : {c->hermite6, c->snap64, c->h6block, c->tr64, c->tr64_h4, c->tr64_h6})
     if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
@@ -1786,18 +1786,116 @@ int hermite_enter(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE
+// ---- the fp64 tracers of the shared-step Hermite calls (nbody_set_tracers_f64; kernels_points64.hip) ----
+// Massless points with a state and caches of their own, laid out like the bodies' (ctx.h).  They are predicted with the step's dt,
+// evaluated by the point kernels in the field of the bodies' PREDICTED state — the field the bodies' own evaluation uses — and corrected
+// by the bodies' kernels on the tracers' arrays.  Nothing of theirs is read by anything the bodies get.
+struct Tracer64Bufs { double *pos, *vel, *acc, *xp, *vp, *ap; };
+Tracer64Bufs tracer64_bufs(const nbody_ctx *c) {
+  const size_t m = (size_t)c->tr64_n;
+  double *b = (double *)c->tr64;
+  return Tracer64Bufs{b, b + 4 * m, b + 8 * m, b + 12 * m, b + 16 * m, b + 20 * m};
+}
+struct TracerH4Bufs { double *a2, *a3, *aj[2], *partials; };
+TracerH4Bufs tracer_h4_bufs(const nbody_ctx *c) {
+  const size_t m = (size_t)c->tr64_n;
+  double *b = (double *)c->tr64_h4;
+  return TracerH4Bufs{b, b + 4 * m, {b + 8 * m, b + 14 * m}, b + 20 * m};
+}
+struct TracerH6Bufs { double *a3, *a4, *a5, *ajs[2], *partials; };
+TracerH6Bufs tracer_h6_bufs(const nbody_ctx *c) {
+  const size_t m = (size_t)c->tr64_n;
+  double *b = (double *)c->tr64_h6;
+  return TracerH6Bufs{b, b + 4 * m, b + 8 * m, {b + 12 * m, b + 21 * m}, b + 30 * m};
+}
+
+// a point pass is never queued into a staging area that does not hold a slab's partial rows
+int points64_part_holds(nbody_ctx *c, int m, int width, const char *what) {
+  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
+  if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
+  return fail(c, NBODY_ERR_STATE, "%s: the partial rows of %d points need %zu float4, the staging area holds %zu", what, m, need, c->probe_part_elems);
+}
+
+// (a, j) at m points (ppos, pvel: double4 each, device) in the field of the bodies at (posm, vel) — the live state or the predicted one —
+// into aj64 ([m][6]), queued as one pass under NBODY_KERNEL_FORCES
+int points64_jerk(nbody_ctx *c, const void *posm, const void *vel, const void *ppos, const void *pvel, int m, double *aj64) {
+  if (int rc = points64_part_holds(c, m, 3, "the point jerk pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Points64Launch L;
+    L.posm = posm; L.vel = vel; L.ppos = ppos; L.pvel = pvel; L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = aj64;
+    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, nbody::launch_jerk_points_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// (a, j, s) the same way, given the bodies' input accelerations (ain) and the points' (pain), into ajs64 ([m][9])
+int points64_snap(nbody_ctx *c, const void *posm, const void *vel, const double *ain, int ain_stride, const void *ppos, const void *pvel,
+                  const double *pain, int pain_stride, int m, double *ajs64) {
+  if (int rc = points64_part_holds(c, m, nbody::kSnapRowWidth, "the point snap pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Points64Launch L;
+    L.posm = posm; L.vel = vel; L.ain = ain; L.ain_stride = ain_stride; L.ppos = ppos; L.pvel = pvel; L.pain = pain; L.pain_stride = pain_stride;
+    L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = ajs64;
+    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, nbody::launch_snap_points_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// what a fourth-order call does for the tracers behind hermite_enter (which has applied the hm_external rule): the cache and the partial
+// rows at first use; (a0, j0) of the stored tracers in the stored bodies' field when they are not valid — one more pass —, zeros for a2, a3
+int hermite_tracers_enter(nbody_ctx *c) {
+  const int m = c->tr64_n;
+  if (m <= 0) return NBODY_OK;
+  if (!c->tr64_h4) HIP_TRY(c, hipMalloc(&c->tr64_h4, (20 * (size_t)m + 2 * (size_t)nbody::energy_fast_slots(m)) * sizeof(double)));
+  if (int rc = ensure_probe_part(c, m, 3)) return rc;
+  if (c->trh_valid) return NBODY_OK;
+  const Tracer64Bufs t = tracer64_bufs(c);
+  const TracerH4Bufs q = tracer_h4_bufs(c);
+  if (int rc = points64_jerk(c, c->posm, c->vel, t.pos, t.vel, m, q.aj[c->trh_cur])) return rc;
+  HIP_TRY(c, hipMemsetAsync(q.a2, 0, 8 * (size_t)m * sizeof(double), c->stream));   // a2 and a3 lie side by side
+  c->trh_valid = true;
+  c->trh_derivs = false;
+  return NBODY_OK;
+}
+
+// the tracers' arrays as the stepping kernels of kernels_hermite.hip take the bodies'
+nbody::HermiteLaunch hermite_tracers_launch(const nbody_ctx *c, double dt) {
+  const Tracer64Bufs t = tracer64_bufs(c);
+  const TracerH4Bufs q = tracer_h4_bufs(c);
+  nbody::HermiteLaunch L;
+  L.posm = t.pos; L.vel = t.vel; L.acc = t.acc; L.xp = t.xp; L.vp = t.vp; L.aj0 = q.aj[c->trh_cur]; L.aj1 = q.aj[c->trh_cur ^ 1];
+  L.a2 = q.a2; L.a3 = q.a3; L.n = c->tr64_n; L.dt = dt;
+  return L;
+}
+
+// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE.
+// With fp64 tracers (their cache valid: hermite_tracers_enter) the tracers' predictor and corrector ride in the same two goes, and their
+// evaluation at the bodies' predicted state is one more pass under NBODY_KERNEL_FORCES.
 int hermite_one_step(nbody_ctx *c, double dt) {
   const HermiteBufs b = hermite_bufs(c);
   nbody::HermiteLaunch L;
   L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.aj0 = b.aj[c->hm_cur]; L.aj1 = b.aj[c->hm_cur ^ 1];
   L.a2 = b.a2; L.a3 = b.a3; L.n = c->p.n_total; L.dt = dt;
+  const bool tracers = c->tr64_n > 0;
+  const nbody::HermiteLaunch T = tracers ? hermite_tracers_launch(c, dt) : nbody::HermiteLaunch{};
   int rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_predict(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+        HIP_TRY(c, nbody::launch_hermite_predict(L, c->stream));
+        if (tracers) HIP_TRY(c, nbody::launch_hermite_predict(T, c->stream));
+        return NBODY_OK;
+      }, false))) return rc;
   if ((rc = hermite_evaluate(c, b.xp, b.vp, b.aj[c->hm_cur ^ 1]))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_correct(L, c->stream)); return NBODY_OK; }))) return rc;
+  if (tracers && (rc = points64_jerk(c, b.xp, b.vp, T.xp, T.vp, T.n, tracer_h4_bufs(c).aj[c->trh_cur ^ 1]))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+        HIP_TRY(c, nbody::launch_hermite_correct(L, c->stream));
+        if (tracers) HIP_TRY(c, nbody::launch_hermite_correct(T, c->stream));
+        return NBODY_OK;
+      }))) return rc;
   c->hm_cur ^= 1;                                                  // (a0, j0) := (a1, j1)
   c->hm_derivs = true;
+  if (tracers) { c->trh_cur ^= 1; c->trh_derivs = true; }
   c->sym_posg_valid = false;
   c->steps_done += 1;
   return NBODY_OK;
@@ -1828,6 +1926,7 @@ int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if ((rc = hermite_block_leave(c, "nbody_hermite_step"))) return rc;
   if ((rc = hermite6_block_leave(c, "nbody_hermite_step"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
+  if ((rc = hermite_tracers_enter(c))) return rc;
   nbody::hermite6_invalidate(c);                                   // (the state moves on without the sixth-order cache)
   for (int s = 0; s < nsteps; ++s)
     if ((rc = hermite_one_step(c, dt))) return rc;
@@ -1864,6 +1963,7 @@ int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_st
   if ((rc = hermite_block_leave(c, "nbody_hermite_advance"))) return rc;
   if ((rc = hermite6_block_leave(c, "nbody_hermite_advance"))) return rc;
   if ((rc = hermite_enter(c))) return rc;
+  if ((rc = hermite_tracers_enter(c))) return rc;
   nbody::hermite6_invalidate(c);
   const double root_eta = std::sqrt(eta);
   while (t_acc < t_span && taken < max_steps) {
@@ -2013,6 +2113,9 @@ int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, doubl
   const double tick = std::ldexp(dt_max, -levels);
   if (!std::isnormal(tick))
     return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: the tick dt_max 2^-levels = %g is not a normal number", tick);
+  if (c->tr64_n > 0)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_hermite_block_begin: the context holds %d fp64 tracers, which the block scheduler does not "
+                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them", c->tr64_n);
   const int n = c->p.n_total;
   if (level_in)
     for (int i = 0; i < n; ++i)
@@ -2322,18 +2425,64 @@ int hermite6_enter(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE
+// what a sixth-order call does for the fp64 tracers behind hermite6_enter (the bodies' cache is valid, the hm_external rule applied): the
+// cache and the partial rows of both passes at first use; when the tracers' (a0, j0, s0) are not valid, a point jerk pass for the
+// tracers' a and one point snap pass with it and the bodies' cached a0 (the input accelerations of the bodies' own next step: at a start
+// the bodies' jerk pass's, in every bit) as its inputs — two more passes —, and zeros for a3, a4, a5
+int hermite6_tracers_enter(nbody_ctx *c) {
+  const int m = c->tr64_n;
+  if (m <= 0) return NBODY_OK;
+  if (!c->tr64_h6) HIP_TRY(c, hipMalloc(&c->tr64_h6, (30 * (size_t)m + 2 * (size_t)nbody::energy_fast_slots(m)) * sizeof(double)));
+  if (int rc = ensure_probe_part(c, m, 3)) return rc;
+  if (int rc = ensure_probe_part(c, m, nbody::kSnapRowWidth)) return rc;
+  if (c->trh6_valid) return NBODY_OK;
+  const Tracer64Bufs t = tracer64_bufs(c);
+  const TracerH6Bufs q = tracer_h6_bufs(c);
+  double *aj = q.ajs[c->trh6_cur ^ 1];                            // (the jerk pass's six doubles per tracer, in the row a step overwrites)
+  if (int rc = points64_jerk(c, c->posm, c->vel, t.pos, t.vel, m, aj)) return rc;
+  if (int rc = points64_snap(c, c->posm, c->vel, hermite6_bufs(c).ajs[c->h6_cur], 9, t.pos, t.vel, aj, 6, m, q.ajs[c->trh6_cur])) return rc;
+  HIP_TRY(c, hipMemsetAsync(q.a3, 0, 12 * (size_t)m * sizeof(double), c->stream));
+  c->trh6_valid = true;
+  c->trh6_derivs = false;
+  return NBODY_OK;
+}
+
+// the tracers' arrays as the stepping kernels of kernels_snap.hip take the bodies'
+nbody::Hermite6Launch hermite6_tracers_launch(const nbody_ctx *c, double dt) {
+  const Tracer64Bufs t = tracer64_bufs(c);
+  const TracerH6Bufs q = tracer_h6_bufs(c);
+  nbody::Hermite6Launch L;
+  L.posm = t.pos; L.vel = t.vel; L.acc = t.acc; L.xp = t.xp; L.vp = t.vp; L.ap = t.ap; L.ajs0 = q.ajs[c->trh6_cur]; L.ajs1 = q.ajs[c->trh6_cur ^ 1];
+  L.a3 = q.a3; L.a4 = q.a4; L.a5 = q.a5; L.n = c->tr64_n; L.dt = dt;
+  return L;
+}
+
+// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE.
+// With fp64 tracers (their cache valid: hermite6_tracers_enter) the tracers' predictor and corrector ride in the same two goes; their
+// point snap pass at the bodies' predicted (xp, vp, ap), with their own predicted accelerations, is one more pass under NBODY_KERNEL_FORCES.
 int hermite6_one_step(nbody_ctx *c, double dt) {
   const Hermite6Bufs b = hermite6_bufs(c);
   nbody::Hermite6Launch L;
   L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.ap = b.ap; L.ajs0 = b.ajs[c->h6_cur]; L.ajs1 = b.ajs[c->h6_cur ^ 1];
   L.a3 = b.a3; L.a4 = b.a4; L.a5 = b.a5; L.n = c->p.n_total; L.dt = dt;
+  const bool tracers = c->tr64_n > 0;
+  const nbody::Hermite6Launch T = tracers ? hermite6_tracers_launch(c, dt) : nbody::Hermite6Launch{};
   int rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_predict(L, c->stream)); return NBODY_OK; }, false))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+        HIP_TRY(c, nbody::launch_hermite6_predict(L, c->stream));
+        if (tracers) HIP_TRY(c, nbody::launch_hermite6_predict(T, c->stream));
+        return NBODY_OK;
+      }, false))) return rc;
   if ((rc = snap_evaluate(c, b.xp, b.vp, b.ap, 4, b.ajs[c->h6_cur ^ 1]))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_correct(L, c->stream)); return NBODY_OK; }))) return rc;
+  if (tracers && (rc = points64_snap(c, b.xp, b.vp, b.ap, 4, T.xp, T.vp, (const double *)T.ap, 4, T.n, tracer_h6_bufs(c).ajs[c->trh6_cur ^ 1]))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+        HIP_TRY(c, nbody::launch_hermite6_correct(L, c->stream));
+        if (tracers) HIP_TRY(c, nbody::launch_hermite6_correct(T, c->stream));
+        return NBODY_OK;
+      }))) return rc;
   c->h6_cur ^= 1;                                                  // (a0, j0, s0) := (a1, j1, s1)
   c->h6_derivs = true;
+  if (tracers) { c->trh6_cur ^= 1; c->trh6_derivs = true; }
   nbody::hermite_invalidate(c);                                    // the fourth-order cache is not this state's
   c->sym_posg_valid = false;
   c->steps_done += 1;
@@ -2398,6 +2547,7 @@ int nbody_hermite6_step(nbody_ctx *c, double dt, int32_t nsteps) {
   if ((rc = hermite_block_leave(c, "nbody_hermite6_step"))) return rc;
   if ((rc = hermite6_block_leave(c, "nbody_hermite6_step"))) return rc;
   if ((rc = hermite6_enter(c))) return rc;
+  if ((rc = hermite6_tracers_enter(c))) return rc;
   for (int s = 0; s < nsteps; ++s)
     if ((rc = hermite6_one_step(c, dt))) return rc;
   return NBODY_OK;
@@ -2433,6 +2583,7 @@ int nbody_hermite6_advance(nbody_ctx *c, double t_span, double eta, double eta_s
   if ((rc = hermite_block_leave(c, "nbody_hermite6_advance"))) return rc;
   if ((rc = hermite6_block_leave(c, "nbody_hermite6_advance"))) return rc;
   if ((rc = hermite6_enter(c))) return rc;
+  if ((rc = hermite6_tracers_enter(c))) return rc;
   while (t_acc < t_span && taken < max_steps) {
     double t = 0.0;
     int32_t at = 0, which = 0;
@@ -2472,6 +2623,220 @@ int nbody_hermite6_get(nbody_ctx *c, double *d18, size_t stride) {
     for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * n + i), 24);   // (zeros until a step has been taken)
     memcpy((char *)d18 + i * stride, rec, 144);
   }
+  return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---- fp64 point queries and the fp64 tracers' public calls (kernels_points64.hip) ----
+namespace {
+// where they exist — the contexts that answer nbody_hermite_step: fp64 state, one device, all bodies — and when: a state set, no step half done
+int points64_ready(nbody_ctx *c, const char *who) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (c->multi) return multi_unsupported(c, who);
+  if (c->p.precision != NBODY_PREC_F64)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): its points are doubles "
+                "in the field of fp64 bodies; create the context with NBODY_PREC_F64 (fp32 contexts have nbody_jerk_at and nbody_set_tracers)", who);
+  if (c->p.i_count != c->p.n_total)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
+  if (int rc = check_ready(c)) return rc;
+  if (c->step_open || c->step_local) return fail(c, NBODY_ERR_STATE, "%s: a step is open (nbody_step_end first)", who);
+  return NBODY_OK;
+}
+
+// n records of three doubles, `stride` bytes apart (NULL: zeros), as double4 rows with a fourth component of 0
+void gather_double4(double *dst, const double *src, size_t stride, size_t n) {
+  for (size_t k = 0; k < n; ++k) {
+    if (src) memcpy(dst + 4 * k, (const char *)src + k * stride, 24);
+    else     dst[4 * k] = dst[4 * k + 1] = dst[4 * k + 2] = 0.0;
+    dst[4 * k + 3] = 0.0;
+  }
+}
+
+// the time scale of the tracers' cached derivatives, waited for — hermite_scale / hermite6_scale over the tracers' arrays
+int hermite_tracers_scale(nbody_ctx *c, double *t, int32_t *at, int32_t *kind) {
+  const TracerH4Bufs q = tracer_h4_bufs(c);
+  const int m = c->tr64_n;
+  if (c->trh_derivs) HIP_TRY(c, nbody::launch_hermite_time(q.aj[c->trh_cur], q.a2, q.a3, m, q.partials, (double *)c->scratch, c->stream));
+  else               HIP_TRY(c, nbody::launch_jerk_time(q.aj[c->trh_cur], m, q.partials, (double *)c->scratch, c->stream));
+  double k = 0.0, where = 0.0;
+  if (int rc = read_energy(c, &k, &where)) return rc;
+  *t = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
+  *at = (int32_t)where;
+  *kind = c->trh_derivs ? 1 : 0;
+  return NBODY_OK;
+}
+int hermite6_tracers_scale(nbody_ctx *c, double *t, int32_t *at, int32_t *kind) {
+  const TracerH6Bufs q = tracer_h6_bufs(c);
+  HIP_TRY(c, nbody::launch_hermite6_time(q.ajs[c->trh6_cur], q.a3, q.a4, q.a5, c->tr64_n, c->trh6_derivs, q.partials, (double *)c->scratch, c->stream));
+  double k = 0.0, where = 0.0;
+  if (int rc = read_energy(c, &k, &where)) return rc;
+  if (k == 0.0) *t = HUGE_VAL;
+  else if (!std::isfinite(k)) *t = 0.0;
+  else *t = c->trh6_derivs ? 1.0 / std::cbrt(std::sqrt(k)) : 1.0 / std::sqrt(k);
+  *at = (int32_t)where;
+  *kind = c->trh6_derivs ? 1 : 0;
+  return NBODY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbody_jerk_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n, double *acc,
+                      size_t acc_stride, double *jerk, size_t jerk_stride) {
+  const char *who = "nbody_jerk_at_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || (vel && vel_stride < 24) || (!acc && !jerk) || (acc && acc_stride < 24) || (jerk && jerk_stride < 24))
+    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, both outputs null, or a stride < 24", who);
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n;
+  if ((rc = ensure_probe_part(c, n, 3))) return rc;
+  if ((rc = ensure_stage(c, m * 14 * sizeof(double)))) return rc;   // the points and their velocities as double4, behind them six doubles per point
+  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
+  gather_double4(h, pos, pos_stride, m);
+  gather_double4(h + 4 * m, vel, vel_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(d, h, m * 64, hipMemcpyHostToDevice, c->stream));
+  if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + 8 * m, d + 8 * m, m * 48, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (acc) scatter_records(acc, acc_stride, h + 8 * m, 24, m, 48);
+  if (jerk) scatter_records(jerk, jerk_stride, h + 8 * m + 3, 24, m, 48);
+  return NBODY_OK;
+}
+
+int nbody_set_tracers_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n) {
+  const char *who = "nbody_set_tracers_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!pos || pos_stride < 24 || (vel && vel_stride < 24))))
+    return fail(c, NBODY_ERR_INVALID, "%s: n < 0, null positions, or a stride < 24", who);
+  if (n > 0 && (c->hb.active || c->h6b.active))
+    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is active, and the block scheduler carries no tracers; nbody_hermite_restart "
+                "ends the session", who);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (void **q : {&c->tr64, &c->tr64_h4, &c->tr64_h6}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+  c->tr64_n = 0;
+  c->trh_valid = c->trh_derivs = c->trh6_valid = c->trh6_derivs = false;   // the tracers' caches, and only those
+  c->trh_cur = c->trh6_cur = 0;
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n;
+  if ((rc = ensure_stage(c, m * 64))) return rc;
+  HIP_TRY(c, hipMalloc(&c->tr64, 24 * m * sizeof(double)));
+  double *h = (double *)c->h_stage;
+  gather_double4(h, pos, pos_stride, m);
+  gather_double4(h + 4 * m, vel, vel_stride, m);
+  HIP_TRY(c, hipMemsetAsync(c->tr64, 0, 24 * m * sizeof(double), c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->tr64, h, m * 64, hipMemcpyHostToDevice, c->stream));   // pos and vel lie side by side
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->tr64_n = n;
+  return NBODY_OK;
+}
+
+int nbody_get_tracers_f64(nbody_ctx *c, double *pos, size_t pos_stride, double *vel, size_t vel_stride) {
+  const char *who = "nbody_get_tracers_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if ((pos && pos_stride < 24) || (vel && vel_stride < 24)) return fail(c, NBODY_ERR_INVALID, "%s: a stride < 24", who);
+  const size_t m = (size_t)c->tr64_n;
+  if (m == 0 || (!pos && !vel)) return NBODY_OK;
+  if ((rc = ensure_stage(c, m * 64))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->tr64, m * 64, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const double *h = (const double *)c->h_stage;
+  if (pos) scatter_records(pos, pos_stride, h, 24, m, 32);
+  if (vel) scatter_records(vel, vel_stride, h + 4 * m, 24, m, 32);
+  return NBODY_OK;
+}
+
+int nbody_tracer_count_f64(nbody_ctx *c, int32_t *n) {
+  int rc = points64_ready(c, "nbody_tracer_count_f64");
+  if (rc) return rc;
+  if (!n) return fail(c, NBODY_ERR_INVALID, "nbody_tracer_count_f64: null output");
+  *n = c->tr64_n;
+  return NBODY_OK;
+}
+
+int nbody_hermite_tracers_get(nbody_ctx *c, double *d12, size_t stride) {
+  int rc = points64_ready(c, "nbody_hermite_tracers_get");
+  if (rc) return rc;
+  if (!d12 || stride < 96) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_tracers_get: null buffer or stride < 96");
+  const size_t m = (size_t)c->tr64_n;
+  if (m == 0) return NBODY_OK;
+  if (!c->tr64_h4 || !c->trh_valid)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite_tracers_get: no derivatives cached for the stored tracers (nbody_hermite_step or "
+                "nbody_hermite_tracers_timescale first)");
+  const TracerH4Bufs q = tracer_h4_bufs(c);
+  if ((rc = ensure_stage(c, m * 112))) return rc;
+  double *h_aj = (double *)c->h_stage, *h_d = h_aj + 6 * m;       // (a2 and a3 lie side by side: 8 doubles per tracer in all)
+  HIP_TRY(c, hipMemcpyAsync(h_aj, q.aj[c->trh_cur], m * 48, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_d, q.a2, m * 64, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < m; ++i) {
+    double rec[12];
+    memcpy(rec, h_aj + 6 * i, 48);
+    memcpy(rec + 6, h_d + 4 * i, 24);                              // (zeros until a step has been taken)
+    memcpy(rec + 9, h_d + 4 * (m + i), 24);
+    memcpy((char *)d12 + i * stride, rec, 96);
+  }
+  return NBODY_OK;
+}
+
+int nbody_hermite6_tracers_get(nbody_ctx *c, double *d18, size_t stride) {
+  int rc = points64_ready(c, "nbody_hermite6_tracers_get");
+  if (rc) return rc;
+  if (!d18 || stride < 144) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_tracers_get: null buffer or stride < 144");
+  const size_t m = (size_t)c->tr64_n;
+  if (m == 0) return NBODY_OK;
+  if (!c->tr64_h6 || !c->trh6_valid)
+    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_tracers_get: no derivatives cached for the stored tracers (nbody_hermite6_step or "
+                "nbody_hermite6_tracers_timescale first)");
+  const TracerH6Bufs q = tracer_h6_bufs(c);
+  if ((rc = ensure_stage(c, m * 168))) return rc;
+  double *h_ajs = (double *)c->h_stage, *h_d = h_ajs + 9 * m;     // (a3, a4 and a5 lie side by side: 12 doubles per tracer in all)
+  HIP_TRY(c, hipMemcpyAsync(h_ajs, q.ajs[c->trh6_cur], m * 72, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_d, q.a3, m * 96, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < m; ++i) {
+    double rec[18];
+    memcpy(rec, h_ajs + 9 * i, 72);
+    for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * m + i), 24);   // (zeros until a step has been taken)
+    memcpy((char *)d18 + i * stride, rec, 144);
+  }
+  return NBODY_OK;
+}
+
+int nbody_hermite_tracers_timescale(nbody_ctx *c, double *t_min, int32_t *tracer, int32_t *kind) {
+  const char *who = "nbody_hermite_tracers_timescale";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!t_min && !tracer && !kind) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
+  if (c->tr64_n <= 0) return fail(c, NBODY_ERR_STATE, "%s: the context holds no fp64 tracers (nbody_set_tracers_f64 first)", who);
+  if (c->hm_external) { nbody::hermite_invalidate(c); nbody::hermite6_invalidate(c); }
+  if ((rc = hermite_tracers_enter(c))) return rc;                  // (a0, j0) of the stored tracers, if they are not valid: the bodies' cache is not needed
+  double t = 0.0;
+  int32_t at = 0, which = 0;
+  if ((rc = hermite_tracers_scale(c, &t, &at, &which))) return rc;
+  if (t_min) *t_min = t;
+  if (tracer) *tracer = at;
+  if (kind) *kind = which;
+  return NBODY_OK;
+}
+
+int nbody_hermite6_tracers_timescale(nbody_ctx *c, double *t_min, int32_t *tracer, int32_t *kind) {
+  const char *who = "nbody_hermite6_tracers_timescale";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!t_min && !tracer && !kind) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
+  if (c->tr64_n <= 0) return fail(c, NBODY_ERR_STATE, "%s: the context holds no fp64 tracers (nbody_set_tracers_f64 first)", who);
+  if ((rc = hermite6_enter(c))) return rc;                         // the tracers' start reads the bodies' a0
+  if ((rc = hermite6_tracers_enter(c))) return rc;
+  double t = 0.0;
+  int32_t at = 0, which = 0;
+  if ((rc = hermite6_tracers_scale(c, &t, &at, &which))) return rc;
+  if (t_min) *t_min = t;
+  if (tracer) *tracer = at;
+  if (kind) *kind = which;
   return NBODY_OK;
 }
 
@@ -2562,6 +2927,9 @@ int nbody_hermite6_block_begin(nbody_ctx *c, double dt_max, int32_t levels, doub
   if (!std::isnormal(tick) || !std::isnormal((tick * tick) * tick))
     return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: the tick dt_max 2^-levels = %g or its cube, which the level rule compares, is not "
                 "a normal number", tick);
+  if (c->tr64_n > 0)
+    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_hermite6_block_begin: the context holds %d fp64 tracers, which the block scheduler does not "
+                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them", c->tr64_n);
   const int n = c->p.n_total;
   if (level_in)
     for (int i = 0; i < n; ++i)

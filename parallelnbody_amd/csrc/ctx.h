@@ -133,6 +133,15 @@ struct nbody_ctx {
     double dt_max = 0.0, tick = 0.0, eta = 0.0;
     int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
   } h6b;
+  // fp64 tracers (nbody_set_tracers_f64, kernels_points64.hip): massless points the four shared-step Hermite calls carry beside the
+  // bodies.  tr64 holds, in doubles, pos, vel, acc, xp, vp, ap ([tr64_n] double4 each).  Each order's cache is allocated at first use and
+  // laid out like the bodies': tr64_h4 = a2, a3 ([tr64_n] double4 each), two rows of (a, j) ([tr64_n][6] each: trh_cur is (a0, j0)),
+  // the reduction's workgroup pairs; tr64_h6 = a3, a4, a5, two rows of (a, j, s) ([tr64_n][9] each: trh6_cur), the workgroup pairs.
+  int tr64_n = 0;
+  void *tr64 = nullptr, *tr64_h4 = nullptr, *tr64_h6 = nullptr;
+  int trh_cur = 0, trh6_cur = 0;
+  bool trh_valid = false, trh6_valid = false;     // the tracers' (a0, j0) / (a0, j0, s0) are those of the stored tracers in the stored bodies' field
+  bool trh_derivs = false, trh6_derivs = false;   // a2, a3 / a3, a4, a5 are those a step left (zeros otherwise)
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
@@ -170,11 +179,19 @@ inline int use_device(nbody_ctx *c) {
 
 // The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): the
 // cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3; a block session ends.
-inline void hermite_invalidate(nbody_ctx *c) { c->hm_valid = false; c->hm_derivs = false; c->hb.active = false; }
+// The fp64 tracers' fourth-order cache goes with the bodies': it was evaluated in the field of a state that is no longer the stored one.
+inline void hermite_invalidate(nbody_ctx *c) {
+  c->hm_valid = false; c->hm_derivs = false; c->hb.active = false;
+  c->trh_valid = false; c->trh_derivs = false;
+}
 // The same for the sixth-order cache, which every caller of hermite_invalidate forgets as well — and so do the fourth-order calls that
 // step the state (nbody_hermite_step, nbody_hermite_advance, nbody_hermite_block_begin), whose cache a sixth-order step forgets in turn.
 // A sixth-order block session lives on that cache and ends with it.
-inline void hermite6_invalidate(nbody_ctx *c) { c->h6_valid = false; c->h6_derivs = false; c->h6b.active = false; }
+// The fp64 tracers' sixth-order cache goes with it.
+inline void hermite6_invalidate(nbody_ctx *c) {
+  c->h6_valid = false; c->h6_derivs = false; c->h6b.active = false;
+  c->trh6_valid = false; c->trh6_derivs = false;
+}
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
 constexpr size_t kTimerPendingCap = 1024;   // live event pairs per timer before a drain

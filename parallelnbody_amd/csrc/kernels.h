@@ -291,6 +291,35 @@ hipError_t launch_hermite6_block_schedule(const Hermite6BlockLaunch &L, hipStrea
 hipError_t launch_hermite6_block_evaluate(const Hermite6BlockLaunch &L, int first, int m, int lanes, hipStream_t s);
 hipError_t launch_hermite6_block_correct(const Hermite6BlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
 
+// The fp64 jerk and snap passes at m points that are not bodies — kernels_points64.hip: launch_jerk's / launch_snap's pair sums on fp64
+// state with the i side taken from (ppos, pvel[, pain]) instead of from the bodies, over the same chunks and tiles in the same order,
+// but with NO pair dropped by index: t = (s2 > 0) ? rsq(s2) : 0.  eps2 == 0: a point exactly on a body drops that pair; eps2 > 0: that
+// pair adds G m w / eps^3 to the jerk, G m b / eps^3 to the snap and nothing to a.  A point's sums depend on the point and the bodies
+// alone (not on m, the other points, the slab or the points per lane); a zero-mass body adds exactly nothing.  The points go in slabs
+// of probe_slab_points(n_total, 3) (kSnapRowWidth: the snap); the rows are folded by launch_jerk_fold_f64 / launch_snap_fold_f64.
+struct Points64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *vel = nullptr;    // [n_total] double4: vx, vy, vz, unused
+  const double *ain = nullptr;  // the snap: body j's input acceleration, ain[j * ain_stride + 0 .. 2]
+  int ain_stride = 0;           // in doubles, >= 3
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused
+  const void *pvel = nullptr;   // [m] double4: vx, vy, vz, unused
+  const double *pain = nullptr; // the snap: point k's input acceleration, pain[k * pain_stride + 0 .. 2]
+  int pain_stride = 0;          // in doubles, >= 3 (4: double4 rows; 6: the jerk's rows)
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 3 / kSnapRowWidth), or nothing is launched
+  double *out = nullptr;        // [m][6]: ax, ay, az, jx, jy, jz — the snap: [m][9], sx, sy, sz behind them
+  int n_total = 0, m = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no sum.
+  double G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_jerk_points_f64(const Points64Launch &L, hipStream_t s);
+hipError_t launch_snap_points_f64(const Points64Launch &L, hipStream_t s);
+// jerk_fold_f64_kernel / snap_fold_f64_kernel on their own: out[k][0 .. 6) / [0 .. 9) = the rows part[(c * m + k) * 6 / 9] added from 0.0
+// in chunk order
+hipError_t launch_jerk_fold_f64(const void *part, int m, int j_split, double *aj64, hipStream_t s);
+hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *ajs64, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

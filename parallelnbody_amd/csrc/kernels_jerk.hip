@@ -227,6 +227,14 @@ hipError_t launch_jerk(const JerkLaunch &L, hipStream_t s) {
   return hipGetLastError();
 }
 
+// jerk_fold_f64_kernel on its own, for the rows another file's kernel wrote in this layout (kernels_points64.hip: the point form)
+hipError_t launch_jerk_fold_f64(const void *part, int m, int j_split, double *aj64, hipStream_t s) {
+  if (m <= 0 || j_split <= 0 || !part || !aj64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(jerk_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)part, m, j_split, aj64,
+                     (float *)nullptr);
+  return hipGetLastError();
+}
+
 hipError_t launch_jerk_time(const double *aj64, int n, double *partials, double *out, hipStream_t s) {
   if (n <= 0 || !aj64 || !partials || !out) return hipErrorInvalidValue;
   const int slots = energy_fast_slots(n);

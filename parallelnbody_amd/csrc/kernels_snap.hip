@@ -182,6 +182,13 @@ hipError_t launch_snap(const SnapLaunch &L, hipStream_t s) {
   return hipGetLastError();
 }
 
+// snap_fold_f64_kernel on its own, for the rows another file's kernel wrote in this layout (kernels_points64.hip: the point form)
+hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *ajs64, hipStream_t s) {
+  if (m <= 0 || j_split <= 0 || !part || !ajs64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(snap_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)part, m, j_split, ajs64);
+  return hipGetLastError();
+}
+
 // the constants are the host's own doubles — products and one quotient each, in the order written (nothing a host compiler could fuse)
 hipError_t launch_hermite6_predict(const Hermite6Launch &L, hipStream_t s) {
   if (bad(L) || !L.xp || !L.vp || !L.ap) return hipErrorInvalidValue;

@@ -600,6 +600,83 @@ class NBodyEngine:
         self._check(self._L.nbody_get_tracers(self._h, _fp(p), _fp(v), _fp(a)))
         return p, v, a
 
+    # -- fp64 point queries and fp64 tracers on the shared-step Hermite calls (fp64 contexts) --
+    @staticmethod
+    def _rows64(a, who, what):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError(f"{who}: {what} must be [n, >= 3]")
+        return np.ascontiguousarray(a[:, :3], np.float64)
+
+    def jerk_at_f64(self, points, vel=None):
+        """(acc, jerk): the bodies' acceleration and jerk at every row of `points` moving with `vel` (nbody_jerk_at_f64): two [n,3]
+        float64 arrays, the unrounded fp64 pair sums over ALL bodies from the live positions and velocities.  vel None = at rest (the
+        bits an array of zeros gives).  No pair is dropped by index: a body asked about at its own (x, v) gets jerk(np.float64)'s row in
+        every bit.  eps == 0: a point exactly on a body drops that pair; eps > 0: it feels G m w / eps^3 in the jerk, nothing in acc.
+        precision="f64" contexts on one device owning all bodies; everything else: ERR_UNSUPPORTED.  Changes nothing a getter shows."""
+        p = self._rows64(points, "jerk_at_f64", "points")
+        v = None if vel is None else self._rows64(vel, "jerk_at_f64", "vel")
+        if v is not None and v.shape != p.shape:
+            raise ValueError("jerk_at_f64: points and vel differ in shape")
+        acc = np.empty((p.shape[0], 3), np.float64)
+        jerk = np.empty((p.shape[0], 3), np.float64)
+        self._check(self._L.nbody_jerk_at_f64(self._h, p.ctypes.data, 24, None if v is None else v.ctypes.data, 24, p.shape[0],
+                                              acc.ctypes.data, 24, jerk.ctypes.data, 24))
+        return acc, jerk
+
+    def set_tracers_f64(self, pos, vel=None):
+        """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
+        (nbody_set_tracers_f64); step(), tick() and compute_forces() leave them where they are.  pos, vel: [n, >= 3] float64; vel None =
+        at rest; an empty pos removes them.  Replaces any earlier set.  Tracers never act on the bodies or on each other and do not
+        enter the shared step (hermite_tracers_timescale() tells what step they would ask for); block sessions do not carry them."""
+        p = self._rows64(np.zeros((0, 3)) if pos is None or np.size(pos) == 0 else pos, "set_tracers_f64", "pos")
+        v = None if vel is None or p.shape[0] == 0 else self._rows64(vel, "set_tracers_f64", "vel")
+        if v is not None and v.shape != p.shape:
+            raise ValueError("set_tracers_f64: pos and vel must have the same number of rows")
+        self._check(self._L.nbody_set_tracers_f64(self._h, p.ctypes.data if p.shape[0] else None, 24,
+                                                  None if v is None else v.ctypes.data, 24, p.shape[0]))
+
+    @property
+    def tracer_count_f64(self):
+        n = ctypes.c_int32()
+        self._check(self._L.nbody_tracer_count_f64(self._h, ctypes.byref(n)))
+        return n.value
+
+    def tracers_f64(self):
+        """(pos, vel) of the fp64 tracers, [n,3] float64 each (nbody_get_tracers_f64; synchronises).  Feeding them back to
+        set_tracers_f64 restores the tracers bit for bit."""
+        n = self.tracer_count_f64
+        p, v = np.zeros((n, 3), np.float64), np.zeros((n, 3), np.float64)
+        self._check(self._L.nbody_get_tracers_f64(self._h, p.ctypes.data, 24, v.ctypes.data, 24))
+        return p, v
+
+    def hermite_tracers_state(self):
+        """(a, j, a2, a3): the fp64 tracers' fourth-order cache, four [n,3] float64 arrays (nbody_hermite_tracers_get); a2 and a3 are
+        zeros until a step has been taken.  ERR_STATE while nothing is cached for the stored tracers."""
+        out = np.empty((self.tracer_count_f64, 12), np.float64)
+        self._check(self._L.nbody_hermite_tracers_get(self._h, out.ctypes.data, 96))
+        return tuple(np.ascontiguousarray(out[:, 3 * k:3 * k + 3]) for k in range(4))
+
+    def hermite6_tracers_state(self):
+        """(a, j, s, a3, a4, a5): the fp64 tracers' sixth-order cache, six [n,3] float64 arrays (nbody_hermite6_tracers_get); a3, a4 and
+        a5 are zeros until a step has been taken.  ERR_STATE while nothing is cached for the stored tracers."""
+        out = np.empty((self.tracer_count_f64, 18), np.float64)
+        self._check(self._L.nbody_hermite6_tracers_get(self._h, out.ctypes.data, 144))
+        return tuple(np.ascontiguousarray(out[:, 3 * k:3 * k + 3]) for k in range(6))
+
+    def hermite_tracers_timescale(self):
+        """(t, tracer, kind): hermite_timescale()'s criterion over the fp64 tracers and the tracer that sets it
+        (nbody_hermite_tracers_timescale).  The shared step ignores it: cap dt_max with it if the tracers should limit the step."""
+        t, at, kind = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.nbody_hermite_tracers_timescale(self._h, ctypes.byref(t), ctypes.byref(at), ctypes.byref(kind)))
+        return t.value, at.value, kind.value
+
+    def hermite6_tracers_timescale(self):
+        """(t, tracer, kind): hermite6_timescale()'s criterion over the fp64 tracers (nbody_hermite6_tracers_timescale)."""
+        t, at, kind = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.nbody_hermite6_tracers_timescale(self._h, ctypes.byref(t), ctypes.byref(at), ctypes.byref(kind)))
+        return t.value, at.value, kind.value
+
     def synchronize(self):
         self._check(self._L.nbody_synchronize(self._h))
 
