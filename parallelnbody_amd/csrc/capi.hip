@@ -1,4 +1,4 @@
-// C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches.  Host C++ over the
+// C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches (the Hermite calls: capi_hermite.hip).  Host C++ over the
 // HIP runtime; no torch types, no exceptions across the boundary (the entry points that allocate host memory catch
 // std::bad_alloc), no CPU fallback.  Which kernel, geometry and plan a context gets — every size threshold — is decided in
 // launch_policy.{h,cpp} (host only, CPU-tested); nbody_create asks the device its CU count and memory and carries the answer out.
@@ -10,21 +10,77 @@
 #include <new>
 
 #include "bh_driver.h"
+#include "capi_common.h"
 #include "ctx.h"
-#include "hermite_block_level.h"
 #include "launch_policy.h"
+
+// ---- what capi_hermite.hip calls as well (capi_common.h) ----
+namespace nbody {
+int multi_unsupported(nbody_ctx *c, const char *who) {
+  return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not available on a multi-device context (nbody_create_multi); use one context per device", who);
+}
+
+// the partial rows of a slab of `m` points (kernels_probe.hip), grown on demand; freed at nbody_destroy
+int ensure_probe_part(nbody_ctx *c, int m, int width) {
+  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
+  if (need <= c->probe_part_elems) return NBODY_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                      // (a tracer pass may still be reading the old one)
+  if (c->probe_part) (void)hipFree(c->probe_part);
+  c->probe_part = nullptr; c->probe_part_elems = 0;
+  HIP_TRY(c, hipMalloc(&c->probe_part, need * 16));
+  c->probe_part_elems = need;
+  return NBODY_OK;
+}
+
+// (Re)allocate the hand-off staging pair for `bytes`.
+int ensure_stage(nbody_ctx *c, size_t bytes) {
+  if (bytes <= c->stage_bytes) return NBODY_OK;
+  if (c->d_stage) (void)hipFree(c->d_stage);
+  if (c->h_stage) (void)hipHostFree(c->h_stage);
+  c->d_stage = c->h_stage = nullptr; c->stage_bytes = 0;
+  HIP_TRY(c, hipMalloc(&c->d_stage, bytes));
+  HIP_TRY(c, hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault));
+  c->stage_bytes = bytes;
+  return NBODY_OK;
+}
+
+// `count` staged records of record_bytes each (src_stride apart: packed unless given) -> the caller's array, records `stride` bytes apart
+void scatter_records(void *dst, size_t stride, const void *src, size_t record_bytes, size_t count, size_t src_stride) {
+  if (src_stride == 0) src_stride = record_bytes;
+  if (stride == record_bytes && src_stride == record_bytes) {
+    memcpy(dst, src, count * record_bytes);
+    return;
+  }
+  for (size_t i = 0; i < count; ++i) memcpy((char *)dst + i * stride, (const char *)src + i * src_stride, record_bytes);
+}
+
+// the two sums an energy reduction left in the scratch, waited for
+int read_energy(nbody_ctx *c, double *ke, double *pe) {
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  double v[2];
+  memcpy(v, c->h_scratch, 16);
+  if (ke) *ke = v[0];
+  if (pe) *pe = v[1];
+  return NBODY_OK;
+}
+
+int check_ready(nbody_ctx *c) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (!c->have_state) return fail(c, NBODY_ERR_STATE, "no particles set (call nbody_set_particles / nbody_set_state_soa first)");
+  return use_device(c);
+}
+}  // namespace nbody
 
 namespace {
 
 using nbody::detector_table_bytes; using nbody::env_flag; using nbody::env_int; using nbody::EventPair; using nbody::fail; using nbody::g_create_error; using nbody::timed_launch; using nbody::use_device;
+using nbody::check_ready; using nbody::ensure_jerk64; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::multi_unsupported; using nbody::queue_body_jerk; using nbody::read_energy; using nbody::scatter_records;
 
 // A call on a multi-device context is answered by its Multi; its message becomes the context's.
 int multi_rc(nbody_ctx *c, int rc) {
   if (rc) c->err = nbody::multi_error(c->multi);
   return rc;
-}
-int multi_unsupported(nbody_ctx *c, const char *who) {
-  return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not available on a multi-device context (nbody_create_multi); use one context per device", who);
 }
 
 // eps^2 of the context's pair law: its own, or the floor of NBODY_ZERO_FLOOR once ensure_floor has computed it
@@ -112,18 +168,6 @@ int ensure_floor(nbody_ctx *c) {
   double f = gm > 0 ? std::pow(gm / lim, 2.0 / 3.0) : 0.0;
   const double tiny = (c->p.precision == NBODY_PREC_F64) ? 1e-280 : 1e-30;
   c->floor_eps2 = f > tiny ? f : tiny;
-  return NBODY_OK;
-}
-
-// the partial rows of a slab of `m` points (kernels_probe.hip), grown on demand; freed at nbody_destroy
-int ensure_probe_part(nbody_ctx *c, int m, int width = 1) {
-  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
-  if (need <= c->probe_part_elems) return NBODY_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));                      // (a tracer pass may still be reading the old one)
-  if (c->probe_part) (void)hipFree(c->probe_part);
-  c->probe_part = nullptr; c->probe_part_elems = 0;
-  HIP_TRY(c, hipMalloc(&c->probe_part, need * 16));
-  c->probe_part_elems = need;
   return NBODY_OK;
 }
 
@@ -275,7 +319,6 @@ int upload_soa(nbody_ctx *c, const T *posm4, const T *vel4, bool keep_history = 
   c->floor_eps2 = -1.0;
   c->sym_posg_valid = false;
   nbody::hermite_invalidate(c);
-  nbody::hermite6_invalidate(c);
   if (c->bh) nbody::bh_positions_changed(c->bh);                   // the next Barnes-Hut frame looks at the positions for its Size
   if (keep_history) return NBODY_OK;
   c->steps_done = 0;
@@ -303,34 +346,12 @@ int download4(nbody_ctx *c, const void *dev, size_t first, size_t count, T *out)
   return NBODY_OK;
 }
 
-// (Re)allocate the hand-off staging pair for `bytes`.
-int ensure_stage(nbody_ctx *c, size_t bytes) {
-  if (bytes <= c->stage_bytes) return NBODY_OK;
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  c->d_stage = c->h_stage = nullptr; c->stage_bytes = 0;
-  HIP_TRY(c, hipMalloc(&c->d_stage, bytes));
-  HIP_TRY(c, hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault));
-  c->stage_bytes = bytes;
-  return NBODY_OK;
-}
-
 // Is [dst, dst + bytes) inside memory the caller pinned for this context?
 bool in_pinned(const nbody_ctx *c, const void *dst, size_t bytes) {
   const char *d = (const char *)dst;
   for (const auto &r : c->pinned)
     if (d >= r.first && d + bytes <= r.first + r.second) return true;
   return false;
-}
-
-// `count` staged records of record_bytes each (src_stride apart: packed unless given) -> the caller's array, records `stride` bytes apart
-void scatter_records(void *dst, size_t stride, const void *src, size_t record_bytes, size_t count, size_t src_stride = 0) {
-  if (src_stride == 0) src_stride = record_bytes;
-  if (stride == record_bytes && src_stride == record_bytes) {
-    memcpy(dst, src, count * record_bytes);
-    return;
-  }
-  for (size_t i = 0; i < count; ++i) memcpy((char *)dst + i * stride, (const char *)src + i * src_stride, record_bytes);
 }
 
 // Does the caller's FParticle array take the records by DMA — packed, and inside memory it pinned for this context?
@@ -369,17 +390,6 @@ int queue_bounds(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-// the two sums an energy reduction left in the scratch, waited for
-int read_energy(nbody_ctx *c, double *ke, double *pe) {
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, c->scratch, 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  double v[2];
-  memcpy(v, c->h_scratch, 16);
-  if (ke) *ke = v[0];
-  if (pe) *pe = v[1];
-  return NBODY_OK;
-}
-
 // The position buffer becomes visible to (or is replaced by) the caller: bodies may move behind the library's back from
 // now on, so fused stepping and the buffer-swapping one-launch step end here, for the life of the context.  The detector
 // table the two-kernel path uses may still hold what the last fused update left in it.
@@ -391,12 +401,6 @@ int posm_escapes(nbody_ctx *c) {
   c->sym_posg_valid = false;
   if (c->bh) nbody::bh_positions_external(c->bh);
   return NBODY_OK;
-}
-
-int check_ready(nbody_ctx *c) {
-  if (!c) return NBODY_ERR_INVALID;
-  if (!c->have_state) return fail(c, NBODY_ERR_STATE, "no particles set (call nbody_set_particles / nbody_set_state_soa first)");
-  return use_device(c);
 }
 
 // nbody_set_state_soa / nbody_set_state_soa_f64 (`who`): the whole state as T x 4
@@ -616,10 +620,11 @@ void nbody_destroy(nbody_ctx *c) {
   if (c->bh_acc) (void)hipFree(c->bh_acc);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->hermite, c->hblock})
+  for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->snap64, c->tr64})
     if (q) (void)hipFree(q);
-  for (void *q : {c->hermite6, c->snap64, c->h6block, c->tr64, c->tr64_h4, c->tr64_h6})
-    if (q) (void)hipFree(q);
+  for (int o = 0; o < 2; ++o)
+    for (void *q : {c->hm[o].buf, c->trh[o].buf, c->hb[o].buf})
+      if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->clk) (void)hipFree(c->clk);
@@ -647,7 +652,6 @@ int nbody_device_ptr(nbody_ctx *c, int32_t which, void **ptr, size_t *bytes) {
   if (int rc = use_device(c)) return rc;
   c->hm_external = true;                                          // whichever buffer: the caller may write the state from now on
   nbody::hermite_invalidate(c);
-  nbody::hermite6_invalidate(c);
   switch (which) {
     case NBODY_BUF_POSM:
       *ptr = c->posm; if (bytes) *bytes = (size_t)c->p.n_total * c->elem;
@@ -667,7 +671,6 @@ int nbody_bind_device_state(nbody_ctx *c, void *posm, void *vel, void *acc) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->hm_external = true;
   nbody::hermite_invalidate(c);
-  nbody::hermite6_invalidate(c);
   if (posm) {
     if (int rc = posm_escapes(c)) return rc;
     if (c->own_posm) (void)hipFree(c->posm);
@@ -814,7 +817,6 @@ int nbody_step_end(nbody_ctx *c, float dt) {
   c->step_open = false;
   if ((rc = run_update(c, dt > 0.0f ? dt : 0.0f))) return rc;
   if (dt > 0.0f) { c->steps_done += 1; nbody::hermite_invalidate(c); }
-  if (dt > 0.0f) nbody::hermite6_invalidate(c);
   return NBODY_OK;
 }
 
@@ -901,7 +903,6 @@ int nbody_step(nbody_ctx *c, float dt, int32_t nsteps) {
   if (nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_step: nsteps < 0");
   if (!(dt > 0.0f)) return NBODY_OK;   // OctreeSearch.cpp:25: PhDeltaTime <= 0 freezes the physics
   nbody::hermite_invalidate(c);
-  nbody::hermite6_invalidate(c);
   if (c->multi) {
     if (c->theta > 0.0f) {                                        // whole frames on every device, one wait per batch (multi_bh_steps)
       int built = 0;
@@ -1061,7 +1062,6 @@ int nbody_tick(nbody_ctx *c, float dt, float *size, void *aos, size_t stride) {
   HIP_TRY(c, hipSetDevice(c->p.device));
   const bool live = dt > 0.0f;                                   // OctreeSearch.cpp:25
   if (live) nbody::hermite_invalidate(c);
-  if (live) nbody::hermite6_invalidate(c);
   // the eps floor of NBODY_ZERO_FLOOR is computed through the same 64-byte scratch the bounds travel in: settle it
   // before the bounds are queued, or the first frame would return the largest mass as Size
   if (live && c->theta == 0.0f && (rc = ensure_floor(c))) return rc;
@@ -1249,7 +1249,6 @@ int nbody_load_checkpoint(nbody_ctx *c, const char *path, int64_t *steps_done) t
   { const int rc2 = f64 ? note_masses(c, (const double *)posm.data()) : note_masses(c, (const float *)posm.data()); if (rc2) return rc2; }
   c->have_state = true; c->floor_eps2 = -1.0; c->step_open = false; c->step_local = false; c->sym_posg_valid = false;
   nbody::hermite_invalidate(c);                                    // (the file holds no derivatives: a resumed run starts from the corrected state)
-  nbody::hermite6_invalidate(c);
   if (c->bh) nbody::bh_positions_changed(c->bh);
   c->steps_done = h.steps_done;
   // Barnes-Hut: the opening angle and the root of the next tree (the previous tree's CoM, OctreeSearch.cpp:77-79) are
@@ -1626,21 +1625,23 @@ int launch_jerk_on(nbody_ctx *c, const void *probe, const void *pvel, int m, dou
   HIP_TRY(c, nbody::launch_jerk(L, c->stream));
   return NBODY_OK;
 }
+}  // namespace
 
 // The bodies' own (a, j), as one pass under NBODY_KERNEL_FORCES; the partial rows in the staging area the point queries use: two
 // float4 per body and chunk, six doubles on fp64 state.
-int queue_body_jerk(nbody_ctx *c, double *aj64, float *ajf) {
+int nbody::queue_body_jerk(nbody_ctx *c, double *aj64, float *ajf) {
   const int n = c->p.n_total;
   if (int rc = ensure_probe_part(c, n, c->p.precision == NBODY_PREC_F64 ? 3 : 2)) return rc;
   return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { return launch_jerk_on(c, nullptr, nullptr, n, aj64, ajf); });
 }
 
 // the bodies' unrounded (a, j), [n_total][6] double, and the reduction's workgroup pairs behind them: allocated at first use
-int ensure_jerk64(nbody_ctx *c) {
+int nbody::ensure_jerk64(nbody_ctx *c) {
   const size_t n = (size_t)c->p.n_total;
   if (!c->jerk64) HIP_TRY(c, hipMalloc(&c->jerk64, (6 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
   return NBODY_OK;
 }
+namespace {
 
 // nbody_get_jerk / nbody_get_jerk_f64: T = float / double
 template <typename T>
@@ -1702,474 +1703,6 @@ int nbody_jerk_time(nbody_ctx *c, double *t_min, int32_t *body) {
   if ((rc = read_energy(c, &k, &at))) return rc;               // (the scratch's two doubles: the largest |j|^2 / |a|^2, its body)
   if (t_min) *t_min = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
   if (body) *body = (int32_t)at;
-  return NBODY_OK;
-}
-
-}  // extern "C"
-
-// ---- fourth-order Hermite stepping of fp64 contexts: predictor, the fp64 jerk pass on the predicted state, corrector (kernels_hermite.hip) ----
-namespace {
-// where it exists — fp64 state, one device, all bodies (such contexts are at theta == 0) — and when: a state set, no step half done
-int hermite_ready(nbody_ctx *c, const char *who) {
-  if (c && c->multi) return multi_unsupported(c, who);
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if (c->p.precision != NBODY_PREC_F64)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): the corrector's "
-                "differences a0 - a1 need fp64 state; create the context with NBODY_PREC_F64", who);
-  if (c->p.i_count != c->p.n_total)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
-  if (c->theta > 0.0f) return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not at theta > 0 (the jerk is a pair sum)", who);
-  if (c->step_open || c->step_local) return fail(c, NBODY_ERR_STATE, "%s: a step is open (nbody_step_end first)", who);
-  return NBODY_OK;
-}
-
-// A shared-step call, or a new begin, on a context with a block session: in mid-frame the bodies are at times of their own and nothing
-// but nbody_hermite_block_advance can move them on; at a frame end the stored state is synchronised, the cache is every body's, and the
-// session simply ends.
-int hermite_block_leave(nbody_ctx *c, const char *who) {
-  if (!c->hb.active) return NBODY_OK;
-  if (c->hb.ticks & ((1ll << c->hb.levels) - 1))
-    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is in mid-frame (tick %lld of frames of %lld): the bodies are at times of "
-                "their own; nbody_hermite_block_advance(ctx, 1, ...) finishes the frame, nbody_hermite_restart abandons the session", who,
-                (long long)c->hb.ticks, 1ll << c->hb.levels);
-  c->hb.active = false;
-  return NBODY_OK;
-}
-
-// The same for a SIXTH-order block session (nbody_hermite6_block_*), which every shared-step call of either order and every begin meets
-// the same way: refused in mid-frame, ended at a frame end.
-int hermite6_block_leave(nbody_ctx *c, const char *who) {
-  if (!c->h6b.active) return NBODY_OK;
-  if (c->h6b.ticks & ((1ll << c->h6b.levels) - 1))
-    return fail(c, NBODY_ERR_STATE, "%s: a sixth-order Hermite block session is in mid-frame (tick %lld of frames of %lld): the bodies are at "
-                "times of their own; nbody_hermite6_block_advance(ctx, 1, ...) finishes the frame, nbody_hermite_restart abandons the session",
-                who, (long long)c->h6b.ticks, 1ll << c->h6b.levels);
-  c->h6b.active = false;
-  return NBODY_OK;
-}
-
-struct HermiteBufs { double *xp, *vp, *a2, *a3, *aj[2], *partials; };
-HermiteBufs hermite_bufs(const nbody_ctx *c) {
-  const size_t n = (size_t)c->p.n_total;
-  double *b = (double *)c->hermite;
-  return HermiteBufs{b, b + 4 * n, b + 8 * n, b + 12 * n, {b + 16 * n, b + 22 * n}, b + 28 * n};
-}
-
-// the cache and the jerk pass's partial rows, at first use
-int hermite_ensure(nbody_ctx *c) {
-  const size_t n = (size_t)c->p.n_total;
-  if (!c->hermite) HIP_TRY(c, hipMalloc(&c->hermite, (28 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
-  return ensure_probe_part(c, (int)n, 3);
-}
-
-// (a, j) of the bodies at (posm, vel) — the live state or the predicted one — into aj64: nbody_get_jerk_f64's pass and fold with the same
-// geometry, a function of n_total alone, queued as one pass under NBODY_KERNEL_FORCES
-int hermite_evaluate(nbody_ctx *c, const void *posm, const void *vel, double *aj64) {
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::JerkLaunch L;
-    L.posm = posm; L.vel = vel; L.part = c->probe_part; L.aj64 = aj64;
-    L.n_total = c->p.n_total; L.m = c->p.n_total; L.precision = NBODY_PREC_F64; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, nbody::launch_jerk(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// what every call does at entry: once somebody else may write the state, nothing cached is believed; (a0, j0) of the stored (x, v)
-int hermite_enter(nbody_ctx *c) {
-  if (int rc = hermite_ensure(c)) return rc;
-  if (c->hm_external) nbody::hermite_invalidate(c);
-  if (c->hm_external) nbody::hermite6_invalidate(c);
-  if (c->hm_valid) return NBODY_OK;
-  if (int rc = hermite_evaluate(c, c->posm, c->vel, hermite_bufs(c).aj[c->hm_cur])) return rc;
-  c->hm_valid = true;
-  return NBODY_OK;
-}
-
-// ---- the fp64 tracers of the shared-step Hermite calls (nbody_set_tracers_f64; kernels_points64.hip) ----
-// Massless points with a state and caches of their own, laid out like the bodies' (ctx.h).  They are predicted with the step's dt,
-// evaluated by the point kernels in the field of the bodies' PREDICTED state — the field the bodies' own evaluation uses — and corrected
-// by the bodies' kernels on the tracers' arrays.  Nothing of theirs is read by anything the bodies get.
-struct Tracer64Bufs { double *pos, *vel, *acc, *xp, *vp, *ap; };
-Tracer64Bufs tracer64_bufs(const nbody_ctx *c) {
-  const size_t m = (size_t)c->tr64_n;
-  double *b = (double *)c->tr64;
-  return Tracer64Bufs{b, b + 4 * m, b + 8 * m, b + 12 * m, b + 16 * m, b + 20 * m};
-}
-struct TracerH4Bufs { double *a2, *a3, *aj[2], *partials; };
-TracerH4Bufs tracer_h4_bufs(const nbody_ctx *c) {
-  const size_t m = (size_t)c->tr64_n;
-  double *b = (double *)c->tr64_h4;
-  return TracerH4Bufs{b, b + 4 * m, {b + 8 * m, b + 14 * m}, b + 20 * m};
-}
-struct TracerH6Bufs { double *a3, *a4, *a5, *ajs[2], *partials; };
-TracerH6Bufs tracer_h6_bufs(const nbody_ctx *c) {
-  const size_t m = (size_t)c->tr64_n;
-  double *b = (double *)c->tr64_h6;
-  return TracerH6Bufs{b, b + 4 * m, b + 8 * m, {b + 12 * m, b + 21 * m}, b + 30 * m};
-}
-
-// a point pass is never queued into a staging area that does not hold a slab's partial rows
-int points64_part_holds(nbody_ctx *c, int m, int width, const char *what) {
-  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
-  if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
-  return fail(c, NBODY_ERR_STATE, "%s: the partial rows of %d points need %zu float4, the staging area holds %zu", what, m, need, c->probe_part_elems);
-}
-
-// (a, j) at m points (ppos, pvel: double4 each, device) in the field of the bodies at (posm, vel) — the live state or the predicted one —
-// into aj64 ([m][6]), queued as one pass under NBODY_KERNEL_FORCES
-int points64_jerk(nbody_ctx *c, const void *posm, const void *vel, const void *ppos, const void *pvel, int m, double *aj64) {
-  if (int rc = points64_part_holds(c, m, 3, "the point jerk pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Points64Launch L;
-    L.posm = posm; L.vel = vel; L.ppos = ppos; L.pvel = pvel; L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = aj64;
-    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, nbody::launch_jerk_points_f64(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// (a, j, s) the same way, given the bodies' input accelerations (ain) and the points' (pain), into ajs64 ([m][9])
-int points64_snap(nbody_ctx *c, const void *posm, const void *vel, const double *ain, int ain_stride, const void *ppos, const void *pvel,
-                  const double *pain, int pain_stride, int m, double *ajs64) {
-  if (int rc = points64_part_holds(c, m, nbody::kSnapRowWidth, "the point snap pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Points64Launch L;
-    L.posm = posm; L.vel = vel; L.ain = ain; L.ain_stride = ain_stride; L.ppos = ppos; L.pvel = pvel; L.pain = pain; L.pain_stride = pain_stride;
-    L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = ajs64;
-    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, nbody::launch_snap_points_f64(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// what a fourth-order call does for the tracers behind hermite_enter (which has applied the hm_external rule): the cache and the partial
-// rows at first use; (a0, j0) of the stored tracers in the stored bodies' field when they are not valid — one more pass —, zeros for a2, a3
-int hermite_tracers_enter(nbody_ctx *c) {
-  const int m = c->tr64_n;
-  if (m <= 0) return NBODY_OK;
-  if (!c->tr64_h4) HIP_TRY(c, hipMalloc(&c->tr64_h4, (20 * (size_t)m + 2 * (size_t)nbody::energy_fast_slots(m)) * sizeof(double)));
-  if (int rc = ensure_probe_part(c, m, 3)) return rc;
-  if (c->trh_valid) return NBODY_OK;
-  const Tracer64Bufs t = tracer64_bufs(c);
-  const TracerH4Bufs q = tracer_h4_bufs(c);
-  if (int rc = points64_jerk(c, c->posm, c->vel, t.pos, t.vel, m, q.aj[c->trh_cur])) return rc;
-  HIP_TRY(c, hipMemsetAsync(q.a2, 0, 8 * (size_t)m * sizeof(double), c->stream));   // a2 and a3 lie side by side
-  c->trh_valid = true;
-  c->trh_derivs = false;
-  return NBODY_OK;
-}
-
-// the tracers' arrays as the stepping kernels of kernels_hermite.hip take the bodies'
-nbody::HermiteLaunch hermite_tracers_launch(const nbody_ctx *c, double dt) {
-  const Tracer64Bufs t = tracer64_bufs(c);
-  const TracerH4Bufs q = tracer_h4_bufs(c);
-  nbody::HermiteLaunch L;
-  L.posm = t.pos; L.vel = t.vel; L.acc = t.acc; L.xp = t.xp; L.vp = t.vp; L.aj0 = q.aj[c->trh_cur]; L.aj1 = q.aj[c->trh_cur ^ 1];
-  L.a2 = q.a2; L.a3 = q.a3; L.n = c->tr64_n; L.dt = dt;
-  return L;
-}
-
-// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE.
-// With fp64 tracers (their cache valid: hermite_tracers_enter) the tracers' predictor and corrector ride in the same two goes, and their
-// evaluation at the bodies' predicted state is one more pass under NBODY_KERNEL_FORCES.
-int hermite_one_step(nbody_ctx *c, double dt) {
-  const HermiteBufs b = hermite_bufs(c);
-  nbody::HermiteLaunch L;
-  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.aj0 = b.aj[c->hm_cur]; L.aj1 = b.aj[c->hm_cur ^ 1];
-  L.a2 = b.a2; L.a3 = b.a3; L.n = c->p.n_total; L.dt = dt;
-  const bool tracers = c->tr64_n > 0;
-  const nbody::HermiteLaunch T = tracers ? hermite_tracers_launch(c, dt) : nbody::HermiteLaunch{};
-  int rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
-        HIP_TRY(c, nbody::launch_hermite_predict(L, c->stream));
-        if (tracers) HIP_TRY(c, nbody::launch_hermite_predict(T, c->stream));
-        return NBODY_OK;
-      }, false))) return rc;
-  if ((rc = hermite_evaluate(c, b.xp, b.vp, b.aj[c->hm_cur ^ 1]))) return rc;
-  if (tracers && (rc = points64_jerk(c, b.xp, b.vp, T.xp, T.vp, T.n, tracer_h4_bufs(c).aj[c->trh_cur ^ 1]))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
-        HIP_TRY(c, nbody::launch_hermite_correct(L, c->stream));
-        if (tracers) HIP_TRY(c, nbody::launch_hermite_correct(T, c->stream));
-        return NBODY_OK;
-      }))) return rc;
-  c->hm_cur ^= 1;                                                  // (a0, j0) := (a1, j1)
-  c->hm_derivs = true;
-  if (tracers) { c->trh_cur ^= 1; c->trh_derivs = true; }
-  c->sym_posg_valid = false;
-  c->steps_done += 1;
-  return NBODY_OK;
-}
-
-// the time scale of the cached derivatives, waited for: *k the largest criterion value, *body where, *kind which criterion
-int hermite_scale(nbody_ctx *c, double *t, int32_t *body, int32_t *kind) {
-  const HermiteBufs b = hermite_bufs(c);
-  const int n = c->p.n_total;
-  if (c->hm_derivs) HIP_TRY(c, nbody::launch_hermite_time(b.aj[c->hm_cur], b.a2, b.a3, n, b.partials, (double *)c->scratch, c->stream));
-  else              HIP_TRY(c, nbody::launch_jerk_time(b.aj[c->hm_cur], n, b.partials, (double *)c->scratch, c->stream));
-  double k = 0.0, at = 0.0;
-  if (int rc = read_energy(c, &k, &at)) return rc;                // (the scratch's two doubles: the largest k, its body)
-  *t = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
-  *body = (int32_t)at;
-  *kind = c->hm_derivs ? 1 : 0;
-  return NBODY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbody_hermite_step(nbody_ctx *c, double dt, int32_t nsteps) {
-  int rc = hermite_ready(c, "nbody_hermite_step");
-  if (rc) return rc;
-  if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_step: dt is not finite, or nsteps < 0");
-  if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
-  if ((rc = hermite_block_leave(c, "nbody_hermite_step"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite_step"))) return rc;
-  if ((rc = hermite_enter(c))) return rc;
-  if ((rc = hermite_tracers_enter(c))) return rc;
-  nbody::hermite6_invalidate(c);                                   // (the state moves on without the sixth-order cache)
-  for (int s = 0; s < nsteps; ++s)
-    if ((rc = hermite_one_step(c, dt))) return rc;
-  return NBODY_OK;
-}
-
-int nbody_hermite_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t *kind) {
-  int rc = hermite_ready(c, "nbody_hermite_timescale");
-  if (rc) return rc;
-  if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_timescale: all three outputs are null");
-  if ((rc = hermite_block_leave(c, "nbody_hermite_timescale"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite_timescale"))) return rc;
-  if ((rc = hermite_enter(c))) return rc;
-  double t = 0.0;
-  int32_t at = 0, which = 0;
-  if ((rc = hermite_scale(c, &t, &at, &which))) return rc;
-  if (t_min) *t_min = t;
-  if (body) *body = at;
-  if (kind) *kind = which;
-  return NBODY_OK;
-}
-
-int nbody_hermite_advance(nbody_ctx *c, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps, double *t_done,
-                          int64_t *steps) {
-  int rc = hermite_ready(c, "nbody_hermite_advance");
-  if (rc) return rc;
-  if (!(eta > 0.0) || !(eta_start > 0.0) || !(dt_max > 0.0) || !(t_span >= 0.0) || !std::isfinite(t_span) || max_steps < 0)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_advance: eta, eta_start and dt_max must be > 0, t_span >= 0 and finite, max_steps >= 0");
-  double t_acc = 0.0;
-  int64_t taken = 0;
-  if (t_done) *t_done = 0.0;
-  if (steps) *steps = 0;
-  if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
-  if ((rc = hermite_block_leave(c, "nbody_hermite_advance"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite_advance"))) return rc;
-  if ((rc = hermite_enter(c))) return rc;
-  if ((rc = hermite_tracers_enter(c))) return rc;
-  nbody::hermite6_invalidate(c);
-  const double root_eta = std::sqrt(eta);
-  while (t_acc < t_span && taken < max_steps) {
-    double t = 0.0;
-    int32_t at = 0, which = 0;
-    if ((rc = hermite_scale(c, &t, &at, &which))) return rc;
-    double dt = std::min(dt_max, which == 1 ? root_eta * t : eta_start * t);
-    const double rest = t_span - t_acc;
-    const bool last = dt >= rest;
-    if (last) dt = rest;
-    if (!(dt > 0.0) || !std::isfinite(dt))
-      return fail(c, NBODY_ERR_STATE, "nbody_hermite_advance: the time scale of body %d gives dt = %g after %lld steps (t = %.17g); the "
-                  "state is that of the last good step", (int)at, dt, (long long)taken, t_acc);
-    if ((rc = hermite_one_step(c, dt))) return rc;
-    t_acc = last ? t_span : t_acc + dt;
-    taken += 1;
-    if (t_done) *t_done = t_acc;
-    if (steps) *steps = taken;
-  }
-  return NBODY_OK;
-}
-
-int nbody_hermite_get(nbody_ctx *c, double *d12, size_t stride) {
-  int rc = hermite_ready(c, "nbody_hermite_get");
-  if (rc) return rc;
-  if (!d12 || stride < 96) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_get: null buffer or stride < 96");
-  if (!c->hermite || !c->hm_valid)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite_get: no derivatives cached for the stored state (nbody_hermite_step or nbody_hermite_timescale first)");
-  const size_t n = (size_t)c->p.n_total;
-  const HermiteBufs b = hermite_bufs(c);
-  if ((rc = ensure_stage(c, n * 112))) return rc;
-  double *h_aj = (double *)c->h_stage, *h_d = h_aj + 6 * n;       // (a2 and a3 lie side by side: 8 doubles per body in all)
-  HIP_TRY(c, hipMemcpyAsync(h_aj, b.aj[c->hm_cur], n * 48, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_d, b.a2, n * 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < n; ++i) {
-    double rec[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    memcpy(rec, h_aj + 6 * i, 48);
-    if (c->hm_derivs || c->hb.active) { memcpy(rec + 6, h_d + 4 * i, 24); memcpy(rec + 9, h_d + 4 * (n + i), 24); }   // (a session keeps zeros where a body has none)
-    memcpy((char *)d12 + i * stride, rec, 96);
-  }
-  return NBODY_OK;
-}
-
-int nbody_hermite_restart(nbody_ctx *c) {
-  int rc = hermite_ready(c, "nbody_hermite_restart");
-  if (rc) return rc;
-  nbody::hermite_invalidate(c);
-  nbody::hermite6_invalidate(c);
-  return NBODY_OK;
-}
-
-}  // extern "C"
-
-// ---- Hermite block time steps: a session of per-body power-of-two steps on the cache above (kernels_hermite_block.hip) ----
-namespace {
-struct HermiteBlockBufs { long long *T, *seg_min, *record; unsigned long long *floor_hits; int *level, *list, *seg_cnt; };
-HermiteBlockBufs hermite_block_bufs_at(void *base, size_t n) {
-  int slots;
-  (void)nbody::hermite_block_segment((int)n, &slots);
-  long long *q = (long long *)base;
-  int *w = (int *)(q + n + slots + 3);
-  return HermiteBlockBufs{q, q + n, q + n + slots, (unsigned long long *)(q + n + slots + 2), w, w + n, w + 2 * n};
-}
-HermiteBlockBufs hermite_block_bufs(const nbody_ctx *c) { return hermite_block_bufs_at(c->hblock, (size_t)c->p.n_total); }
-size_t hermite_block_bytes(int n) {
-  int slots;
-  (void)nbody::hermite_block_segment(n, &slots);
-  return ((size_t)n + slots + 3) * 8 + (2 * (size_t)n + slots) * 4;
-}
-
-nbody::HermiteBlockLaunch hermite_block_launch(const nbody_ctx *c) {
-  const HermiteBufs b = hermite_bufs(c);
-  const HermiteBlockBufs q = hermite_block_bufs(c);
-  nbody::HermiteBlockLaunch L;
-  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.aj0 = b.aj[c->hm_cur]; L.a2 = b.a2; L.a3 = b.a3;
-  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = q.record;
-  L.floor_hits = q.floor_hits; L.n = c->p.n_total; L.levels = c->hb.levels; L.tick = c->hb.tick; L.dt_max = c->hb.dt_max;
-  L.root_eta = c->hb.root_eta; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-  return L;
-}
-
-// the totals since begin; the levels' range and the floor hits are read from the device (4 n + 8 bytes): waits for the stream
-int hermite_block_fill(nbody_ctx *c, nbody_hermite_block_stats *out) {
-  const size_t n = (size_t)c->p.n_total;
-  const HermiteBlockBufs q = hermite_block_bufs(c);
-  if (int rc = ensure_stage(c, n * 4 + 8)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.floor_hits, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int64_t floor_hits;
-  memcpy(&floor_hits, c->h_stage, 8);
-  const int32_t *lv = (const int32_t *)((const char *)c->h_stage + 8);
-  out->synchronised = (c->hb.ticks & ((1ll << c->hb.levels) - 1)) == 0 ? 1 : 0;
-  out->ticks = c->hb.ticks; out->frames_done = c->hb.ticks >> c->hb.levels; out->block_steps = c->hb.block_steps;
-  out->body_steps = c->hb.body_steps; out->pairs = c->hb.pairs; out->floor_hits = floor_hits;
-  out->level_min = *std::min_element(lv, lv + n); out->level_max = *std::max_element(lv, lv + n);
-  return NBODY_OK;
-}
-
-// one block step, from the schedule to the stored bodies; the host waits once, for (T_next, m), to size the evaluation
-int hermite_block_one_step(nbody_ctx *c) {
-  const nbody::HermiteBlockLaunch L = hermite_block_launch(c);
-  int rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_schedule(L, c->stream)); return NBODY_OK; }, false))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  long long rec[2];
-  memcpy(rec, c->h_scratch, 16);
-  const long long t_next = rec[0];
-  const int n = c->p.n_total, m = (int)rec[1];
-  if (rec[1] < 1 || rec[1] > n || t_next <= c->hb.ticks)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_advance: the schedule gave T_next = %lld, m = %lld at tick %lld", t_next, rec[1], (long long)c->hb.ticks);
-  const int lanes = nbody::hermite_block_lanes(m, c->hb.lanes);
-  const int slab = (int)std::min<size_t>(nbody::probe_slab_points(n, 3), (size_t)n);   // (the partial rows of ensure_probe_part(n, 3))
-  for (int first = 0; first < m; first += slab) {
-    const int ms = std::min(slab, m - first);
-    const bool last = first + ms == m;
-    if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_evaluate(L, first, ms, lanes, c->stream)); return NBODY_OK; }, last))) return rc;
-    if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite_block_correct(L, first, ms, t_next, c->stream)); return NBODY_OK; }, last))) return rc;
-  }
-  c->hb.ticks = t_next;
-  c->hb.block_steps += 1; c->hb.body_steps += m; c->hb.pairs += (int64_t)m * n;
-  if (c->hb.ticks >= (1ll << c->hb.levels)) c->hm_derivs = true;    // a whole frame: every body has stepped, every a2 and a3 is a step's
-  c->sym_posg_valid = false;
-  c->steps_done += 1;
-  return NBODY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbody_hermite_block_level(double dt_c, double dt_max, int32_t levels, int32_t *floor_hit) {
-  if (levels < 0 || levels > nbody::kHermiteBlockMaxLevels) return -1;
-  int hit = 0;
-  const int k = nbody::hermite_block_level(dt_c, dt_max, levels, &hit);
-  if (floor_hit) *floor_hit = hit;
-  return k;
-}
-
-int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
-  int rc = hermite_ready(c, "nbody_hermite_block_begin");
-  if (rc) return rc;
-  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (!positive(dt_max) || !positive(eta) || !positive(eta_start) || levels < 0 || levels > nbody::kHermiteBlockMaxLevels)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: dt_max, eta and eta_start must be finite and > 0, levels 0 .. %d", nbody::kHermiteBlockMaxLevels);
-  const double tick = std::ldexp(dt_max, -levels);
-  if (!std::isnormal(tick))
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: the tick dt_max 2^-levels = %g is not a normal number", tick);
-  if (c->tr64_n > 0)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_hermite_block_begin: the context holds %d fp64 tracers, which the block scheduler does not "
-                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them", c->tr64_n);
-  const int n = c->p.n_total;
-  if (level_in)
-    for (int i = 0; i < n; ++i)
-      if (level_in[i] < 0 || level_in[i] > levels)
-        return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
-  if ((rc = hermite_block_leave(c, "nbody_hermite_block_begin"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite_block_begin"))) return rc;
-  if ((rc = hermite_enter(c))) return rc;
-  nbody::hermite6_invalidate(c);
-  if (!c->hblock) HIP_TRY(c, hipMalloc(&c->hblock, hermite_block_bytes(n)));
-  c->hb.levels = levels; c->hb.dt_max = dt_max; c->hb.tick = tick; c->hb.root_eta = std::sqrt(eta);
-  c->hb.lanes = nbody::env_int("NBODY_HERMITE_BLOCK_LANES", 0);
-  c->hb.ticks = c->hb.block_steps = c->hb.body_steps = c->hb.pairs = 0;
-  const nbody::HermiteBlockLaunch L = hermite_block_launch(c);
-  if (!c->hm_derivs) HIP_TRY(c, hipMemsetAsync(L.a2, 0, (size_t)n * 64, c->stream));   // a2 and a3 lie side by side: zeros until a body steps
-  HIP_TRY(c, hipMemsetAsync(L.record, 0, 24, c->stream));          // the record and the floor hits
-  if (level_in) HIP_TRY(c, hipMemcpyAsync(L.list, level_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, nbody::launch_hermite_block_init(L, level_in ? L.list : nullptr, eta_start, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's array is its own again
-  c->hb.active = true;
-  return NBODY_OK;
-}
-
-int nbody_hermite_block_advance(nbody_ctx *c, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out) {
-  int rc = hermite_ready(c, "nbody_hermite_block_advance");
-  if (rc) return rc;
-  if (frames < 0 || max_block_steps < 0 || (out && out->struct_size != sizeof(nbody_hermite_block_stats)))
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_advance: frames < 0, max_block_steps < 0, or out->struct_size is not "
-                "sizeof(nbody_hermite_block_stats) = %d", (int)sizeof(nbody_hermite_block_stats));
-  if (!c->hb.active)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_advance: no block session (nbody_hermite_block_begin first; uploads, kick-drift "
-                "steps, handed-out pointers, shared Hermite steps and nbody_hermite_restart end one)");
-  const int64_t frame_now = c->hb.ticks >> c->hb.levels;
-  if (frames >= (1ll << 62 >> c->hb.levels) - frame_now)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite_block_advance: %lld more frames of 2^%d ticks pass 2^62 ticks", (long long)frames, c->hb.levels);
-  const int64_t target = frames == 0 ? c->hb.ticks : (frame_now + frames) << c->hb.levels;
-  for (int64_t taken = 0; c->hb.ticks < target && taken < max_block_steps; ++taken)
-    if ((rc = hermite_block_one_step(c))) return rc;
-  return out ? hermite_block_fill(c, out) : NBODY_OK;
-}
-
-int nbody_hermite_block_get(nbody_ctx *c, int64_t *ticks, int32_t *level) {
-  int rc = hermite_ready(c, "nbody_hermite_block_get");
-  if (rc) return rc;
-  if (!c->hb.active)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite_block_get: no block session (nbody_hermite_block_begin first)");
-  const size_t n = (size_t)c->p.n_total;
-  const HermiteBlockBufs q = hermite_block_bufs(c);
-  if ((rc = ensure_stage(c, n * 12))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.T, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + n * 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (ticks) memcpy(ticks, c->h_stage, n * 8);
-  if (level) memcpy(level, (const char *)c->h_stage + n * 8, n * 4);
   return NBODY_OK;
 }
 
@@ -2358,632 +1891,6 @@ int nbody_get_launch_config(nbody_ctx *c, int32_t *tile, int32_t *i_per_thread, 
   if (j_split) *j_split = c->j_split;
   if (blocks) *blocks = b;
   if (threads) *threads = t;
-  return NBODY_OK;
-}
-
-}  // extern "C"
-
-// ---- the snap and sixth-order Hermite stepping of fp64 contexts: predictor, the fp64 snap pass on the predicted state, corrector (kernels_snap.hip) ----
-namespace {
-// where the snap exists: fp64 state, one device, all bodies
-int snap_supported(nbody_ctx *c, const char *who) {
-  if (c->p.precision != NBODY_PREC_F64)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): the snap's pair term "
-                "takes differences of accelerations, which need fp64 state; create the context with NBODY_PREC_F64", who);
-  if (c->p.i_count != c->p.n_total)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
-  return NBODY_OK;
-}
-
-// (a, j, s) of the bodies at (posm, vel) given the input accelerations ain — the live state or the predicted one — into ajs64, queued as
-// one pass under NBODY_KERNEL_FORCES: the kernel, fold and geometry (a function of n_total alone) of nbody_get_snap_f64
-// a pass is never queued into a staging area that does not hold its partial rows
-int probe_part_holds(nbody_ctx *c, int width, const char *what) {
-  const size_t need = nbody::probe_part_elems(c->p.n_total, c->p.n_total, width);
-  if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
-  return fail(c, NBODY_ERR_STATE, "%s: the partial rows need %zu float4, the staging area holds %zu", what, need, c->probe_part_elems);
-}
-
-int snap_evaluate(nbody_ctx *c, const void *posm, const void *vel, const double *ain, int ain_stride, double *ajs64) {
-  if (int rc = probe_part_holds(c, nbody::kSnapRowWidth, "the snap pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::SnapLaunch L;
-    L.posm = posm; L.vel = vel; L.ain = ain; L.ain_stride = ain_stride; L.part = c->probe_part; L.ajs64 = ajs64;
-    L.n_total = c->p.n_total; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, nbody::launch_snap(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-struct Hermite6Bufs { double *xp, *vp, *ap, *a3, *a4, *a5, *ajs[2], *partials; };
-Hermite6Bufs hermite6_bufs(const nbody_ctx *c) {
-  const size_t n = (size_t)c->p.n_total;
-  double *b = (double *)c->hermite6;
-  return Hermite6Bufs{b, b + 4 * n, b + 8 * n, b + 12 * n, b + 16 * n, b + 20 * n, {b + 24 * n, b + 33 * n}, b + 42 * n};
-}
-
-// what every sixth-order call does at entry: the cache and the partial rows at first use; once somebody else may write the state, nothing
-// cached is believed; then (a0, j0, s0) of the stored (x, v) — one jerk pass for a, one snap pass with that a as its input — and zeros
-// for a3, a4, a5
-int hermite6_enter(nbody_ctx *c) {
-  const size_t n = (size_t)c->p.n_total;
-  if (!c->hermite6) HIP_TRY(c, hipMalloc(&c->hermite6, (42 * n + 2 * (size_t)nbody::energy_fast_slots((int)n)) * sizeof(double)));
-  // the partial rows of BOTH passes a start runs: the staging area only grows, and neither width's need covers the other's (the slabs
-  // are whole multiples of 1024 points: at N = 65536 the jerk pass's rows take 16 515 072 float4, the snap pass's 16 384 000)
-  if (int rc = ensure_probe_part(c, (int)n, 3)) return rc;
-  if (int rc = ensure_probe_part(c, (int)n, nbody::kSnapRowWidth)) return rc;
-  if (c->hm_external) { nbody::hermite_invalidate(c); nbody::hermite6_invalidate(c); }
-  if (c->h6_valid) return NBODY_OK;
-  const Hermite6Bufs b = hermite6_bufs(c);
-  double *aj = b.ajs[c->h6_cur ^ 1];                              // (the jerk pass's six doubles per body, in the row a step overwrites)
-  if (int rc = probe_part_holds(c, 3, "the jerk pass of a sixth-order start")) return rc;
-  if (int rc = hermite_evaluate(c, c->posm, c->vel, aj)) return rc;
-  if (int rc = snap_evaluate(c, c->posm, c->vel, aj, 6, b.ajs[c->h6_cur])) return rc;
-  HIP_TRY(c, hipMemsetAsync(b.a3, 0, 12 * n * sizeof(double), c->stream));
-  c->h6_valid = true;
-  c->h6_derivs = false;
-  return NBODY_OK;
-}
-
-// what a sixth-order call does for the fp64 tracers behind hermite6_enter (the bodies' cache is valid, the hm_external rule applied): the
-// cache and the partial rows of both passes at first use; when the tracers' (a0, j0, s0) are not valid, a point jerk pass for the
-// tracers' a and one point snap pass with it and the bodies' cached a0 (the input accelerations of the bodies' own next step: at a start
-// the bodies' jerk pass's, in every bit) as its inputs — two more passes —, and zeros for a3, a4, a5
-int hermite6_tracers_enter(nbody_ctx *c) {
-  const int m = c->tr64_n;
-  if (m <= 0) return NBODY_OK;
-  if (!c->tr64_h6) HIP_TRY(c, hipMalloc(&c->tr64_h6, (30 * (size_t)m + 2 * (size_t)nbody::energy_fast_slots(m)) * sizeof(double)));
-  if (int rc = ensure_probe_part(c, m, 3)) return rc;
-  if (int rc = ensure_probe_part(c, m, nbody::kSnapRowWidth)) return rc;
-  if (c->trh6_valid) return NBODY_OK;
-  const Tracer64Bufs t = tracer64_bufs(c);
-  const TracerH6Bufs q = tracer_h6_bufs(c);
-  double *aj = q.ajs[c->trh6_cur ^ 1];                            // (the jerk pass's six doubles per tracer, in the row a step overwrites)
-  if (int rc = points64_jerk(c, c->posm, c->vel, t.pos, t.vel, m, aj)) return rc;
-  if (int rc = points64_snap(c, c->posm, c->vel, hermite6_bufs(c).ajs[c->h6_cur], 9, t.pos, t.vel, aj, 6, m, q.ajs[c->trh6_cur])) return rc;
-  HIP_TRY(c, hipMemsetAsync(q.a3, 0, 12 * (size_t)m * sizeof(double), c->stream));
-  c->trh6_valid = true;
-  c->trh6_derivs = false;
-  return NBODY_OK;
-}
-
-// the tracers' arrays as the stepping kernels of kernels_snap.hip take the bodies'
-nbody::Hermite6Launch hermite6_tracers_launch(const nbody_ctx *c, double dt) {
-  const Tracer64Bufs t = tracer64_bufs(c);
-  const TracerH6Bufs q = tracer_h6_bufs(c);
-  nbody::Hermite6Launch L;
-  L.posm = t.pos; L.vel = t.vel; L.acc = t.acc; L.xp = t.xp; L.vp = t.vp; L.ap = t.ap; L.ajs0 = q.ajs[c->trh6_cur]; L.ajs1 = q.ajs[c->trh6_cur ^ 1];
-  L.a3 = q.a3; L.a4 = q.a4; L.a5 = q.a5; L.n = c->tr64_n; L.dt = dt;
-  return L;
-}
-
-// one P(EC) step from a valid cache, queued: the predictor and the corrector are the two goes of ONE pass under NBODY_KERNEL_UPDATE.
-// With fp64 tracers (their cache valid: hermite6_tracers_enter) the tracers' predictor and corrector ride in the same two goes; their
-// point snap pass at the bodies' predicted (xp, vp, ap), with their own predicted accelerations, is one more pass under NBODY_KERNEL_FORCES.
-int hermite6_one_step(nbody_ctx *c, double dt) {
-  const Hermite6Bufs b = hermite6_bufs(c);
-  nbody::Hermite6Launch L;
-  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.ap = b.ap; L.ajs0 = b.ajs[c->h6_cur]; L.ajs1 = b.ajs[c->h6_cur ^ 1];
-  L.a3 = b.a3; L.a4 = b.a4; L.a5 = b.a5; L.n = c->p.n_total; L.dt = dt;
-  const bool tracers = c->tr64_n > 0;
-  const nbody::Hermite6Launch T = tracers ? hermite6_tracers_launch(c, dt) : nbody::Hermite6Launch{};
-  int rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
-        HIP_TRY(c, nbody::launch_hermite6_predict(L, c->stream));
-        if (tracers) HIP_TRY(c, nbody::launch_hermite6_predict(T, c->stream));
-        return NBODY_OK;
-      }, false))) return rc;
-  if ((rc = snap_evaluate(c, b.xp, b.vp, b.ap, 4, b.ajs[c->h6_cur ^ 1]))) return rc;
-  if (tracers && (rc = points64_snap(c, b.xp, b.vp, b.ap, 4, T.xp, T.vp, (const double *)T.ap, 4, T.n, tracer_h6_bufs(c).ajs[c->trh6_cur ^ 1]))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
-        HIP_TRY(c, nbody::launch_hermite6_correct(L, c->stream));
-        if (tracers) HIP_TRY(c, nbody::launch_hermite6_correct(T, c->stream));
-        return NBODY_OK;
-      }))) return rc;
-  c->h6_cur ^= 1;                                                  // (a0, j0, s0) := (a1, j1, s1)
-  c->h6_derivs = true;
-  if (tracers) { c->trh6_cur ^= 1; c->trh6_derivs = true; }
-  nbody::hermite_invalidate(c);                                    // the fourth-order cache is not this state's
-  c->sym_posg_valid = false;
-  c->steps_done += 1;
-  return NBODY_OK;
-}
-
-// the time scale of the cached derivatives, waited for: *t from the largest criterion value, *body where, *kind which criterion
-int hermite6_scale(nbody_ctx *c, double *t, int32_t *body, int32_t *kind) {
-  const Hermite6Bufs b = hermite6_bufs(c);
-  HIP_TRY(c, nbody::launch_hermite6_time(b.ajs[c->h6_cur], b.a3, b.a4, b.a5, c->p.n_total, c->h6_derivs, b.partials, (double *)c->scratch, c->stream));
-  double k = 0.0, at = 0.0;
-  if (int rc = read_energy(c, &k, &at)) return rc;                // (the scratch's two doubles: the largest k, its body)
-  if (k == 0.0) *t = HUGE_VAL;
-  else if (!std::isfinite(k)) *t = 0.0;
-  else *t = c->h6_derivs ? 1.0 / std::cbrt(std::sqrt(k)) : 1.0 / std::sqrt(k);
-  *body = (int32_t)at;
-  *kind = c->h6_derivs ? 1 : 0;
-  return NBODY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbody_get_snap_f64(nbody_ctx *c, const double *acc_in, size_t acc_in_stride, double *acc, size_t acc_stride, double *jerk,
-                       size_t jerk_stride, double *snap, size_t snap_stride) {
-  const char *who = "nbody_get_snap_f64";
-  if (c && c->multi) return multi_unsupported(c, who);
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if ((rc = snap_supported(c, who))) return rc;
-  if ((!acc && !jerk && !snap) || (acc_in && acc_in_stride < 24) || (acc && acc_stride < 24) || (jerk && jerk_stride < 24) || (snap && snap_stride < 24))
-    return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null, or a stride < 24", who);
-  const size_t n = (size_t)c->p.n_total, rec = 9 * sizeof(double);
-  if ((rc = ensure_stage(c, n * rec))) return rc;
-  if (!c->snap64) HIP_TRY(c, hipMalloc(&c->snap64, 13 * n * sizeof(double)));
-  if ((rc = ensure_probe_part(c, (int)n, nbody::kSnapRowWidth))) return rc;
-  double *ajs = (double *)c->snap64, *ain = ajs + 9 * n;
-  int ain_stride = 4;
-  if (acc_in) {
-    double *h = (double *)c->h_stage;
-    for (size_t i = 0; i < n; ++i) { memcpy(h + 4 * i, (const char *)acc_in + i * acc_in_stride, 24); h[4 * i + 3] = 0.0; }
-    HIP_TRY(c, hipMemcpyAsync(ain, h, n * 32, hipMemcpyHostToDevice, c->stream));
-  } else {                                                         // the live state's own accelerations, unrounded: the fp64 jerk pass first
-    if ((rc = ensure_jerk64(c))) return rc;
-    if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
-    ain = (double *)c->jerk64; ain_stride = 6;
-  }
-  if ((rc = snap_evaluate(c, c->posm, c->vel, ain, ain_stride, ajs))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, ajs, n * rec, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (acc) scatter_records(acc, acc_stride, c->h_stage, 24, n, rec);
-  if (jerk) scatter_records(jerk, jerk_stride, (const char *)c->h_stage + 24, 24, n, rec);
-  if (snap) scatter_records(snap, snap_stride, (const char *)c->h_stage + 48, 24, n, rec);
-  return NBODY_OK;
-}
-
-int nbody_hermite6_step(nbody_ctx *c, double dt, int32_t nsteps) {
-  int rc = hermite_ready(c, "nbody_hermite6_step");
-  if (rc) return rc;
-  if (!std::isfinite(dt) || nsteps < 0) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_step: dt is not finite, or nsteps < 0");
-  if (!(dt > 0.0) || nsteps == 0) return NBODY_OK;
-  if ((rc = hermite_block_leave(c, "nbody_hermite6_step"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite6_step"))) return rc;
-  if ((rc = hermite6_enter(c))) return rc;
-  if ((rc = hermite6_tracers_enter(c))) return rc;
-  for (int s = 0; s < nsteps; ++s)
-    if ((rc = hermite6_one_step(c, dt))) return rc;
-  return NBODY_OK;
-}
-
-int nbody_hermite6_timescale(nbody_ctx *c, double *t_min, int32_t *body, int32_t *kind) {
-  int rc = hermite_ready(c, "nbody_hermite6_timescale");
-  if (rc) return rc;
-  if (!t_min && !body && !kind) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_timescale: all three outputs are null");
-  if ((rc = hermite_block_leave(c, "nbody_hermite6_timescale"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite6_timescale"))) return rc;
-  if ((rc = hermite6_enter(c))) return rc;
-  double t = 0.0;
-  int32_t at = 0, which = 0;
-  if ((rc = hermite6_scale(c, &t, &at, &which))) return rc;
-  if (t_min) *t_min = t;
-  if (body) *body = at;
-  if (kind) *kind = which;
-  return NBODY_OK;
-}
-
-int nbody_hermite6_advance(nbody_ctx *c, double t_span, double eta, double eta_start, double dt_max, int64_t max_steps, double *t_done,
-                           int64_t *steps) {
-  int rc = hermite_ready(c, "nbody_hermite6_advance");
-  if (rc) return rc;
-  if (!(eta > 0.0) || !(eta_start > 0.0) || !(dt_max > 0.0) || !(t_span >= 0.0) || !std::isfinite(t_span) || max_steps < 0)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_advance: eta, eta_start and dt_max must be > 0, t_span >= 0 and finite, max_steps >= 0");
-  double t_acc = 0.0;
-  int64_t taken = 0;
-  if (t_done) *t_done = 0.0;
-  if (steps) *steps = 0;
-  if (!(t_acc < t_span) || max_steps == 0) return NBODY_OK;
-  if ((rc = hermite_block_leave(c, "nbody_hermite6_advance"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite6_advance"))) return rc;
-  if ((rc = hermite6_enter(c))) return rc;
-  if ((rc = hermite6_tracers_enter(c))) return rc;
-  while (t_acc < t_span && taken < max_steps) {
-    double t = 0.0;
-    int32_t at = 0, which = 0;
-    if ((rc = hermite6_scale(c, &t, &at, &which))) return rc;
-    double dt = std::min(dt_max, which == 1 ? eta * t : eta_start * t);   // (eta times t itself: no square root in this criterion)
-    const double rest = t_span - t_acc;
-    const bool last = dt >= rest;
-    if (last) dt = rest;
-    if (!(dt > 0.0) || !std::isfinite(dt))
-      return fail(c, NBODY_ERR_STATE, "nbody_hermite6_advance: the time scale of body %d gives dt = %g after %lld steps (t = %.17g); the "
-                  "state is that of the last good step", (int)at, dt, (long long)taken, t_acc);
-    if ((rc = hermite6_one_step(c, dt))) return rc;
-    t_acc = last ? t_span : t_acc + dt;
-    taken += 1;
-    if (t_done) *t_done = t_acc;
-    if (steps) *steps = taken;
-  }
-  return NBODY_OK;
-}
-
-int nbody_hermite6_get(nbody_ctx *c, double *d18, size_t stride) {
-  int rc = hermite_ready(c, "nbody_hermite6_get");
-  if (rc) return rc;
-  if (!d18 || stride < 144) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_get: null buffer or stride < 144");
-  if (!c->hermite6 || !c->h6_valid)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_get: no derivatives cached for the stored state (nbody_hermite6_step or nbody_hermite6_timescale first)");
-  const size_t n = (size_t)c->p.n_total;
-  const Hermite6Bufs b = hermite6_bufs(c);
-  if ((rc = ensure_stage(c, n * 168))) return rc;
-  double *h_ajs = (double *)c->h_stage, *h_d = h_ajs + 9 * n;     // (a3, a4 and a5 lie side by side: 12 doubles per body in all)
-  HIP_TRY(c, hipMemcpyAsync(h_ajs, b.ajs[c->h6_cur], n * 72, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_d, b.a3, n * 96, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < n; ++i) {
-    double rec[18];
-    memcpy(rec, h_ajs + 9 * i, 72);
-    for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * n + i), 24);   // (zeros until a step has been taken)
-    memcpy((char *)d18 + i * stride, rec, 144);
-  }
-  return NBODY_OK;
-}
-
-}  // extern "C"
-
-// ---- fp64 point queries and the fp64 tracers' public calls (kernels_points64.hip) ----
-namespace {
-// where they exist — the contexts that answer nbody_hermite_step: fp64 state, one device, all bodies — and when: a state set, no step half done
-int points64_ready(nbody_ctx *c, const char *who) {
-  if (!c) return NBODY_ERR_INVALID;
-  if (c->multi) return multi_unsupported(c, who);
-  if (c->p.precision != NBODY_PREC_F64)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): its points are doubles "
-                "in the field of fp64 bodies; create the context with NBODY_PREC_F64 (fp32 contexts have nbody_jerk_at and nbody_set_tracers)", who);
-  if (c->p.i_count != c->p.n_total)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
-  if (int rc = check_ready(c)) return rc;
-  if (c->step_open || c->step_local) return fail(c, NBODY_ERR_STATE, "%s: a step is open (nbody_step_end first)", who);
-  return NBODY_OK;
-}
-
-// n records of three doubles, `stride` bytes apart (NULL: zeros), as double4 rows with a fourth component of 0
-void gather_double4(double *dst, const double *src, size_t stride, size_t n) {
-  for (size_t k = 0; k < n; ++k) {
-    if (src) memcpy(dst + 4 * k, (const char *)src + k * stride, 24);
-    else     dst[4 * k] = dst[4 * k + 1] = dst[4 * k + 2] = 0.0;
-    dst[4 * k + 3] = 0.0;
-  }
-}
-
-// the time scale of the tracers' cached derivatives, waited for — hermite_scale / hermite6_scale over the tracers' arrays
-int hermite_tracers_scale(nbody_ctx *c, double *t, int32_t *at, int32_t *kind) {
-  const TracerH4Bufs q = tracer_h4_bufs(c);
-  const int m = c->tr64_n;
-  if (c->trh_derivs) HIP_TRY(c, nbody::launch_hermite_time(q.aj[c->trh_cur], q.a2, q.a3, m, q.partials, (double *)c->scratch, c->stream));
-  else               HIP_TRY(c, nbody::launch_jerk_time(q.aj[c->trh_cur], m, q.partials, (double *)c->scratch, c->stream));
-  double k = 0.0, where = 0.0;
-  if (int rc = read_energy(c, &k, &where)) return rc;
-  *t = k == 0.0 ? HUGE_VAL : (std::isfinite(k) ? 1.0 / std::sqrt(k) : 0.0);
-  *at = (int32_t)where;
-  *kind = c->trh_derivs ? 1 : 0;
-  return NBODY_OK;
-}
-int hermite6_tracers_scale(nbody_ctx *c, double *t, int32_t *at, int32_t *kind) {
-  const TracerH6Bufs q = tracer_h6_bufs(c);
-  HIP_TRY(c, nbody::launch_hermite6_time(q.ajs[c->trh6_cur], q.a3, q.a4, q.a5, c->tr64_n, c->trh6_derivs, q.partials, (double *)c->scratch, c->stream));
-  double k = 0.0, where = 0.0;
-  if (int rc = read_energy(c, &k, &where)) return rc;
-  if (k == 0.0) *t = HUGE_VAL;
-  else if (!std::isfinite(k)) *t = 0.0;
-  else *t = c->trh6_derivs ? 1.0 / std::cbrt(std::sqrt(k)) : 1.0 / std::sqrt(k);
-  *at = (int32_t)where;
-  *kind = c->trh6_derivs ? 1 : 0;
-  return NBODY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbody_jerk_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n, double *acc,
-                      size_t acc_stride, double *jerk, size_t jerk_stride) {
-  const char *who = "nbody_jerk_at_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (n < 0 || !pos || pos_stride < 24 || (vel && vel_stride < 24) || (!acc && !jerk) || (acc && acc_stride < 24) || (jerk && jerk_stride < 24))
-    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, both outputs null, or a stride < 24", who);
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n;
-  if ((rc = ensure_probe_part(c, n, 3))) return rc;
-  if ((rc = ensure_stage(c, m * 14 * sizeof(double)))) return rc;   // the points and their velocities as double4, behind them six doubles per point
-  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  gather_double4(h + 4 * m, vel, vel_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(d, h, m * 64, hipMemcpyHostToDevice, c->stream));
-  if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + 8 * m, d + 8 * m, m * 48, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (acc) scatter_records(acc, acc_stride, h + 8 * m, 24, m, 48);
-  if (jerk) scatter_records(jerk, jerk_stride, h + 8 * m + 3, 24, m, 48);
-  return NBODY_OK;
-}
-
-int nbody_set_tracers_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n) {
-  const char *who = "nbody_set_tracers_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!pos || pos_stride < 24 || (vel && vel_stride < 24))))
-    return fail(c, NBODY_ERR_INVALID, "%s: n < 0, null positions, or a stride < 24", who);
-  if (n > 0 && (c->hb.active || c->h6b.active))
-    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is active, and the block scheduler carries no tracers; nbody_hermite_restart "
-                "ends the session", who);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (void **q : {&c->tr64, &c->tr64_h4, &c->tr64_h6}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-  c->tr64_n = 0;
-  c->trh_valid = c->trh_derivs = c->trh6_valid = c->trh6_derivs = false;   // the tracers' caches, and only those
-  c->trh_cur = c->trh6_cur = 0;
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n;
-  if ((rc = ensure_stage(c, m * 64))) return rc;
-  HIP_TRY(c, hipMalloc(&c->tr64, 24 * m * sizeof(double)));
-  double *h = (double *)c->h_stage;
-  gather_double4(h, pos, pos_stride, m);
-  gather_double4(h + 4 * m, vel, vel_stride, m);
-  HIP_TRY(c, hipMemsetAsync(c->tr64, 0, 24 * m * sizeof(double), c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->tr64, h, m * 64, hipMemcpyHostToDevice, c->stream));   // pos and vel lie side by side
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->tr64_n = n;
-  return NBODY_OK;
-}
-
-int nbody_get_tracers_f64(nbody_ctx *c, double *pos, size_t pos_stride, double *vel, size_t vel_stride) {
-  const char *who = "nbody_get_tracers_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if ((pos && pos_stride < 24) || (vel && vel_stride < 24)) return fail(c, NBODY_ERR_INVALID, "%s: a stride < 24", who);
-  const size_t m = (size_t)c->tr64_n;
-  if (m == 0 || (!pos && !vel)) return NBODY_OK;
-  if ((rc = ensure_stage(c, m * 64))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->tr64, m * 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const double *h = (const double *)c->h_stage;
-  if (pos) scatter_records(pos, pos_stride, h, 24, m, 32);
-  if (vel) scatter_records(vel, vel_stride, h + 4 * m, 24, m, 32);
-  return NBODY_OK;
-}
-
-int nbody_tracer_count_f64(nbody_ctx *c, int32_t *n) {
-  int rc = points64_ready(c, "nbody_tracer_count_f64");
-  if (rc) return rc;
-  if (!n) return fail(c, NBODY_ERR_INVALID, "nbody_tracer_count_f64: null output");
-  *n = c->tr64_n;
-  return NBODY_OK;
-}
-
-int nbody_hermite_tracers_get(nbody_ctx *c, double *d12, size_t stride) {
-  int rc = points64_ready(c, "nbody_hermite_tracers_get");
-  if (rc) return rc;
-  if (!d12 || stride < 96) return fail(c, NBODY_ERR_INVALID, "nbody_hermite_tracers_get: null buffer or stride < 96");
-  const size_t m = (size_t)c->tr64_n;
-  if (m == 0) return NBODY_OK;
-  if (!c->tr64_h4 || !c->trh_valid)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite_tracers_get: no derivatives cached for the stored tracers (nbody_hermite_step or "
-                "nbody_hermite_tracers_timescale first)");
-  const TracerH4Bufs q = tracer_h4_bufs(c);
-  if ((rc = ensure_stage(c, m * 112))) return rc;
-  double *h_aj = (double *)c->h_stage, *h_d = h_aj + 6 * m;       // (a2 and a3 lie side by side: 8 doubles per tracer in all)
-  HIP_TRY(c, hipMemcpyAsync(h_aj, q.aj[c->trh_cur], m * 48, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_d, q.a2, m * 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < m; ++i) {
-    double rec[12];
-    memcpy(rec, h_aj + 6 * i, 48);
-    memcpy(rec + 6, h_d + 4 * i, 24);                              // (zeros until a step has been taken)
-    memcpy(rec + 9, h_d + 4 * (m + i), 24);
-    memcpy((char *)d12 + i * stride, rec, 96);
-  }
-  return NBODY_OK;
-}
-
-int nbody_hermite6_tracers_get(nbody_ctx *c, double *d18, size_t stride) {
-  int rc = points64_ready(c, "nbody_hermite6_tracers_get");
-  if (rc) return rc;
-  if (!d18 || stride < 144) return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_tracers_get: null buffer or stride < 144");
-  const size_t m = (size_t)c->tr64_n;
-  if (m == 0) return NBODY_OK;
-  if (!c->tr64_h6 || !c->trh6_valid)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_tracers_get: no derivatives cached for the stored tracers (nbody_hermite6_step or "
-                "nbody_hermite6_tracers_timescale first)");
-  const TracerH6Bufs q = tracer_h6_bufs(c);
-  if ((rc = ensure_stage(c, m * 168))) return rc;
-  double *h_ajs = (double *)c->h_stage, *h_d = h_ajs + 9 * m;     // (a3, a4 and a5 lie side by side: 12 doubles per tracer in all)
-  HIP_TRY(c, hipMemcpyAsync(h_ajs, q.ajs[c->trh6_cur], m * 72, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_d, q.a3, m * 96, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < m; ++i) {
-    double rec[18];
-    memcpy(rec, h_ajs + 9 * i, 72);
-    for (size_t k = 0; k < 3; ++k) memcpy(rec + 9 + 3 * k, h_d + 4 * (k * m + i), 24);   // (zeros until a step has been taken)
-    memcpy((char *)d18 + i * stride, rec, 144);
-  }
-  return NBODY_OK;
-}
-
-int nbody_hermite_tracers_timescale(nbody_ctx *c, double *t_min, int32_t *tracer, int32_t *kind) {
-  const char *who = "nbody_hermite_tracers_timescale";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!t_min && !tracer && !kind) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
-  if (c->tr64_n <= 0) return fail(c, NBODY_ERR_STATE, "%s: the context holds no fp64 tracers (nbody_set_tracers_f64 first)", who);
-  if (c->hm_external) { nbody::hermite_invalidate(c); nbody::hermite6_invalidate(c); }
-  if ((rc = hermite_tracers_enter(c))) return rc;                  // (a0, j0) of the stored tracers, if they are not valid: the bodies' cache is not needed
-  double t = 0.0;
-  int32_t at = 0, which = 0;
-  if ((rc = hermite_tracers_scale(c, &t, &at, &which))) return rc;
-  if (t_min) *t_min = t;
-  if (tracer) *tracer = at;
-  if (kind) *kind = which;
-  return NBODY_OK;
-}
-
-int nbody_hermite6_tracers_timescale(nbody_ctx *c, double *t_min, int32_t *tracer, int32_t *kind) {
-  const char *who = "nbody_hermite6_tracers_timescale";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!t_min && !tracer && !kind) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
-  if (c->tr64_n <= 0) return fail(c, NBODY_ERR_STATE, "%s: the context holds no fp64 tracers (nbody_set_tracers_f64 first)", who);
-  if ((rc = hermite6_enter(c))) return rc;                         // the tracers' start reads the bodies' a0
-  if ((rc = hermite6_tracers_enter(c))) return rc;
-  double t = 0.0;
-  int32_t at = 0, which = 0;
-  if ((rc = hermite6_tracers_scale(c, &t, &at, &which))) return rc;
-  if (t_min) *t_min = t;
-  if (tracer) *tracer = at;
-  if (kind) *kind = which;
-  return NBODY_OK;
-}
-
-}  // extern "C"
-
-// ---- sixth-order Hermite block time steps: a session of per-body power-of-two steps on the sixth-order cache (kernels_hermite6_block.hip) ----
-namespace {
-nbody::Hermite6BlockLaunch hermite6_block_launch(const nbody_ctx *c) {
-  const Hermite6Bufs b = hermite6_bufs(c);
-  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, (size_t)c->p.n_total);
-  nbody::Hermite6BlockLaunch L;
-  L.posm = c->posm; L.vel = c->vel; L.acc = c->acc; L.xp = b.xp; L.vp = b.vp; L.ap = b.ap; L.ajs0 = b.ajs[c->h6_cur];
-  L.a3 = b.a3; L.a4 = b.a4; L.a5 = b.a5;
-  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = q.record;
-  L.floor_hits = q.floor_hits; L.n = c->p.n_total; L.levels = c->h6b.levels; L.tick = c->h6b.tick; L.dt_max = c->h6b.dt_max;
-  L.eta = c->h6b.eta; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-  return L;
-}
-
-// the totals since begin; the levels' range and the floor hits are read from the device (4 n + 8 bytes): waits for the stream
-int hermite6_block_fill(nbody_ctx *c, nbody_hermite_block_stats *out) {
-  const size_t n = (size_t)c->p.n_total;
-  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, n);
-  if (int rc = ensure_stage(c, n * 4 + 8)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.floor_hits, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int64_t floor_hits;
-  memcpy(&floor_hits, c->h_stage, 8);
-  const int32_t *lv = (const int32_t *)((const char *)c->h_stage + 8);
-  out->synchronised = (c->h6b.ticks & ((1ll << c->h6b.levels) - 1)) == 0 ? 1 : 0;
-  out->ticks = c->h6b.ticks; out->frames_done = c->h6b.ticks >> c->h6b.levels; out->block_steps = c->h6b.block_steps;
-  out->body_steps = c->h6b.body_steps; out->pairs = c->h6b.pairs; out->floor_hits = floor_hits;
-  out->level_min = *std::min_element(lv, lv + n); out->level_max = *std::max_element(lv, lv + n);
-  return NBODY_OK;
-}
-
-// one block step, from the schedule to the stored bodies; the host waits once, for (T_next, m), to size the evaluation.  An active set
-// larger than a slab of partial rows goes through evaluation and corrector slab by slab: the predicted state is in buffers of its own, so
-// a corrected slab changes nothing a later slab's evaluation reads.
-int hermite6_block_one_step(nbody_ctx *c) {
-  const nbody::Hermite6BlockLaunch L = hermite6_block_launch(c);
-  int rc;
-  if ((rc = probe_part_holds(c, nbody::kSnapRowWidth, "the snap pass of a block step"))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_schedule(L, c->stream)); return NBODY_OK; }, false))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  long long rec[2];
-  memcpy(rec, c->h_scratch, 16);
-  const long long t_next = rec[0];
-  const int n = c->p.n_total, m = (int)rec[1];
-  if (rec[1] < 1 || rec[1] > n || t_next <= c->h6b.ticks)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_advance: the schedule gave T_next = %lld, m = %lld at tick %lld", t_next, rec[1], (long long)c->h6b.ticks);
-  const int lanes = nbody::hermite_block_lanes(m, c->h6b.lanes);
-  const int slab = (int)std::min<size_t>(nbody::probe_slab_points(n, nbody::kSnapRowWidth), (size_t)n);
-  for (int first = 0; first < m; first += slab) {
-    const int ms = std::min(slab, m - first);
-    const bool last = first + ms == m;
-    if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_evaluate(L, first, ms, lanes, c->stream)); return NBODY_OK; }, last))) return rc;
-    if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, nbody::launch_hermite6_block_correct(L, first, ms, t_next, c->stream)); return NBODY_OK; }, last))) return rc;
-  }
-  c->h6b.ticks = t_next;
-  c->h6b.block_steps += 1; c->h6b.body_steps += m; c->h6b.pairs += (int64_t)m * n;
-  if (c->h6b.ticks >= (1ll << c->h6b.levels)) c->h6_derivs = true;   // a whole frame: every body has stepped, every a3, a4, a5 is a step's
-  c->sym_posg_valid = false;
-  c->steps_done += 1;
-  return NBODY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbody_hermite6_block_level(double k, double dt_max, int32_t levels, double eta, int32_t *floor_hit) {
-  if (levels < 0 || levels > nbody::kHermiteBlockMaxLevels) return -1;
-  int hit = 0;
-  const int kw = nbody::hermite6_block_level(k, dt_max, levels, eta, &hit);
-  if (floor_hit) *floor_hit = hit;
-  return kw;
-}
-
-int nbody_hermite6_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
-  int rc = hermite_ready(c, "nbody_hermite6_block_begin");
-  if (rc) return rc;
-  const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (!positive(dt_max) || !positive(eta) || !positive(eta_start) || levels < 0 || levels > nbody::kHermiteBlockMaxLevels)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: dt_max, eta and eta_start must be finite and > 0, levels 0 .. %d", nbody::kHermiteBlockMaxLevels);
-  const double tick = std::ldexp(dt_max, -levels);
-  if (!std::isnormal(tick) || !std::isnormal((tick * tick) * tick))
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: the tick dt_max 2^-levels = %g or its cube, which the level rule compares, is not "
-                "a normal number", tick);
-  if (c->tr64_n > 0)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "nbody_hermite6_block_begin: the context holds %d fp64 tracers, which the block scheduler does not "
-                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them", c->tr64_n);
-  const int n = c->p.n_total;
-  if (level_in)
-    for (int i = 0; i < n; ++i)
-      if (level_in[i] < 0 || level_in[i] > levels)
-        return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_begin: level_in[%d] = %d is outside 0 .. %d", i, (int)level_in[i], (int)levels);
-  if ((rc = hermite_block_leave(c, "nbody_hermite6_block_begin"))) return rc;
-  if ((rc = hermite6_block_leave(c, "nbody_hermite6_block_begin"))) return rc;
-  if ((rc = hermite6_enter(c))) return rc;
-  nbody::hermite_invalidate(c);                                    // (the state moves on without the fourth-order cache)
-  if (!c->h6block) HIP_TRY(c, hipMalloc(&c->h6block, hermite_block_bytes(n)));
-  c->h6b.levels = levels; c->h6b.dt_max = dt_max; c->h6b.tick = tick; c->h6b.eta = eta;
-  c->h6b.lanes = nbody::env_int("NBODY_HERMITE6_BLOCK_LANES", 0);
-  c->h6b.ticks = c->h6b.block_steps = c->h6b.body_steps = c->h6b.pairs = 0;
-  const nbody::Hermite6BlockLaunch L = hermite6_block_launch(c);
-  if (!c->h6_derivs) HIP_TRY(c, hipMemsetAsync(L.a3, 0, (size_t)n * 96, c->stream));   // a3, a4, a5 lie side by side: zeros until a body steps
-  HIP_TRY(c, hipMemsetAsync(L.record, 0, 24, c->stream));          // the record and the floor hits
-  if (level_in) HIP_TRY(c, hipMemcpyAsync(L.list, level_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, nbody::launch_hermite6_block_init(L, level_in ? L.list : nullptr, eta_start, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's array is its own again
-  c->h6b.active = true;
-  return NBODY_OK;
-}
-
-int nbody_hermite6_block_advance(nbody_ctx *c, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out) {
-  int rc = hermite_ready(c, "nbody_hermite6_block_advance");
-  if (rc) return rc;
-  if (frames < 0 || max_block_steps < 0 || (out && out->struct_size != sizeof(nbody_hermite_block_stats)))
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_advance: frames < 0, max_block_steps < 0, or out->struct_size is not "
-                "sizeof(nbody_hermite_block_stats) = %d", (int)sizeof(nbody_hermite_block_stats));
-  if (!c->h6b.active)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_advance: no sixth-order block session (nbody_hermite6_block_begin first; uploads, "
-                "kick-drift steps, handed-out pointers, shared Hermite steps and nbody_hermite_restart end one)");
-  const int64_t frame_now = c->h6b.ticks >> c->h6b.levels;
-  if (frames >= (1ll << 62 >> c->h6b.levels) - frame_now)
-    return fail(c, NBODY_ERR_INVALID, "nbody_hermite6_block_advance: %lld more frames of 2^%d ticks pass 2^62 ticks", (long long)frames, c->h6b.levels);
-  const int64_t target = frames == 0 ? c->h6b.ticks : (frame_now + frames) << c->h6b.levels;
-  for (int64_t taken = 0; c->h6b.ticks < target && taken < max_block_steps; ++taken)
-    if ((rc = hermite6_block_one_step(c))) return rc;
-  return out ? hermite6_block_fill(c, out) : NBODY_OK;
-}
-
-int nbody_hermite6_block_get(nbody_ctx *c, int64_t *ticks, int32_t *level) {
-  int rc = hermite_ready(c, "nbody_hermite6_block_get");
-  if (rc) return rc;
-  if (!c->h6b.active)
-    return fail(c, NBODY_ERR_STATE, "nbody_hermite6_block_get: no sixth-order block session (nbody_hermite6_block_begin first)");
-  const size_t n = (size_t)c->p.n_total;
-  const HermiteBlockBufs q = hermite_block_bufs_at(c->h6block, n);
-  if ((rc = ensure_stage(c, n * 12))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.T, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + n * 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (ticks) memcpy(ticks, c->h_stage, n * 8);
-  if (level) memcpy(level, (const char *)c->h_stage + n * 8, n * 4);
   return NBODY_OK;
 }
 

@@ -1,4 +1,4 @@
-// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, bh_driver.hip) share: error
+// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, capi_hermite.hip, bh_driver.hip) share: error
 // texts, the device made current, the kernel timers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,35 @@ struct KernelTimer {
   std::vector<EventPair> pool;      // free
   double total_ms = 0.0;
   int64_t launches = 0;
+};
+
+// One cache of Hermite derivatives — the bodies' or the fp64 tracers', of one order —, allocated at first use.  With `count` the bodies
+// (n_total) or the tracers (tr64_n), buf holds, in doubles:
+//   the bodies' caches only: the predicted arrays, [count] double4 each
+//   the higher derivatives a step leaves, [count] double4 each
+//   two rows of the evaluated derivatives, [count][width] each: row `cur` is the stored state's, the other takes the predicted state's
+//     (and, at a sixth-order start, the jerk pass's [count][6])
+//   the time scale's reduction: its workgroup pairs
+//                  predicted    higher derivatives   a row             width
+//   fourth order   xp, vp       a2, a3               (a0, j0)          6
+//   sixth order    xp, vp, ap   a3, a4, a5           (a0, j0, s0)      9
+// (the tracers' predicted arrays lie in tr64)
+struct HermiteCache {
+  void *buf = nullptr;
+  int cur = 0;
+  bool valid = false;    // row `cur` is that of the stored (x, v) — the tracers': of the stored tracers in the stored bodies' field
+  bool derivs = false;   // the higher derivatives are those a step left at the stored state (sixth order and the tracers: zeros otherwise)
+};
+
+// One session of Hermite block time steps on the bodies' cache of its order.  buf, allocated at the first begin: T [n] int64, the
+// scheduler's segment minima [slots] int64, the record (T_next, m) and the floor-hit count (int64 each), then level [n], list [n] and the
+// segment counts [slots] as int32
+struct HermiteBlockSession {
+  void *buf = nullptr;
+  bool active = false;         // between the order's block_begin and whatever ends the session
+  int levels = 0, lanes = 0;   // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE_BLOCK_LANES / NBODY_HERMITE6_BLOCK_LANES (0: by the list's length)
+  double dt_max = 0.0, tick = 0.0, eta = 0.0;
+  int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
 };
 
 }  // namespace nbody
@@ -97,51 +126,17 @@ struct nbody_ctx {
   void *tidal64 = nullptr;     // nbody_tidal_time: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
   void *jerk64 = nullptr;      // nbody_get_jerk_f64 / nbody_jerk_time: [n_total][6] double, the bodies' unrounded (a, j), then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
-  // fourth-order Hermite stepping (nbody_hermite_*, kernels_hermite.hip; fp64 contexts): allocated at first use.  hermite holds, in
-  // doubles, xp, vp, a2, a3 ([n_total] double4 each), two rows of (a, j) ([n_total][6] each: hm_cur is (a0, j0), the other takes the
-  // predicted state's), then the reduction's workgroup pairs
-  void *hermite = nullptr;
-  int hm_cur = 0;
-  bool hm_valid = false;       // (a0, j0) are those of the stored (x, v)
-  bool hm_derivs = false;      // a2, a3 are those a step left at the stored state
-  bool hm_external = false;    // a buffer was bound or a pointer handed out: somebody else may write the state, every call evaluates anew
-  // sixth-order Hermite stepping (nbody_hermite6_*, kernels_snap.hip; fp64 contexts): a cache of its own, allocated at first use.
-  // hermite6 holds, in doubles, xp, vp, ap, a3, a4, a5 ([n_total] double4 each), two rows of (a, j, s) ([n_total][9] each: h6_cur is
-  // (a0, j0, s0), the other takes the predicted state's — and, at a start, the jerk pass's [n_total][6]), then the reduction's workgroup
-  // pairs.  hm_external rules this cache as it rules the fourth-order one.
-  void *hermite6 = nullptr;
-  int h6_cur = 0;
-  bool h6_valid = false;       // (a0, j0, s0) are those of the stored (x, v)
-  bool h6_derivs = false;      // a3, a4, a5 are those a step left at the stored state (zeros otherwise)
-  void *snap64 = nullptr;      // nbody_get_snap_f64: [n_total][9] double, the bodies' (a, j, s), then [n_total] double4, the input accelerations
-  // Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip): a session on the cache above.  hblock, allocated at the
-  // first begin: T [n] int64, the scheduler's segment minima [slots] int64, the record (T_next, m) and the floor-hit count (int64 each),
-  // then level [n], list [n] and the segment counts [slots] as int32
-  void *hblock = nullptr;
-  struct {
-    bool active = false;       // between nbody_hermite_block_begin and whatever ends the session
-    int levels = 0, lanes = 0; // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE_BLOCK_LANES (0: by the list's length)
-    double dt_max = 0.0, tick = 0.0, root_eta = 0.0;
-    int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
-  } hb;
-  // Sixth-order Hermite block time steps (nbody_hermite6_block_*, kernels_hermite6_block.hip): a session of its own on the sixth-order
-  // cache.  h6block, allocated at the first begin, is laid out like hblock
-  void *h6block = nullptr;
-  struct {
-    bool active = false;       // between nbody_hermite6_block_begin and whatever ends the session
-    int levels = 0, lanes = 0; // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE6_BLOCK_LANES (0: by the list's length)
-    double dt_max = 0.0, tick = 0.0, eta = 0.0;
-    int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
-  } h6b;
+  // Hermite stepping of fp64 contexts (capi_hermite.hip), every instance indexed by order: [0] fourth (nbody_hermite_*,
+  // kernels_hermite.hip, kernels_hermite_block.hip), [1] sixth (nbody_hermite6_*, kernels_snap.hip, kernels_hermite6_block.hip)
+  nbody::HermiteCache hm[2];          // the bodies' caches
+  bool hm_external = false;           // a buffer was bound or a pointer handed out: somebody else may write the state, every call of either order evaluates anew
+  nbody::HermiteBlockSession hb[2];   // the block sessions, each on its order's cache
+  void *snap64 = nullptr;             // nbody_get_snap_f64: [n_total][9] double, the bodies' (a, j, s), then [n_total] double4, the input accelerations
   // fp64 tracers (nbody_set_tracers_f64, kernels_points64.hip): massless points the four shared-step Hermite calls carry beside the
-  // bodies.  tr64 holds, in doubles, pos, vel, acc, xp, vp, ap ([tr64_n] double4 each).  Each order's cache is allocated at first use and
-  // laid out like the bodies': tr64_h4 = a2, a3 ([tr64_n] double4 each), two rows of (a, j) ([tr64_n][6] each: trh_cur is (a0, j0)),
-  // the reduction's workgroup pairs; tr64_h6 = a3, a4, a5, two rows of (a, j, s) ([tr64_n][9] each: trh6_cur), the workgroup pairs.
+  // bodies.  tr64 holds, in doubles, pos, vel, acc, xp, vp, ap ([tr64_n] double4 each); trh are their caches.
   int tr64_n = 0;
-  void *tr64 = nullptr, *tr64_h4 = nullptr, *tr64_h6 = nullptr;
-  int trh_cur = 0, trh6_cur = 0;
-  bool trh_valid = false, trh6_valid = false;     // the tracers' (a0, j0) / (a0, j0, s0) are those of the stored tracers in the stored bodies' field
-  bool trh_derivs = false, trh6_derivs = false;   // a2, a3 / a3, a4, a5 are those a step left (zeros otherwise)
+  void *tr64 = nullptr;
+  nbody::HermiteCache trh[2];
   bool bh_tree_valid = false;  // the tree in the Barnes-Hut state's arrays is that of a frame that was built, with bh_tree_theta
   float bh_tree_theta = 0.0f;
   nbody::KernelTimer timers[2];
@@ -177,20 +172,19 @@ inline int use_device(nbody_ctx *c) {
   return NBODY_OK;
 }
 
-// The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): the
-// cached derivatives are no longer theirs.  The next Hermite call evaluates (a0, j0) anew and has no a2, a3; a block session ends.
-// The fp64 tracers' fourth-order cache goes with the bodies': it was evaluated in the field of a state that is no longer the stored one.
-inline void hermite_invalidate(nbody_ctx *c) {
-  c->hm_valid = false; c->hm_derivs = false; c->hb.active = false;
-  c->trh_valid = false; c->trh_derivs = false;
+// One order's caches are no longer the stored state's: the next call of that order evaluates anew and has no higher derivatives, the
+// order's block session ends, and the fp64 tracers' cache of that order — evaluated in the field of a state that is no longer the
+// stored one — goes with the bodies'.  capi_hermite.hip alone forgets one order without the other (the table in DESIGN.md).
+inline void hermite_invalidate_order(nbody_ctx *c, int order_index) {
+  c->hm[order_index].valid = c->hm[order_index].derivs = false;
+  c->hb[order_index].active = false;
+  c->trh[order_index].valid = c->trh[order_index].derivs = false;
 }
-// The same for the sixth-order cache, which every caller of hermite_invalidate forgets as well — and so do the fourth-order calls that
-// step the state (nbody_hermite_step, nbody_hermite_advance, nbody_hermite_block_begin), whose cache a sixth-order step forgets in turn.
-// A sixth-order block session lives on that cache and ends with it.
-// The fp64 tracers' sixth-order cache goes with it.
-inline void hermite6_invalidate(nbody_ctx *c) {
-  c->h6_valid = false; c->h6_derivs = false; c->h6b.active = false;
-  c->trh6_valid = false; c->trh6_derivs = false;
+// The stored (x, v) are about to change by something other than a Hermite step (an upload, a kick-drift step, a caller's pointer): both
+// orders forget.
+inline void hermite_invalidate(nbody_ctx *c) {
+  hermite_invalidate_order(c, 0);
+  hermite_invalidate_order(c, 1);
 }
 
 // ---- kernel timers (time_kernels): one event pair around every pass, read when nbody_kernel_time asks or the list grows long
