@@ -791,15 +791,71 @@ NBODY_AMD_API int nbody_hermite6_block_get(nbody_ctx *ctx, int64_t *ticks, int32
  *   under NBODY_KERNEL_FORCES, the allocations of a first sixth-order call, and nbody_hermite6_get succeeds afterwards where it would
  *   have reported NBODY_ERR_STATE.  The fourth-order call needs and touches nothing of the bodies' caches.
  *
- * Block sessions carry no fp64 tracers: nbody_hermite_block_begin and nbody_hermite6_block_begin report NBODY_ERR_UNSUPPORTED on a
- * context that holds some — nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them —, and nbody_set_tracers_f64 with n > 0 reports
- * NBODY_ERR_STATE while a block session of either order is active.
+ * Block sessions and fp64 tracers.  nbody_hermite_block_begin and nbody_hermite6_block_begin still report NBODY_ERR_UNSUPPORTED on a
+ * context that holds some — nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them, nbody_hermite[6]_block_begin_tracers starts a
+ * session that CARRIES them —, and nbody_set_tracers_f64 with n > 0 reports NBODY_ERR_STATE while a block session of either order is
+ * active.
+ *
+ * nbody_hermite_block_begin_tracers / nbody_hermite6_block_begin_tracers: the plain begin of the order — its argument rules, contexts
+ *   and error codes — for a context that may hold fp64 tracers.  WITHOUT tracers it IS the plain begin, every byte and every launch
+ *   (a non-NULL tracer_level_in is then NBODY_ERR_INVALID).  WITH tracers it applies the plain begin's rules to the bodies, fills the
+ *   tracers' cache of its order where that is invalid (one pass under NBODY_KERNEL_FORCES more in fourth order, two in sixth, behind the
+ *   bodies' own start; the higher derivatives then read as zeros), sets every tracer's T := 0 and takes the tracers' levels from
+ *   tracer_level_in: nbody_tracer_count_f64 values, each 0 .. levels (else NBODY_ERR_INVALID, the message names the index).  NULL: the
+ *   bodies' start rule on the tracer's own (a0, j0): k = |j|^2 / |a|^2, dt_c = eta_start t, nbody_hermite_block_level(dt_c, ...); a
+ *   tracer that no level fits is a TRACER floor hit.
+ * One block step of a session that carries tracers — the joint schedule:
+ *   schedule   T_next = min over bodies AND tracers of T + step.  Two active lists, each in ascending index: the m_b bodies and the m_t
+ *              tracers that attain T_next; m_b + m_t >= 1, either may be 0.  EVERY body and EVERY tracer is predicted to T_next with its
+ *              own dt_i = (double)(T_next - T_i) tick by the order's block predictor.
+ *   bodies     the active bodies are evaluated against all N predicted bodies and corrected, exactly as without tracers.
+ *   tracers    the active tracers are evaluated against all N PREDICTED bodies — fourth order: (xp, vp); sixth: (xp, vp, ap), with the
+ *              tracer's own predicted ap as its input acceleration — by the point forms of the jerk / snap pass, and corrected by the
+ *              order's block corrector with the tracer's own dt_i: T_i := T_next, the same level rule, one level up at most and only
+ *              when aligned.  Inactive tracers and inactive bodies keep every byte.
+ *   A tracer's result depends neither on other tracers, nor on its place in the list, nor on M, the slab or the points per lane
+ *   (NBODY_HERMITE_BLOCK_LANES / NBODY_HERMITE6_BLOCK_LANES govern the tracers' evaluation too), and the bodies advance BYTE FOR BYTE
+ *   as in the same session without tracers.  N bodies with M tracers equal, in every byte after every block step, a context that holds
+ *   the tracers as M bodies of mass 0 behind the bodies in a plain session with level_in = the bodies' levels followed by the tracers'
+ *   (N + M <= 32768) — at (m_b + m_t) N pairs a block step instead of (m_b + m_t) (N + M).
+ *   nbody_steps_done and nbody_hermite_block_stats.block_steps grow by one per block step, tracer-only ones included; body_steps, pairs,
+ *   floor_hits and level_min / level_max of nbody_hermite_block_stats stay the BODIES' alone.  A block step is one pass under
+ *   NBODY_KERNEL_UPDATE and one under NBODY_KERNEL_FORCES per non-empty evaluation: one or two.  The host waits once per block step and
+ *   reads 32 bytes.
+ * nbody_hermite_block_tracers_get / nbody_hermite6_block_tracers_get: T_i and k_i of the tracers the session carries and their totals
+ *   since begin (set stats->struct_size = sizeof(nbody_hermite_block_tracer_stats) first, another size is NBODY_ERR_INVALID); any of the
+ *   three outputs may be NULL, not all three.  A session without tracers: carried = 0, nothing else written.  No session of that order:
+ *   NBODY_ERR_STATE.  Synchronises.
+ * Sessions.  At a frame end every tracer is at the frame end too; once a whole frame has passed the tracers' cache has its higher
+ *   derivatives, like the bodies'.  Shared-step calls at a frame end end the session and go on from both caches, carrying the tracers as
+ *   they always do; in mid-frame they report NBODY_ERR_STATE, and nbody_hermite[6]_tracers_timescale follows nbody_hermite[6]_timescale's
+ *   rule there.  nbody_hermite[6]_tracers_get and nbody_get_tracers_f64 work during a session: a row belongs to its tracer's own T_i,
+ *   the state is ragged in mid-frame.  nbody_set_tracers_f64 with ANY n, 0 included, reports NBODY_ERR_STATE while a session that
+ *   carries tracers is active (nbody_hermite_restart ends it first).  Whatever ends a plain session ends a carrying one.  Checkpoints
+ *   stay NBDYCKP2 byte for byte: "save, nbody_hermite_restart, begin_tracers with the levels of _block_get and _block_tracers_get, go on"
+ *   on the writing context equals, in every byte, "load, nbody_set_tracers_f64 with what nbody_get_tracers_f64 gave, the same begin, go
+ *   on" on a fresh one.
  */
 NBODY_AMD_API int nbody_jerk_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
                                     double *acc, size_t acc_stride, double *jerk, size_t jerk_stride);
 NBODY_AMD_API int nbody_set_tracers_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n);
 NBODY_AMD_API int nbody_get_tracers_f64(nbody_ctx *ctx, double *pos, size_t pos_stride, double *vel, size_t vel_stride);
 NBODY_AMD_API int nbody_tracer_count_f64(nbody_ctx *ctx, int32_t *n);
+typedef struct nbody_hermite_block_tracer_stats {
+  uint32_t struct_size;        /* caller sets sizeof(nbody_hermite_block_tracer_stats) before the call */
+  int32_t carried;             /* tracers the session carries (0: a session without tracers) */
+  int64_t tracer_steps;        /* sum over block steps of m_t, the active tracers */
+  int64_t pairs;               /* sum of m_t * n_total */
+  int64_t tracer_only_steps;   /* block steps in which no BODY was due */
+  int64_t floor_hits;          /* tracers clamped to the deepest level, begin's included */
+  int32_t level_min, level_max;   /* over the tracers, now (0, 0 when carried == 0) */
+} nbody_hermite_block_tracer_stats;   /* 48 bytes */
+NBODY_AMD_API int nbody_hermite_block_begin_tracers(nbody_ctx *ctx, double dt_max, int32_t levels, double eta, double eta_start,
+                                                    const int32_t *level_in, const int32_t *tracer_level_in);
+NBODY_AMD_API int nbody_hermite6_block_begin_tracers(nbody_ctx *ctx, double dt_max, int32_t levels, double eta, double eta_start,
+                                                     const int32_t *level_in, const int32_t *tracer_level_in);
+NBODY_AMD_API int nbody_hermite_block_tracers_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level, nbody_hermite_block_tracer_stats *stats);
+NBODY_AMD_API int nbody_hermite6_block_tracers_get(nbody_ctx *ctx, int64_t *ticks, int32_t *level, nbody_hermite_block_tracer_stats *stats);
 NBODY_AMD_API int nbody_hermite_tracers_get(nbody_ctx *ctx, double *d12, size_t stride);
 NBODY_AMD_API int nbody_hermite6_tracers_get(nbody_ctx *ctx, double *d18, size_t stride);
 NBODY_AMD_API int nbody_hermite_tracers_timescale(nbody_ctx *ctx, double *t_min, int32_t *tracer, int32_t *kind);

@@ -97,6 +97,20 @@ class HermiteBlockStats(ctypes.Structure):
     ]
 
 
+class HermiteBlockTracerStats(ctypes.Structure):
+    """struct nbody_hermite_block_tracer_stats (include/nbody.h): the tracers' totals of a block session that carries them."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("carried", ctypes.c_int32),
+        ("tracer_steps", ctypes.c_int64),
+        ("pairs", ctypes.c_int64),
+        ("tracer_only_steps", ctypes.c_int64),
+        ("floor_hits", ctypes.c_int64),
+        ("level_min", ctypes.c_int32),
+        ("level_max", ctypes.c_int32),
+    ]
+
+
 MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
 
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
@@ -199,6 +213,10 @@ def lib():
     sig("nbody_hermite6_tracers_get", c_int, vp, vp, sz)
     sig("nbody_hermite_tracers_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
     sig("nbody_hermite6_tracers_timescale", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
+    sig("nbody_hermite_block_begin_tracers", c_int, vp, c_d, c_i32, c_d, c_d, vp, vp)
+    sig("nbody_hermite6_block_begin_tracers", c_int, vp, c_d, c_i32, c_d, c_d, vp, vp)
+    sig("nbody_hermite_block_tracers_get", c_int, vp, vp, vp, ctypes.POINTER(HermiteBlockTracerStats))
+    sig("nbody_hermite6_block_tracers_get", c_int, vp, vp, vp, ctypes.POINTER(HermiteBlockTracerStats))
     sig("nbody_set_tracers", c_int, vp, fp, fp, c_i32)
     sig("nbody_get_tracers", c_int, vp, fp, fp, fp)
     sig("nbody_tracer_count", c_int, vp, ctypes.POINTER(c_i32))

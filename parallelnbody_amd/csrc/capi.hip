@@ -623,7 +623,7 @@ void nbody_destroy(nbody_ctx *c) {
   for (void *q : {c->tr_pos, c->tr_vel, c->tr_acc, c->probe_part, c->probe_dev, c->pot64, c->tidal64, c->jerk64, c->snap64, c->tr64})
     if (q) (void)hipFree(q);
   for (int o = 0; o < 2; ++o)
-    for (void *q : {c->hm[o].buf, c->trh[o].buf, c->hb[o].buf})
+    for (void *q : {c->hm[o].buf, c->trh[o].buf, c->hb[o].buf, c->hb[o].tbuf})
       if (q) (void)hipFree(q);
   if (c->probe_host) (void)hipHostFree(c->probe_host);
   if (c->scratch) (void)hipFree(c->scratch);

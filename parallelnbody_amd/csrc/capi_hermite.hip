@@ -161,8 +161,16 @@ struct Order4 {
   static constexpr auto predict = nbody::launch_hermite_predict, correct = nbody::launch_hermite_correct;
   static constexpr auto block_init = nbody::launch_hermite_block_init;
   static constexpr auto block_schedule = nbody::launch_hermite_block_schedule;
+  static constexpr auto block_schedule_joint = nbody::launch_hermite_block_schedule_joint;
   static constexpr auto block_evaluate = nbody::launch_hermite_block_evaluate;
   static constexpr auto block_correct = nbody::launch_hermite_block_correct;
+  // the rows of the listed tracers P.list[first .. first + m) at the bodies' predicted (xp, vp)
+  static hipError_t block_evaluate_points(nbody_ctx *c, const BlockLaunch &B, const BlockLaunch &P, int first, int m, int lanes) {
+    nbody::Points64Launch L;
+    L.posm = B.xp; L.vel = B.vp; L.ppos = P.xp; L.pvel = P.vp; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
+    L.n_total = B.n; L.m = m; L.lanes = lanes; L.G = B.G; L.eps2 = B.eps2;
+    return nbody::launch_jerk_points_list_f64(L, P.list + first, c->stream);
+  }
 
   // Aarseth's criterion with a step's a2, a3, |j|^2 / |a|^2 without: k is the inverse square of a time either way, and a step is
   // dt = sqrt(eta) t (at a start: eta_start t)
@@ -232,8 +240,17 @@ struct Order6 {
   static constexpr auto predict = nbody::launch_hermite6_predict, correct = nbody::launch_hermite6_correct;
   static constexpr auto block_init = nbody::launch_hermite6_block_init;
   static constexpr auto block_schedule = nbody::launch_hermite6_block_schedule;
+  static constexpr auto block_schedule_joint = nbody::launch_hermite6_block_schedule_joint;
   static constexpr auto block_evaluate = nbody::launch_hermite6_block_evaluate;
   static constexpr auto block_correct = nbody::launch_hermite6_block_correct;
+  // the rows of the listed tracers P.list[first .. first + m) at the bodies' predicted (xp, vp, ap), each with its own predicted ap
+  static hipError_t block_evaluate_points(nbody_ctx *c, const BlockLaunch &B, const BlockLaunch &P, int first, int m, int lanes) {
+    nbody::Points64Launch L;
+    L.posm = B.xp; L.vel = B.vp; L.ain = (const double *)B.ap; L.ain_stride = 4; L.ppos = P.xp; L.pvel = P.vp;
+    L.pain = (const double *)P.ap; L.pain_stride = 4; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
+    L.n_total = B.n; L.m = m; L.lanes = lanes; L.G = B.G; L.eps2 = B.eps2;
+    return nbody::launch_snap_points_list_f64(L, P.list + first, c->stream);
+  }
 
   // (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2) with a step's derivatives — the inverse SIXTH power of a time —, |j|^2 / |a|^2
   // without; a step is dt = eta t (eta times t itself: no square root in this criterion; at a start: eta_start t)
@@ -255,19 +272,19 @@ struct Order6 {
 // own and nothing but that session's block_advance can move them on; at a frame end the stored state is synchronised, the cache is every
 // body's, and the session simply ends.
 template <class O>
-int block_leave(nbody_ctx *c, const char *who) {
+int block_leave(nbody_ctx *c, const char *who, bool end = true) {
   HermiteBlockSession &s = c->hb[O::index];
   if (!s.active) return NBODY_OK;
   if (s.ticks & ((1ll << s.levels) - 1))
     return fail(c, NBODY_ERR_STATE, "%s: a %sHermite block session is in mid-frame (tick %lld of frames of %lld): the bodies are at times of "
                 "their own; %s_block_advance(ctx, 1, ...) finishes the frame, nbody_hermite_restart abandons the session", who, O::kOrdinal,
                 (long long)s.ticks, 1ll << s.levels, O::kPrefix);
-  s.active = false;
+  if (end) s.active = false;
   return NBODY_OK;
 }
-int block_leave_both(nbody_ctx *c, const char *who) {
-  if (int rc = block_leave<Order4>(c, who)) return rc;
-  return block_leave<Order6>(c, who);
+int block_leave_both(nbody_ctx *c, const char *who, bool end = true) {
+  if (int rc = block_leave<Order4>(c, who, end)) return rc;
+  return block_leave<Order6>(c, who, end);
 }
 
 // what every call does at entry: the cache and the partial rows at first use; once somebody else may write the state, nothing cached is
@@ -480,70 +497,126 @@ size_t block_bytes(int n) {
   return ((size_t)n + slots + 3) * 8 + (2 * (size_t)n + slots) * 4;
 }
 
+// A session that carries tracers keeps a second set of the scheduler's arrays for them (HermiteBlockSession::tbuf): the joint record in
+// front — the bodies' (T_next, m), then the tracers' —, the tracers' BlockBufs behind it.
+constexpr size_t kJointRecordBytes = 32;
+long long *joint_record(const HermiteBlockSession &s) { return (long long *)s.tbuf; }
+BlockBufs tracer_bufs(const HermiteBlockSession &s) { return block_bufs((char *)s.tbuf + kJointRecordBytes, (size_t)s.carried); }
+
+template <class O>
+typename O::BlockLaunch block_launch_on(nbody_ctx *c, const CacheView &v, const BlockBufs &q, long long *record) {
+  const HermiteBlockSession &s = c->hb[O::index];
+  typename O::BlockLaunch L = O::block_launch(v, s.eta);
+  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = record;
+  L.floor_hits = q.floor_hits; L.n = v.count; L.n_field = c->p.n_total; L.levels = s.levels; L.tick = s.tick; L.dt_max = s.dt_max;
+  L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+  return L;
+}
 template <class O>
 typename O::BlockLaunch block_launch(nbody_ctx *c) {
   const HermiteBlockSession &s = c->hb[O::index];
   const BlockBufs q = block_bufs(s.buf, (size_t)c->p.n_total);
-  typename O::BlockLaunch L = O::block_launch(body_view<O>(c), s.eta);
-  L.part = c->probe_part; L.T = q.T; L.level = q.level; L.list = q.list; L.seg_min = q.seg_min; L.seg_cnt = q.seg_cnt; L.record = q.record;
-  L.floor_hits = q.floor_hits; L.n = c->p.n_total; L.levels = s.levels; L.tick = s.tick; L.dt_max = s.dt_max; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-  return L;
+  return block_launch_on<O>(c, body_view<O>(c), q, s.carried > 0 ? joint_record(s) : q.record);
+}
+// the same kernels on the tracers' arrays: their own T, levels, list and floor hits; the partial rows' chunks stay the bodies'
+template <class O>
+typename O::BlockLaunch tracer_block_launch(nbody_ctx *c) {
+  const HermiteBlockSession &s = c->hb[O::index];
+  return block_launch_on<O>(c, tracer_view<O>(c), tracer_bufs(s), joint_record(s) + 2);
 }
 
 // the totals since begin; the levels' range and the floor hits are read from the device (4 n + 8 bytes): waits for the stream
-int block_fill(nbody_ctx *c, const HermiteBlockSession &s, nbody_hermite_block_stats *out) {
-  const size_t n = (size_t)c->p.n_total;
-  const BlockBufs q = block_bufs(s.buf, n);
+int block_read_levels(nbody_ctx *c, const BlockBufs &q, size_t n, int64_t *floor_hits, int32_t *level_min, int32_t *level_max) {
   if (int rc = ensure_stage(c, n * 4 + 8)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.floor_hits, 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + 8, q.level, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int64_t floor_hits;
-  memcpy(&floor_hits, c->h_stage, 8);
+  memcpy(floor_hits, c->h_stage, 8);
   const int32_t *lv = (const int32_t *)((const char *)c->h_stage + 8);
+  *level_min = *std::min_element(lv, lv + n); *level_max = *std::max_element(lv, lv + n);
+  return NBODY_OK;
+}
+int block_fill(nbody_ctx *c, const HermiteBlockSession &s, nbody_hermite_block_stats *out) {
   out->synchronised = (s.ticks & ((1ll << s.levels) - 1)) == 0 ? 1 : 0;
   out->ticks = s.ticks; out->frames_done = s.ticks >> s.levels; out->block_steps = s.block_steps;
-  out->body_steps = s.body_steps; out->pairs = s.pairs; out->floor_hits = floor_hits;
-  out->level_min = *std::min_element(lv, lv + n); out->level_max = *std::max_element(lv, lv + n);
-  return NBODY_OK;
+  out->body_steps = s.body_steps; out->pairs = s.pairs;
+  const size_t n = (size_t)c->p.n_total;
+  return block_read_levels(c, block_bufs(s.buf, n), n, &out->floor_hits, &out->level_min, &out->level_max);
+}
+// the tracers' totals since begin (the bodies' stay in nbody_hermite_block_stats, untouched by the tracers)
+int block_fill_tracers(nbody_ctx *c, const HermiteBlockSession &s, nbody_hermite_block_tracer_stats *out) {
+  out->carried = s.carried; out->tracer_steps = s.tracer_steps; out->pairs = s.tracer_pairs; out->tracer_only_steps = s.tracer_only_steps;
+  out->floor_hits = 0; out->level_min = out->level_max = 0;
+  if (s.carried == 0) return NBODY_OK;
+  return block_read_levels(c, tracer_bufs(s), (size_t)s.carried, &out->floor_hits, &out->level_min, &out->level_max);
 }
 
 // one block step, from the schedule to the stored bodies; the host waits once, for (T_next, m), to size the evaluation.  An active set
 // larger than a slab of partial rows goes through evaluation and corrector slab by slab: the predicted state is in buffers of its own, so
 // a corrected slab changes nothing a later slab's evaluation reads.
+// A session that carries tracers schedules both sets jointly — T_next over bodies AND tracers, a list each, everything predicted — and
+// reads (T_next, m_b, T_next, m_t).  The due bodies are evaluated and corrected as ever; then the due tracers, at the bodies' PREDICTED
+// state (the corrector wrote the stored one), through the same staging area on the same stream.  Either set may be empty, not both.
 template <class O>
 int block_one_step(nbody_ctx *c, const char *who) {
   HermiteBlockSession &s = c->hb[O::index];
-  const typename O::BlockLaunch L = block_launch<O>(c);
+  const bool carrying = s.carried > 0;
+  const typename O::BlockLaunch L = block_launch<O>(c), P = carrying ? tracer_block_launch<O>(c) : typename O::BlockLaunch{};
+  const int n = c->p.n_total;
+  const size_t slab = nbody::probe_slab_points(n, O::kPartWidth);
   int rc;
-  if ((rc = O::block_parts_hold(c))) return rc;
-  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, O::block_schedule(L, c->stream)); return NBODY_OK; }, false))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, 16, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = O::block_parts_hold(c))) return rc;                    // (the partial rows of reserve_parts(n), and of reserve_parts(carried))
+  if (carrying && (rc = points64_part_holds(c, (int)std::min(slab, (size_t)s.carried), O::kPartWidth, "the tracers' pass of a block step"))) return rc;
+  if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int {
+        HIP_TRY(c, carrying ? O::block_schedule_joint(L, P, c->stream) : O::block_schedule(L, c->stream));
+        return NBODY_OK;
+      }, false))) return rc;
+  const size_t rec_bytes = carrying ? kJointRecordBytes : 16;
+  HIP_TRY(c, hipMemcpyAsync(c->h_scratch, L.record, rec_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  long long rec[2];
-  memcpy(rec, c->h_scratch, 16);
+  long long rec[4] = {0, 0, 0, 0};
+  memcpy(rec, c->h_scratch, rec_bytes);
   const long long t_next = rec[0];
-  const int n = c->p.n_total, m = (int)rec[1];
-  if (rec[1] < 1 || rec[1] > n || t_next <= s.ticks)
-    return fail(c, NBODY_ERR_STATE, "%s: the schedule gave T_next = %lld, m = %lld at tick %lld", who, t_next, rec[1], (long long)s.ticks);
-  const int lanes = nbody::hermite_block_lanes(m, s.lanes);
-  const int slab = (int)std::min<size_t>(nbody::probe_slab_points(n, O::kPartWidth), (size_t)n);   // (the partial rows of reserve_parts(n))
-  for (int first = 0; first < m; first += slab) {
-    const int ms = std::min(slab, m - first);
-    const bool last = first + ms == m;
-    if ((rc = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int { HIP_TRY(c, O::block_evaluate(L, first, ms, lanes, c->stream)); return NBODY_OK; }, last))) return rc;
-    if ((rc = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, O::block_correct(L, first, ms, t_next, c->stream)); return NBODY_OK; }, last))) return rc;
-  }
+  if (rec[1] < 0 || rec[1] > n || rec[3] < 0 || rec[3] > s.carried || rec[1] + rec[3] < 1 || t_next <= s.ticks || (carrying && rec[2] != t_next))
+    return fail(c, NBODY_ERR_STATE, "%s: the schedule gave T_next = %lld, m = %lld (tracers: T_next = %lld, m = %lld) at tick %lld", who,
+                t_next, rec[1], rec[2], rec[3], (long long)s.ticks);
+  const int m_b = (int)rec[1], m_t = (int)rec[3];
+  // the due rows of one set — the bodies (X = L) or the tracers (X = P) —: evaluation and corrector, slab by slab
+  const auto pass = [&](const typename O::BlockLaunch &X, int m, bool points, bool last_set) -> int {
+    const int lanes = nbody::hermite_block_lanes(m, s.lanes);
+    const int rows = (int)std::min(slab, (size_t)X.n);
+    for (int first = 0; first < m; first += rows) {
+      const int ms = std::min(rows, m - first);
+      const bool last = first + ms == m;
+      if (int e = timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+            HIP_TRY(c, points ? O::block_evaluate_points(c, L, X, first, ms, lanes) : O::block_evaluate(X, first, ms, lanes, c->stream));
+            return NBODY_OK;
+          }, last)) return e;
+      if (int e = timed_launch(c, NBODY_KERNEL_UPDATE, [&]() -> int { HIP_TRY(c, O::block_correct(X, first, ms, t_next, c->stream)); return NBODY_OK; },
+                               last && last_set)) return e;
+    }
+    return NBODY_OK;
+  };
+  if (m_b > 0 && (rc = pass(L, m_b, false, m_t == 0))) return rc;
+  if (m_t > 0 && (rc = pass(P, m_t, true, true))) return rc;
   s.ticks = t_next;
-  s.block_steps += 1; s.body_steps += m; s.pairs += (int64_t)m * n;
-  if (s.ticks >= (1ll << s.levels)) c->hm[O::index].derivs = true;   // a whole frame: every body has stepped, every higher derivative is a step's
+  s.block_steps += 1; s.body_steps += m_b; s.pairs += (int64_t)m_b * n;
+  s.tracer_steps += m_t; s.tracer_pairs += (int64_t)m_t * n; s.tracer_only_steps += m_b == 0 ? 1 : 0;
+  if (s.ticks >= (1ll << s.levels)) {                              // a whole frame: every body has stepped, every higher derivative is a step's
+    c->hm[O::index].derivs = true;
+    if (carrying) c->trh[O::index].derivs = true;
+  }
   c->sym_posg_valid = false;
   c->steps_done += 1;
   return NBODY_OK;
 }
 
+// carry == false: the plain begin, which refuses a context with fp64 tracers.  carry == true (the order's block_begin_tracers): the same
+// begin, and on a context with tracers a session that carries them — their cache filled where it is invalid, T := 0, their levels from
+// tracer_level_in or from the start rule on their own (a0, j0), by the bodies' init kernel on the tracers' arrays.
 template <class O>
-int block_begin(nbody_ctx *c, const char *who, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
+int block_begin(nbody_ctx *c, const char *who, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in,
+                bool carry, const int32_t *tracer_level_in) {
   int rc = hermite_ready(c, who);
   if (rc) return rc;
   const auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
@@ -551,29 +624,52 @@ int block_begin(nbody_ctx *c, const char *who, double dt_max, int32_t levels, do
     return fail(c, NBODY_ERR_INVALID, "%s: dt_max, eta and eta_start must be finite and > 0, levels 0 .. %d", who, nbody::kHermiteBlockMaxLevels);
   const double tick = std::ldexp(dt_max, -levels);
   if (const char *why = O::tick_refused(tick)) return fail(c, NBODY_ERR_INVALID, "%s: the tick dt_max 2^-levels = %g %s", who, tick, why);
-  if (c->tr64_n > 0)
+  if (!carry && c->tr64_n > 0) {
+    if ((rc = block_leave_both(c, who, false))) return rc;         // (a carrying session in mid-frame: that first; the check ends nothing)
     return fail(c, NBODY_ERR_UNSUPPORTED, "%s: the context holds %d fp64 tracers, which the block scheduler does not "
-                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them", who, c->tr64_n);
-  const int n = c->p.n_total;
+                "carry (they have no levels of their own); nbody_set_tracers_f64(ctx, NULL, 0, NULL, 0, 0) removes them "
+                "(%s_block_begin_tracers starts a session that carries them)", who, c->tr64_n, O::kPrefix);
+  }
+  const int n = c->p.n_total, m = carry ? c->tr64_n : 0;
   if (level_in)
     for (int i = 0; i < n; ++i)
       if (level_in[i] < 0 || level_in[i] > levels)
         return fail(c, NBODY_ERR_INVALID, "%s: level_in[%d] = %d is outside 0 .. %d", who, i, (int)level_in[i], (int)levels);
+  if (tracer_level_in && m == 0) return fail(c, NBODY_ERR_INVALID, "%s: tracer_level_in is not NULL, and the context holds no fp64 tracers", who);
+  if (tracer_level_in)
+    for (int i = 0; i < m; ++i)
+      if (tracer_level_in[i] < 0 || tracer_level_in[i] > levels)
+        return fail(c, NBODY_ERR_INVALID, "%s: tracer_level_in[%d] = %d is outside 0 .. %d", who, i, (int)tracer_level_in[i], (int)levels);
   if ((rc = block_leave_both(c, who))) return rc;
   if ((rc = enter<O>(c))) return rc;
+  if (m > 0 && (rc = tracers_enter<O>(c))) return rc;
   hermite_invalidate_order(c, O::index ^ 1);                       // (the state moves on without the other order's cache)
   HermiteBlockSession &s = c->hb[O::index];
   if (!s.buf) HIP_TRY(c, hipMalloc(&s.buf, block_bytes(n)));
+  if (m > 0 && s.tbuf_n != m) {
+    if (s.tbuf) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(s.tbuf); s.tbuf = nullptr; s.tbuf_n = 0; }
+    HIP_TRY(c, hipMalloc(&s.tbuf, kJointRecordBytes + block_bytes(m)));
+    s.tbuf_n = m;
+  }
   s.levels = levels; s.dt_max = dt_max; s.tick = tick; s.eta = eta;
   s.lanes = nbody::env_int(O::kLanesEnv, 0);
   s.ticks = s.block_steps = s.body_steps = s.pairs = 0;
+  s.carried = m; s.tracer_steps = s.tracer_pairs = s.tracer_only_steps = 0;
   const typename O::BlockLaunch L = block_launch<O>(c);
   // the higher derivatives lie side by side, 64 / 96 bytes per body: zeros until a body steps
   if (!c->hm[O::index].derivs) HIP_TRY(c, hipMemsetAsync(body_view<O>(c).d, 0, (size_t)n * O::kDerivs * 32, c->stream));
-  HIP_TRY(c, hipMemsetAsync(L.record, 0, 24, c->stream));          // the record and the floor hits
+  HIP_TRY(c, hipMemsetAsync(block_bufs(s.buf, (size_t)n).record, 0, 24, c->stream));   // the record and the floor hits
   if (level_in) HIP_TRY(c, hipMemcpyAsync(L.list, level_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, O::block_init(L, level_in ? L.list : nullptr, eta_start, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's array is its own again
+  if (m > 0) {
+    const typename O::BlockLaunch P = tracer_block_launch<O>(c);
+    if (!c->trh[O::index].derivs) HIP_TRY(c, hipMemsetAsync(tracer_view<O>(c).d, 0, (size_t)m * O::kDerivs * 32, c->stream));
+    HIP_TRY(c, hipMemsetAsync(joint_record(s), 0, kJointRecordBytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(tracer_bufs(s).record, 0, 24, c->stream));
+    if (tracer_level_in) HIP_TRY(c, hipMemcpyAsync(P.list, tracer_level_in, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, O::block_init(P, tracer_level_in ? P.list : nullptr, eta_start, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // the caller's arrays are its own again
   s.active = true;
   return NBODY_OK;
 }
@@ -611,6 +707,31 @@ int block_get(nbody_ctx *c, const char *who, int64_t *ticks, int32_t *level) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (ticks) memcpy(ticks, c->h_stage, n * 8);
   if (level) memcpy(level, (const char *)c->h_stage + n * 8, n * 4);
+  return NBODY_OK;
+}
+
+// T_i and k_i of the tracers a session carries, and their totals since begin
+template <class O>
+int block_tracers_get(nbody_ctx *c, const char *who, int64_t *ticks, int32_t *level, nbody_hermite_block_tracer_stats *stats) {
+  int rc = hermite_ready(c, who);
+  if (rc) return rc;
+  if ((!ticks && !level && !stats) || (stats && stats->struct_size != sizeof(nbody_hermite_block_tracer_stats)))
+    return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null, or stats->struct_size is not "
+                "sizeof(nbody_hermite_block_tracer_stats) = %d", who, (int)sizeof(nbody_hermite_block_tracer_stats));
+  const HermiteBlockSession &s = c->hb[O::index];
+  if (!s.active) return fail(c, NBODY_ERR_STATE, "%s: no %sblock session (%s_block_begin_tracers first)", who, O::kOrdinal, O::kPrefix);
+  const size_t m = (size_t)s.carried;
+  if (m > 0 && (ticks || level)) {
+    const BlockBufs q = tracer_bufs(s);
+    if ((rc = ensure_stage(c, m * 12))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_stage, q.T, m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + m * 8, q.level, m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ticks) memcpy(ticks, c->h_stage, m * 8);
+    if (level) memcpy(level, (const char *)c->h_stage + m * 8, m * 4);
+  }
+  if (stats) return block_fill_tracers(c, s, stats);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return NBODY_OK;
 }
 
@@ -667,6 +788,7 @@ int tracers_timescale(nbody_ctx *c, const char *who, double *t_min, int32_t *tra
   if (rc) return rc;
   if (!t_min && !tracer && !kind) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
   if (c->tr64_n <= 0) return fail(c, NBODY_ERR_STATE, "%s: the context holds no fp64 tracers (nbody_set_tracers_f64 first)", who);
+  if ((rc = block_leave_both(c, who))) return rc;                  // (a session that carries them: the rule of the bodies' timescale)
   if constexpr (O::kTracerStartReadsCache) { if ((rc = enter<O>(c))) return rc; }
   else if (c->hm_external) hermite_invalidate(c);                  // (the rule enter applies, where the bodies' cache is not needed)
   if ((rc = tracers_enter<O>(c))) return rc;
@@ -722,10 +844,24 @@ int nbody_hermite6_block_level(double k, double dt_max, int32_t levels, double e
 }
 
 int nbody_hermite_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
-  return block_begin<Order4>(c, "nbody_hermite_block_begin", dt_max, levels, eta, eta_start, level_in);
+  return block_begin<Order4>(c, "nbody_hermite_block_begin", dt_max, levels, eta, eta_start, level_in, false, nullptr);
 }
 int nbody_hermite6_block_begin(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in) {
-  return block_begin<Order6>(c, "nbody_hermite6_block_begin", dt_max, levels, eta, eta_start, level_in);
+  return block_begin<Order6>(c, "nbody_hermite6_block_begin", dt_max, levels, eta, eta_start, level_in, false, nullptr);
+}
+int nbody_hermite_block_begin_tracers(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in,
+                                      const int32_t *tracer_level_in) {
+  return block_begin<Order4>(c, "nbody_hermite_block_begin_tracers", dt_max, levels, eta, eta_start, level_in, true, tracer_level_in);
+}
+int nbody_hermite6_block_begin_tracers(nbody_ctx *c, double dt_max, int32_t levels, double eta, double eta_start, const int32_t *level_in,
+                                       const int32_t *tracer_level_in) {
+  return block_begin<Order6>(c, "nbody_hermite6_block_begin_tracers", dt_max, levels, eta, eta_start, level_in, true, tracer_level_in);
+}
+int nbody_hermite_block_tracers_get(nbody_ctx *c, int64_t *ticks, int32_t *level, nbody_hermite_block_tracer_stats *stats) {
+  return block_tracers_get<Order4>(c, "nbody_hermite_block_tracers_get", ticks, level, stats);
+}
+int nbody_hermite6_block_tracers_get(nbody_ctx *c, int64_t *ticks, int32_t *level, nbody_hermite_block_tracer_stats *stats) {
+  return block_tracers_get<Order6>(c, "nbody_hermite6_block_tracers_get", ticks, level, stats);
 }
 
 int nbody_hermite_block_advance(nbody_ctx *c, int64_t frames, int64_t max_block_steps, nbody_hermite_block_stats *out) {
@@ -810,8 +946,11 @@ int nbody_set_tracers_f64(nbody_ctx *c, const double *pos, size_t pos_stride, co
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!pos || pos_stride < 24 || (vel && vel_stride < 24))))
     return fail(c, NBODY_ERR_INVALID, "%s: n < 0, null positions, or a stride < 24", who);
+  for (const HermiteBlockSession &s : c->hb)                       // (n == 0 too: the session's lists index the tracers it began with)
+    if (s.active && s.carried > 0)
+      return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session carries the %d fp64 tracers; nbody_hermite_restart ends the session", who, s.carried);
   if (n > 0 && (c->hb[0].active || c->hb[1].active))
-    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is active, and the block scheduler carries no tracers; nbody_hermite_restart "
+    return fail(c, NBODY_ERR_STATE, "%s: a Hermite block session is active, and it began without tracers (nbody_hermite[6]_block_begin_tracers carries those a context holds at begin); nbody_hermite_restart "
                 "ends the session", who);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->tr64) (void)hipFree(c->tr64);

@@ -54,6 +54,12 @@ struct HermiteBlockSession {
   int levels = 0, lanes = 0;   // lanes: bodies per lane of the evaluation forced by NBODY_HERMITE_BLOCK_LANES / NBODY_HERMITE6_BLOCK_LANES (0: by the list's length)
   double dt_max = 0.0, tick = 0.0, eta = 0.0;
   int64_t ticks = 0, block_steps = 0, body_steps = 0, pairs = 0;   // T_sys and the totals since begin
+  // A session that carries the fp64 tracers (the order's block_begin_tracers): tbuf, allocated for tbuf_n tracers, holds the joint record
+  // — (T_next, m) of the bodies, then of the tracers: the 32 bytes the host reads per block step — and behind it the tracers' T, segment
+  // minima, record (unused), floor-hit count, level, list and segment counts in the layout of buf.
+  void *tbuf = nullptr;
+  int tbuf_n = 0, carried = 0;   // carried: the tracers this session carries (0: none; the plain begins' sessions)
+  int64_t tracer_steps = 0, tracer_pairs = 0, tracer_only_steps = 0;
 };
 
 }  // namespace nbody

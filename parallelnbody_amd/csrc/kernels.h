@@ -210,6 +210,7 @@ struct HermiteBlockLaunch {
   long long *record = nullptr;                            // [2]: T_next, m
   unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
   int n = 0, levels = 0;
+  int n_field = 0;   // the tracers' arrays: the bodies whose chunks (probe_geometry) the partial rows follow; 0: n
   double tick = 0.0, dt_max = 0.0, root_eta = 0.0, G = 0.0, eps2 = 0.0;
 };
 constexpr int kHermiteBlockOneLaneMax = 1024;   // listed bodies up to which the evaluation holds one body per lane (more workgroups)
@@ -219,6 +220,9 @@ hipError_t launch_hermite_block_init(const HermiteBlockLaunch &L, const int *lev
 hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_t s);
 hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first, int m, int lanes, hipStream_t s);
 hipError_t launch_hermite_block_correct(const HermiteBlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
+// the schedule of a session that carries fp64 tracers — B the bodies' arrays, P the tracers' —: T_next is the smallest due time of
+// BOTH sets; each set gets its own record (T_next, m: 0 and an empty list where nobody is due) and every row of both is predicted
+hipError_t launch_hermite_block_schedule_joint(const HermiteBlockLaunch &B, const HermiteBlockLaunch &P, hipStream_t s);
 // the schedule's first kernel alone — seg_min[q], seg_cnt[q] of every segment q: the smallest T[i] + step_i and how many bodies attain it —,
 // which the sixth-order session queues ahead of a list kernel of its own (integers only: it reads no cache)
 hipError_t launch_hermite_block_next(const long long *T, const int *level, int n, int levels, long long *seg_min, int *seg_cnt, hipStream_t s);
@@ -284,12 +288,16 @@ struct Hermite6BlockLaunch {
   long long *record = nullptr;                            // [2]: T_next, m
   unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
   int n = 0, levels = 0;
+  int n_field = 0;   // as HermiteBlockLaunch's
   double tick = 0.0, dt_max = 0.0, eta = 0.0, G = 0.0, eps2 = 0.0;
 };
 hipError_t launch_hermite6_block_init(const Hermite6BlockLaunch &L, const int *level_in, double eta_start, hipStream_t s);
 hipError_t launch_hermite6_block_schedule(const Hermite6BlockLaunch &L, hipStream_t s);
 hipError_t launch_hermite6_block_evaluate(const Hermite6BlockLaunch &L, int first, int m, int lanes, hipStream_t s);
 hipError_t launch_hermite6_block_correct(const Hermite6BlockLaunch &L, int first, int m, long long t_next, hipStream_t s);
+// the schedule of a session that carries fp64 tracers — B the bodies' arrays, P the tracers' —: T_next is the smallest due time of
+// BOTH sets; each set gets its own record (T_next, m: 0 and an empty list where nobody is due) and every row of both is predicted
+hipError_t launch_hermite6_block_schedule_joint(const Hermite6BlockLaunch &B, const Hermite6BlockLaunch &P, hipStream_t s);
 
 // The fp64 jerk and snap passes at m points that are not bodies — kernels_points64.hip: launch_jerk's / launch_snap's pair sums on fp64
 // state with the i side taken from (ppos, pvel[, pain]) instead of from the bodies, over the same chunks and tiles in the same order,
@@ -315,6 +323,11 @@ struct Points64Launch {
 };
 hipError_t launch_jerk_points_f64(const Points64Launch &L, hipStream_t s);
 hipError_t launch_snap_points_f64(const Points64Launch &L, hipStream_t s);
+// The list forms, for a block step's active tracers: point k < m is row list[k] of (ppos, pvel[, pain]); ONE slab (m <=
+// probe_slab_points(n_total, 3 / kSnapRowWidth)) into part[(c * m + k) * 6 / 9], left unfolded for the block corrector; `out` is not
+// used, lanes is 1 or 2.
+hipError_t launch_jerk_points_list_f64(const Points64Launch &L, const int *list, hipStream_t s);
+hipError_t launch_snap_points_list_f64(const Points64Launch &L, const int *list, hipStream_t s);
 // jerk_fold_f64_kernel / snap_fold_f64_kernel on their own: out[k][0 .. 6) / [0 .. 9) = the rows part[(c * m + k) * 6 / 9] added from 0.0
 // in chunk order
 hipError_t launch_jerk_fold_f64(const void *part, int m, int j_split, double *aj64, hipStream_t s);

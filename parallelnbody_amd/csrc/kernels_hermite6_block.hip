@@ -11,6 +11,8 @@
 //   hermite6_block_correct_kernel  <- the listed bodies: the chunks' rows added in chunk order (snap_fold_f64_kernel's sums), the corrector
 //                                     of kernels_snap.hip with the body's own dt, T[i] := T_next, the new level (hermite_block_level.h)
 //   hermite6_block_init_kernel     <- T := 0 and the first levels, given or from eta_start |a0| / |j0|
+// A session that carries fp64 tracers (nbody_hermite6_block_begin_tracers) runs the same kernels on the tracers' arrays as a second
+// set; hermite6_block_list_kernel<true> then takes T_next over both sets, and the tracers' rows come from snap_points_f64_kernel<., ., true>.
 // EVERY operation outside the pair sums is one correctly rounded fp64 operation in the order written: contraction is off for the whole
 // file, so that numpy (tests/hermite6_block_ref.py) reproduces a block step in every bit.  No scratch, no grid-wide waits; the one atomic
 // is an integer count of floor hits.
@@ -37,6 +39,9 @@ __device__ __forceinline__ Ajs load_ajs(const double *__restrict__ ajs, int i) {
 // c2 = d2 0.5, c3 = (d2 dt) / 6, c4 = (d2 d2) / 24, c5 = ((d2 d2) dt) / 120:
 //   xp = ((((x + dt v) + c2 a0) + c3 j0) + c4 s0) + c5 a3;  vp = (((v + dt a0) + c2 j0) + c3 s0) + c4 a3;  ap = ((a0 + dt j0) + c2 s0) + c3 a3
 // xp.w = m, vp.w = 0, ap.w = 0
+// JOINT: T_next is the smallest due time of BOTH sets of a session that carries tracers — this set's segments and the other's
+// (other_min[0 .. other_slots)) —; a set with nobody due at T_next writes m = 0 and an empty list.  <false> is the kernel it was.
+template <bool JOINT>
 __global__ __launch_bounds__(kBlock) void hermite6_block_list_kernel(const long long *__restrict__ T, const int *__restrict__ level,
                                                                      const long long *__restrict__ seg_min, const int *__restrict__ seg_cnt,
                                                                      int slots, int n, int seg_len, int levels, double tick,
@@ -44,12 +49,15 @@ __global__ __launch_bounds__(kBlock) void hermite6_block_list_kernel(const long 
                                                                      const double *__restrict__ ajs0, const double4 *__restrict__ a3,
                                                                      double4 *__restrict__ xp, double4 *__restrict__ vp,
                                                                      double4 *__restrict__ ap, int *__restrict__ list,
-                                                                     long long *__restrict__ record) {
+                                                                     long long *__restrict__ record,
+                                                                     const long long *__restrict__ other_min, int other_slots) {
   __shared__ long long redl[kBlock / 64];
   __shared__ int redi[kBlock / 64], wave_cnt[kBlock / 64];
   const int t = threadIdx.x, s = blockIdx.x;
   long long tn = kNever;
   for (int q = t; q < slots; q += kBlock) tn = seg_min[q] < tn ? seg_min[q] : tn;
+  if (JOINT)
+    for (int q = t; q < other_slots; q += kBlock) tn = other_min[q] < tn ? other_min[q] : tn;
   tn = block_min_workgroup(tn, redl);
   int before = 0, total = 0;
   for (int q = t; q < slots; q += kBlock) {
@@ -215,10 +223,28 @@ hipError_t launch_hermite6_block_schedule(const Hermite6BlockLaunch &L, hipStrea
   int slots;
   const int seg_len = hermite_block_segment(L.n, &slots);
   if (hipError_t e = launch_hermite_block_next(L.T, L.level, L.n, L.levels, L.seg_min, L.seg_cnt, s)) return e;
-  hipLaunchKernelGGL(hermite6_block_list_kernel, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
+  hipLaunchKernelGGL(hermite6_block_list_kernel<false>, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
                      (const long long *)L.seg_min, (const int *)L.seg_cnt, slots, L.n, seg_len, L.levels, L.tick, (const double4 *)L.posm,
                      (const double4 *)L.vel, (const double *)L.ajs0, (const double4 *)L.a3, (double4 *)L.xp, (double4 *)L.vp,
-                     (double4 *)L.ap, L.list, L.record);
+                     (double4 *)L.ap, L.list, L.record, (const long long *)nullptr, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_hermite6_block_schedule_joint(const Hermite6BlockLaunch &B, const Hermite6BlockLaunch &P, hipStream_t s) {
+  if (bad(B) || !B.xp || !B.vp || !B.ap || bad(P) || !P.xp || !P.vp || !P.ap || B.levels != P.levels || B.tick != P.tick)
+    return hipErrorInvalidValue;
+  int slots[2];
+  const Hermite6BlockLaunch *set[2] = {&B, &P};
+  for (const Hermite6BlockLaunch *L : set)
+    if (hipError_t e = launch_hermite_block_next(L->T, L->level, L->n, L->levels, L->seg_min, L->seg_cnt, s)) return e;
+  const int seg_len[2] = {hermite_block_segment(B.n, &slots[0]), hermite_block_segment(P.n, &slots[1])};
+  for (int k = 0; k < 2; ++k) {
+    const Hermite6BlockLaunch &L = *set[k], &O = *set[k ^ 1];
+    hipLaunchKernelGGL(hermite6_block_list_kernel<true>, dim3(slots[k]), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
+                       (const long long *)L.seg_min, (const int *)L.seg_cnt, slots[k], L.n, seg_len[k], L.levels, L.tick,
+                       (const double4 *)L.posm, (const double4 *)L.vel, (const double *)L.ajs0, (const double4 *)L.a3, (double4 *)L.xp,
+                       (double4 *)L.vp, (double4 *)L.ap, L.list, L.record, (const long long *)O.seg_min, slots[k ^ 1]);
+  }
   return hipGetLastError();
 }
 
@@ -240,7 +266,7 @@ hipError_t launch_hermite6_block_evaluate(const Hermite6BlockLaunch &L, int firs
 hipError_t launch_hermite6_block_correct(const Hermite6BlockLaunch &L, int first, int m, long long t_next, hipStream_t s) {
   if (bad(L) || !L.acc || !L.a4 || !L.a5 || !L.part || first < 0 || m <= 0 || first + m > L.n) return hipErrorInvalidValue;
   int j_split, j_chunk;
-  probe_geometry(L.n, &j_split, &j_chunk);
+  probe_geometry(L.n_field > 0 ? L.n_field : L.n, &j_split, &j_chunk);   // (the rows' chunks are those of the bodies that exert the field)
   const Block6Rule r{L.tick, L.dt_max, L.eta, L.levels};
   hipLaunchKernelGGL(hermite6_block_correct_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const int *)L.list + first, m,
                      (const double *)L.part, j_split, t_next, r, L.T, L.level, (double4 *)L.posm, (double4 *)L.vel, (double4 *)L.acc, L.ajs0,

@@ -10,6 +10,8 @@
 //   hermite_block_correct_kernel  <- the listed bodies: the chunks' rows added in chunk order (jerk_fold_f64_kernel's sums), the corrector
 //                                    of kernels_hermite.hip with the body's own dt, T[i] := T_next, the new level (hermite_block_level.h)
 //   hermite_block_init_kernel     <- T := 0 and the first levels, given or from eta_start |a| / |j|
+// A session that carries fp64 tracers (nbody_hermite_block_begin_tracers) runs the same kernels on a second set of arrays, the tracers';
+// hermite_block_list_kernel<true> then takes T_next over both sets, and the tracers' rows come from jerk_points_f64_kernel<., ., true>.
 // EVERY operation outside the pair sums is one correctly rounded fp64 operation in the order written: contraction is off for the whole
 // file, so that numpy (tests/hermite_block_ref.py) reproduces a block step in every bit.
 #include "jerk_tile64.h"
@@ -53,18 +55,24 @@ __device__ __forceinline__ Aj load_aj(const double *__restrict__ aj, int i) {
 
 // record[0] = T_next, record[1] = m; list[0 .. m) ascending; per body and component, with dt = (double)(T_next - T[i]) tick,
 // c2 = (dt dt) 0.5 and c3 = ((dt dt) dt) / 6:  xp = ((x + dt v) + c2 a0) + c3 j0;  vp = (v + dt a0) + c2 j0;  xp.w = m, vp.w = 0
+// JOINT: T_next is the smallest due time of BOTH sets of a session that carries tracers — this set's segments and the other's
+// (other_min[0 .. other_slots)) —; a set with nobody due at T_next writes m = 0 and an empty list.  <false> is the kernel it was.
+template <bool JOINT>
 __global__ __launch_bounds__(kBlock) void hermite_block_list_kernel(const long long *__restrict__ T, const int *__restrict__ level,
                                                                     const long long *__restrict__ seg_min, const int *__restrict__ seg_cnt,
                                                                     int slots, int n, int seg_len, int levels, double tick,
                                                                     const double4 *__restrict__ posm, const double4 *__restrict__ vel,
                                                                     const double *__restrict__ aj0, double4 *__restrict__ xp,
                                                                     double4 *__restrict__ vp, int *__restrict__ list,
-                                                                    long long *__restrict__ record) {
+                                                                    long long *__restrict__ record,
+                                                                    const long long *__restrict__ other_min, int other_slots) {
   __shared__ long long redl[kBlock / 64];
   __shared__ int redi[kBlock / 64], wave_cnt[kBlock / 64];
   const int t = threadIdx.x, s = blockIdx.x;
   long long tn = kNever;
   for (int q = t; q < slots; q += kBlock) tn = seg_min[q] < tn ? seg_min[q] : tn;
+  if (JOINT)
+    for (int q = t; q < other_slots; q += kBlock) tn = other_min[q] < tn ? other_min[q] : tn;
   tn = block_min_workgroup(tn, redl);
   int before = 0, total = 0;
   for (int q = t; q < slots; q += kBlock) {
@@ -231,9 +239,27 @@ hipError_t launch_hermite_block_schedule(const HermiteBlockLaunch &L, hipStream_
   int slots;
   const int seg_len = hermite_block_segment(L.n, &slots);
   if (hipError_t e = launch_hermite_block_next(L.T, L.level, L.n, L.levels, L.seg_min, L.seg_cnt, s)) return e;
-  hipLaunchKernelGGL(hermite_block_list_kernel, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
+  hipLaunchKernelGGL(hermite_block_list_kernel<false>, dim3(slots), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
                      (const long long *)L.seg_min, (const int *)L.seg_cnt, slots, L.n, seg_len, L.levels, L.tick, (const double4 *)L.posm,
-                     (const double4 *)L.vel, (const double *)L.aj0, (double4 *)L.xp, (double4 *)L.vp, L.list, L.record);
+                     (const double4 *)L.vel, (const double *)L.aj0, (double4 *)L.xp, (double4 *)L.vp, L.list, L.record,
+                     (const long long *)nullptr, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_hermite_block_schedule_joint(const HermiteBlockLaunch &B, const HermiteBlockLaunch &P, hipStream_t s) {
+  if (bad(B) || !B.xp || !B.vp || bad(P) || !P.xp || !P.vp || B.levels != P.levels || B.tick != P.tick) return hipErrorInvalidValue;
+  int slots[2];
+  const HermiteBlockLaunch *set[2] = {&B, &P};
+  for (const HermiteBlockLaunch *L : set)
+    if (hipError_t e = launch_hermite_block_next(L->T, L->level, L->n, L->levels, L->seg_min, L->seg_cnt, s)) return e;
+  const int seg_len[2] = {hermite_block_segment(B.n, &slots[0]), hermite_block_segment(P.n, &slots[1])};
+  for (int k = 0; k < 2; ++k) {
+    const HermiteBlockLaunch &L = *set[k], &O = *set[k ^ 1];
+    hipLaunchKernelGGL(hermite_block_list_kernel<true>, dim3(slots[k]), dim3(kBlock), 0, s, (const long long *)L.T, (const int *)L.level,
+                       (const long long *)L.seg_min, (const int *)L.seg_cnt, slots[k], L.n, seg_len[k], L.levels, L.tick,
+                       (const double4 *)L.posm, (const double4 *)L.vel, (const double *)L.aj0, (double4 *)L.xp, (double4 *)L.vp, L.list,
+                       L.record, (const long long *)O.seg_min, slots[k ^ 1]);
+  }
   return hipGetLastError();
 }
 
@@ -254,7 +280,7 @@ hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first,
 hipError_t launch_hermite_block_correct(const HermiteBlockLaunch &L, int first, int m, long long t_next, hipStream_t s) {
   if (bad(L) || !L.acc || !L.a2 || !L.a3 || !L.part || first < 0 || m <= 0 || first + m > L.n) return hipErrorInvalidValue;
   int j_split, j_chunk;
-  probe_geometry(L.n, &j_split, &j_chunk);
+  probe_geometry(L.n_field > 0 ? L.n_field : L.n, &j_split, &j_chunk);   // (the rows' chunks are those of the bodies that exert the field)
   const BlockRule r{L.tick, L.dt_max, L.root_eta, L.levels};
   hipLaunchKernelGGL(hermite_block_correct_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const int *)L.list + first, m,
                      (const double *)L.part, j_split, t_next, r, L.T, L.level, (double4 *)L.posm, (double4 *)L.vel, (double4 *)L.acc, L.aj0,

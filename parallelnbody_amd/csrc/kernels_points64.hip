@@ -4,6 +4,10 @@
 //                             double4 velocities against all n_total bodies
 //   snap_points_f64_kernel <- the tile loop of snap_tile64.h the same way; a point's input acceleration (the acc_i of b = acc_j - acc_i)
 //                             is three doubles at pain[k * pain_stride]
+//   <., ., true> of both   <- the LIST forms: the i side taken through an index list — the ACTIVE tracers of a block step
+//                             (nbody_hermite[6]_block_begin_tracers), rows of the tracers' predicted arrays —, the partial rows left
+//                             unfolded for the block corrector.  The <., ., false> forms are instruction for instruction the kernels
+//                             they were (profiles/block_tracers_isa_compare.txt)
 // Both are SIBLINGS of the body templates, not further forms of them: the two headers stay as they are, and so does every kernel built
 // from them (profiles/tracers_f64_isa_compare.txt).  What they share is written out again here, operation for operation in the same
 // order: the chunks of probe_geometry(n_total), the double-buffered 256-body LDS tiles, two j-bodies per staged group,
@@ -30,11 +34,13 @@ namespace {
 
 // local point il = blockIdx.x * (kBlock * IPT) + t + k * kBlock of the slab (ppos, pvel) — the lanes past m repeat point m - 1 and
 // write nothing — against the bodies of chunk blockIdx.y
-template <bool SOFT, int IPT>
+// LIST: local point il is row list[il] of (ppos, pvel) — the active tracers of a block step in the tracers' predicted arrays —, its
+// partial row still part[(c * m + il) * 6]
+template <bool SOFT, int IPT, bool LIST>
 __global__ __launch_bounds__(kBlock) void jerk_points_f64_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
                                                                  const double4 *__restrict__ ppos, const double4 *__restrict__ pvel,
                                                                  double *__restrict__ part, int n_total, int m, int j_chunk,
-                                                                 double gscale, double eps2) {
+                                                                 double gscale, double eps2, const int *__restrict__ list) {
   constexpr int JB = kJerk64Jb, TILE = kJerkTile;
   static_assert(TILE == kBlock, "a lane stages one body per tile");
   __shared__ double4 shp[2][TILE], shv[2][TILE];
@@ -51,7 +57,8 @@ __global__ __launch_bounds__(kBlock) void jerk_points_f64_kernel(const double4 *
 #pragma unroll
   for (int k = 0; k < IPT; ++k) {
     const int il = min(ibase + t + k * kBlock, m - 1);
-    const double4 p = ppos[il], v = pvel[il];
+    const int ip = LIST ? list[il] : il;
+    const double4 p = ppos[ip], v = pvel[ip];
     xi[k] = p.x; yi[k] = p.y; zi[k] = p.z; vxi[k] = v.x; vyi[k] = v.y; vzi[k] = v.z;
 #pragma unroll
     for (int q = 0; q < 3; ++q) { A[k][q] = 0.0; J[k][q] = 0.0; }
@@ -127,13 +134,14 @@ __global__ __launch_bounds__(kBlock) void jerk_points_f64_kernel(const double4 *
 }
 
 // the same for the snap: ain holds body j's input acceleration at ain[j * ain_stride + 0 .. 2], pain point il's at pain[il * pain_stride + 0 .. 2]
-template <bool SOFT, int IPT>
+// (LIST: pain is read at row list[il] too)
+template <bool SOFT, int IPT, bool LIST>
 __global__ __launch_bounds__(kBlock) void snap_points_f64_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
                                                                  const double *__restrict__ ain, int ain_stride,
                                                                  const double4 *__restrict__ ppos, const double4 *__restrict__ pvel,
                                                                  const double *__restrict__ pain, int pain_stride,
                                                                  double *__restrict__ part, int n_total, int m, int j_chunk,
-                                                                 double gscale, double eps2) {
+                                                                 double gscale, double eps2, const int *__restrict__ list) {
   constexpr int JB = kSnapJb, TILE = kSnapTile;
   static_assert(TILE == kBlock, "a lane stages one body per tile");
   __shared__ double4 shp[2][TILE], shv[2][TILE], sha[2][TILE];
@@ -150,7 +158,8 @@ __global__ __launch_bounds__(kBlock) void snap_points_f64_kernel(const double4 *
 #pragma unroll
   for (int k = 0; k < IPT; ++k) {
     const int il = min(ibase + t + k * kBlock, m - 1);
-    const double4 p = ppos[il], v = pvel[il], a = load_ain(pain, pain_stride, il);
+    const int ip = LIST ? list[il] : il;
+    const double4 p = ppos[ip], v = pvel[ip], a = load_ain(pain, pain_stride, ip);
     xi[k] = p.x; yi[k] = p.y; zi[k] = p.z; vxi[k] = v.x; vyi[k] = v.y; vzi[k] = v.z; axi[k] = a.x; ayi[k] = a.y; azi[k] = a.z;
 #pragma unroll
     for (int q = 0; q < 3; ++q) { A[k][q] = 0.0; J[k][q] = 0.0; S[k][q] = 0.0; }
@@ -237,8 +246,8 @@ __global__ __launch_bounds__(kBlock) void snap_points_f64_kernel(const double4 *
 }
 
 // what both launchers refuse: nothing to do, a missing array, or a staging area that does not hold a slab's rows
-bool bad(const Points64Launch &L, int width) {
-  if (L.m <= 0 || L.n_total <= 0 || !L.posm || !L.vel || !L.ppos || !L.pvel || !L.part || !L.out) return true;
+bool bad(const Points64Launch &L, int width, bool folds = true) {
+  if (L.m <= 0 || L.n_total <= 0 || !L.posm || !L.vel || !L.ppos || !L.pvel || !L.part || (folds && !L.out)) return true;
   return L.part_elems < probe_part_elems(L.n_total, L.m, width);
 }
 
@@ -254,10 +263,10 @@ hipError_t launch_jerk_points_f64(const Points64Launch &L, hipStream_t s) {
   for (size_t first = 0; first < (size_t)L.m; first += slab) {
     const int m = (int)std::min(slab, (size_t)L.m - first);
     const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
-    const auto kernel = ipt == 2 ? (soft ? jerk_points_f64_kernel<true, 2> : jerk_points_f64_kernel<false, 2>)
-                                 : (soft ? jerk_points_f64_kernel<true, 1> : jerk_points_f64_kernel<false, 1>);
+    const auto kernel = ipt == 2 ? (soft ? jerk_points_f64_kernel<true, 2, false> : jerk_points_f64_kernel<false, 2, false>)
+                                 : (soft ? jerk_points_f64_kernel<true, 1, false> : jerk_points_f64_kernel<false, 1, false>);
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.vel, (const double4 *)L.ppos + first,
-                       (const double4 *)L.pvel + first, (double *)L.part, L.n_total, m, j_chunk, L.G, L.eps2);
+                       (const double4 *)L.pvel + first, (double *)L.part, L.n_total, m, j_chunk, L.G, L.eps2, (const int *)nullptr);
     if (hipError_t e = launch_jerk_fold_f64(L.part, m, j_split, L.out + 6 * first, s)) return e;
   }
   return hipGetLastError();
@@ -273,13 +282,43 @@ hipError_t launch_snap_points_f64(const Points64Launch &L, hipStream_t s) {
   for (size_t first = 0; first < (size_t)L.m; first += slab) {
     const int m = (int)std::min(slab, (size_t)L.m - first);
     const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
-    const auto kernel = ipt == 2 ? (soft ? snap_points_f64_kernel<true, 2> : snap_points_f64_kernel<false, 2>)
-                                 : (soft ? snap_points_f64_kernel<true, 1> : snap_points_f64_kernel<false, 1>);
+    const auto kernel = ipt == 2 ? (soft ? snap_points_f64_kernel<true, 2, false> : snap_points_f64_kernel<false, 2, false>)
+                                 : (soft ? snap_points_f64_kernel<true, 1, false> : snap_points_f64_kernel<false, 1, false>);
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.vel, L.ain, L.ain_stride,
                        (const double4 *)L.ppos + first, (const double4 *)L.pvel + first, L.pain + first * (size_t)L.pain_stride, L.pain_stride,
-                       (double *)L.part, L.n_total, m, j_chunk, L.G, L.eps2);
+                       (double *)L.part, L.n_total, m, j_chunk, L.G, L.eps2, (const int *)nullptr);
     if (hipError_t e = launch_snap_fold_f64(L.part, m, j_split, L.out + 9 * first, s)) return e;
   }
+  return hipGetLastError();
+}
+
+// The list forms: ONE slab — list[0 .. m), m <= the slab — into part, unfolded: the block corrector adds the chunks' rows itself.
+hipError_t launch_jerk_points_list_f64(const Points64Launch &L, const int *list, hipStream_t s) {
+  if (bad(L, 3, false) || !list || (size_t)L.m > probe_slab_points(L.n_total, 3) || (L.lanes != 1 && L.lanes != 2)) return hipErrorInvalidValue;
+  const bool soft = L.eps2 > 0.0;
+  int j_split, j_chunk;
+  probe_geometry(L.n_total, &j_split, &j_chunk);
+  const dim3 grid((L.m + kBlock * L.lanes - 1) / (kBlock * L.lanes), j_split);
+  const auto kernel = L.lanes == 2 ? (soft ? jerk_points_f64_kernel<true, 2, true> : jerk_points_f64_kernel<false, 2, true>)
+                                   : (soft ? jerk_points_f64_kernel<true, 1, true> : jerk_points_f64_kernel<false, 1, true>);
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.vel, (const double4 *)L.ppos,
+                     (const double4 *)L.pvel, (double *)L.part, L.n_total, L.m, j_chunk, L.G, L.eps2, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_snap_points_list_f64(const Points64Launch &L, const int *list, hipStream_t s) {
+  if (bad(L, kSnapRowWidth, false) || !list || !L.ain || L.ain_stride < 3 || !L.pain || L.pain_stride < 3 ||
+      (size_t)L.m > probe_slab_points(L.n_total, kSnapRowWidth) || (L.lanes != 1 && L.lanes != 2))
+    return hipErrorInvalidValue;
+  const bool soft = L.eps2 > 0.0;
+  int j_split, j_chunk;
+  probe_geometry(L.n_total, &j_split, &j_chunk);
+  const dim3 grid((L.m + kBlock * L.lanes - 1) / (kBlock * L.lanes), j_split);
+  const auto kernel = L.lanes == 2 ? (soft ? snap_points_f64_kernel<true, 2, true> : snap_points_f64_kernel<false, 2, true>)
+                                   : (soft ? snap_points_f64_kernel<true, 1, true> : snap_points_f64_kernel<false, 1, true>);
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.vel, L.ain, L.ain_stride,
+                     (const double4 *)L.ppos, (const double4 *)L.pvel, L.pain, L.pain_stride, (double *)L.part, L.n_total, L.m, j_chunk,
+                     L.G, L.eps2, list);
   return hipGetLastError();
 }
 

@@ -628,7 +628,8 @@ class NBodyEngine:
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
         (nbody_set_tracers_f64); step(), tick() and compute_forces() leave them where they are.  pos, vel: [n, >= 3] float64; vel None =
         at rest; an empty pos removes them.  Replaces any earlier set.  Tracers never act on the bodies or on each other and do not
-        enter the shared step (hermite_tracers_timescale() tells what step they would ask for); block sessions do not carry them."""
+        enter the shared step (hermite_tracers_timescale() tells what step they would ask for); hermite_block_begin_tracers() and
+        hermite6_block_begin_tracers() start block sessions that carry them."""
         p = self._rows64(np.zeros((0, 3)) if pos is None or np.size(pos) == 0 else pos, "set_tracers_f64", "pos")
         v = None if vel is None or p.shape[0] == 0 else self._rows64(vel, "set_tracers_f64", "vel")
         if v is not None and v.shape != p.shape:
@@ -676,6 +677,54 @@ class NBodyEngine:
         t, at, kind = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
         self._check(self._L.nbody_hermite6_tracers_timescale(self._h, ctypes.byref(t), ctypes.byref(at), ctypes.byref(kind)))
         return t.value, at.value, kind.value
+
+    # -- block sessions that carry the fp64 tracers --
+    def _block_begin_tracers(self, fn, dt_max, levels, eta, eta_start, level_in, tracer_level_in):
+        def levels_of(a, count, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.int32)
+            if a.shape != (count,):
+                raise ValueError(f"{name} must hold {count} levels")
+            return a
+        lv = levels_of(level_in, self.n_total, "level_in")
+        tl = None if tracer_level_in is None else np.ascontiguousarray(tracer_level_in, np.int32)
+        if tl is not None and tl.ndim != 1:
+            raise ValueError("tracer_level_in must be one-dimensional")
+        if tl is not None and self.tracer_count_f64 and tl.shape != (self.tracer_count_f64,):
+            raise ValueError(f"tracer_level_in must hold {self.tracer_count_f64} levels")
+        self._check(fn(self._h, float(dt_max), int(levels), float(eta), float(eta_start), None if lv is None else lv.ctypes.data,
+                       None if tl is None else tl.ctypes.data))
+
+    def _block_tracers_state(self, fn):
+        st = _lib.HermiteBlockTracerStats()
+        st.struct_size = ctypes.sizeof(st)
+        self._check(fn(self._h, None, None, ctypes.byref(st)))       # how many the SESSION carries
+        ticks, level = np.empty(st.carried, np.int64), np.empty(st.carried, np.int32)
+        if st.carried:
+            self._check(fn(self._h, ticks.ctypes.data, level.ctypes.data, None))
+        return ticks, level, {name: int(getattr(st, name)) for name, _ in st._fields_ if name != "struct_size"}
+
+    def hermite_block_begin_tracers(self, dt_max, levels, eta=0.02, eta_start=0.01, level_in=None, tracer_level_in=None):
+        """hermite_block_begin() for a context that holds fp64 tracers (nbody_hermite_block_begin_tracers): the session carries them with
+        levels of their own.  One block step takes T_next over bodies AND tracers, predicts everything, and evaluates and corrects the
+        due bodies, then the due tracers in the field of the bodies' predicted state: (m_b + m_t) N pairs.  tracer_level_in: a level per
+        tracer, 0 .. levels; None: from eta_start |a| / |j| of each tracer's own (a0, j0).  Without tracers it is hermite_block_begin()."""
+        self._block_begin_tracers(self._L.nbody_hermite_block_begin_tracers, dt_max, levels, eta, eta_start, level_in, tracer_level_in)
+
+    def hermite6_block_begin_tracers(self, dt_max, levels, eta=0.5, eta_start=0.01, level_in=None, tracer_level_in=None):
+        """hermite6_block_begin() for a context that holds fp64 tracers (nbody_hermite6_block_begin_tracers); see
+        hermite_block_begin_tracers()."""
+        self._block_begin_tracers(self._L.nbody_hermite6_block_begin_tracers, dt_max, levels, eta, eta_start, level_in, tracer_level_in)
+
+    def hermite_block_tracers_state(self):
+        """(ticks [M] int64, levels [M] int32, stats): every carried tracer's own time and level, and the tracers' totals since begin as
+        a dict: carried, tracer_steps, pairs, tracer_only_steps, floor_hits, level_min, level_max (nbody_hermite_block_tracers_get)."""
+        return self._block_tracers_state(self._L.nbody_hermite_block_tracers_get)
+
+    def hermite6_block_tracers_state(self):
+        """hermite_block_tracers_state() of a sixth-order session (nbody_hermite6_block_tracers_get)."""
+        return self._block_tracers_state(self._L.nbody_hermite6_block_tracers_get)
 
     def synchronize(self):
         self._check(self._L.nbody_synchronize(self._h))
