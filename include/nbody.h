@@ -861,6 +861,63 @@ NBODY_AMD_API int nbody_hermite6_tracers_get(nbody_ctx *ctx, double *d18, size_t
 NBODY_AMD_API int nbody_hermite_tracers_timescale(nbody_ctx *ctx, double *t_min, int32_t *tracer, int32_t *kind);
 NBODY_AMD_API int nbody_hermite6_tracers_timescale(nbody_ctx *ctx, double *t_min, int32_t *tracer, int32_t *kind);
 
+/*
+ * The fp64 POTENTIAL, TIDAL TENSOR and SNAP AT POINTS (build-defined: the reference computes none) — what nbody_potential_at,
+ * nbody_get_potentials, nbody_tidal_at, nbody_get_tidal and nbody_tidal_time are to fp32 contexts, for the contexts that answer
+ * nbody_jerk_at_f64: NBODY_PREC_F64, one device, owning all bodies (such contexts are at theta == 0).  NBODY_PREC_F32,
+ * NBODY_PREC_F32_KAHAN, slice and nbody_create_multi contexts report NBODY_ERR_UNSUPPORTED with a message that names the call and says
+ * why; no particles set, or a pending nbody_step_begin: NBODY_ERR_STATE.  The fp32 calls stay exactly what they are, their refusal of
+ * fp64 contexts included.  nbody_jerk_at_f64 with vel == NULL already is the fp64 form of nbody_field_at.
+ *
+ * Definitions.  With d = x_j - x and s^2 = |d|^2 + eps^2, over ALL bodies j of the LIVE positions:
+ *     phi(x)  = -sum_j G m_j / s
+ *     T_ab(x) =  sum_j G m_j [3 d_a d_b / s^5 - delta_ab / s^3]          six components: xx, yy, zz, xy, xz, yz
+ * The pair form.  nbody_get_jerk_f64's chunks (a function of n_total alone), tiles, s^2 = fma(dx, dx, fma(dy, dy, dz dz [+ eps^2]))
+ * and 1 / sqrt; then, with contraction off and every bracket one fp64 operation, gm = G m_j,
+ *     t2 = t * t;  q = (gm * t) * t2                                     (the jerk's q)
+ *     potential:  P = fma(gm, t, P)
+ *     tidal:      h = (3.0 * q) * t2;  hx = h * dx;  hy = h * dy;  hz = h * dz
+ *                 Sxx = fma(hx, dx, Sxx);  Sxy = fma(hx, dy, Sxy);  Sxz = fma(hx, dz, Sxz)
+ *                 Syy = fma(hy, dy, Syy);  Syz = fma(hy, dz, Syz);  Szz = fma(hz, dz, Szz);  Q = Q + q
+ * — one chain per sum and chunk, in body order; the chunks' rows are added from 0.0 in chunk order, then phi = -P and T_aa = S_aa - Q,
+ * one operation each.  The results are those doubles, unrounded.  (s^-5 is formed: unlike fp32, fp64 has the range for it.)
+ * The d == 0 rule.  Point forms (_at): t = (s^2 > 0) ? 1 / s : 0 — NO pair is dropped by index.  Per-body forms (_get_, _time): the
+ * body itself is additionally left out BY INDEX.  A pair with t == 0 and a body of mass 0 add exactly nothing.  So
+ *   - a point's bits depend on the point and the bodies ALONE: not on n, the other points, the slab of the staging area, the rows per
+ *     lane or the device;
+ *   - N bodies queried at M points equal, in every bit, rows N .. N + M - 1 of the per-body call on a context that holds the points
+ *     appended as bodies of mass 0 (while both have 256-body chunks: N + M <= 32768), at every eps;
+ *   - with eps == 0 a body asked about at its own position gets its per-body row in every bit, and a point exactly on a body (or two
+ *     coincident bodies) drops that pair from every sum;
+ *   - with eps > 0 a point exactly on body i additionally feels -G m_i / eps in phi and -G m_i / eps^3 on the diagonal of T (S gets
+ *     exactly 0 from that pair, Q gets q); coincident bodies feel each other the same way.
+ *
+ * nbody_potential_at_f64 / nbody_tidal_at_f64: phi / T at n points.  pos: 3 doubles per point, stride >= 24 bytes; phi: one double per
+ *   point, stride >= 8; t6: six doubles per point, stride >= 48.  n == 0: a no-op.  NULL pointers (NULL pos even with n == 0), n < 0 or
+ *   a stride too small: NBODY_ERR_INVALID.
+ * nbody_get_potentials_f64 / nbody_get_tidal_f64: every body's phi / T from all OTHER bodies — n_total rows, `stride` bytes apart
+ *   (>= 8 / >= 48).  A single body gets 0.
+ * nbody_tidal_time_f64: nbody_tidal_time's rule, in every detail, on the unrounded tensors of nbody_get_tidal_f64:
+ *   n2 = (Txx^2 + Tyy^2) + Tzz^2 + 2 ((Txy^2 + Txz^2) + Tyz^2) per body, the largest n2 and the lowest body index that attains it from the
+ *   same fixed-order reduction; *t_min = 1 / sqrt(sqrt(max n2)), +inf when the maximum is 0 (a single body), 0 when it is not finite.
+ *   Either output may be NULL, not both (NBODY_ERR_INVALID).
+ * nbody_snap_at_f64: the PHYSICAL a, j and s = d^2 a / dt^2 at n moving points (pos, vel as nbody_jerk_at_f64; vel == NULL: at rest).
+ *   Three passes: the bodies' fp64 jerk pass of the live state gives their unrounded accelerations (as nbody_get_snap_f64 with
+ *   acc_in == NULL), the point jerk pass gives the points' own, and the point snap pass takes both as its input accelerations (the pair
+ *   form of nbody_jerk_at_f64 above).  A body asked about at its own (x, v) gets the row of nbody_get_snap_f64(acc_in = NULL) in every
+ *   bit.  acc, jerk, snap: 3 doubles per point, strides >= 24; any may be NULL, not all three.  n == 0, NULL pos, n < 0, short strides:
+ *   as nbody_jerk_at_f64.  THREE passes under NBODY_KERNEL_FORCES.
+ * Every other call here is ONE pass under NBODY_KERNEL_FORCES.  All six synchronise, read the live buffers, change nothing a getter
+ * shows, and leave both Hermite caches, the fp64 tracers and any block session alone.
+ */
+NBODY_AMD_API int nbody_potential_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, double *phi, size_t phi_stride);
+NBODY_AMD_API int nbody_get_potentials_f64(nbody_ctx *ctx, double *phi, size_t stride);
+NBODY_AMD_API int nbody_tidal_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, double *t6, size_t t_stride);
+NBODY_AMD_API int nbody_get_tidal_f64(nbody_ctx *ctx, double *t6, size_t stride);
+NBODY_AMD_API int nbody_tidal_time_f64(nbody_ctx *ctx, double *t_min, int32_t *body);
+NBODY_AMD_API int nbody_snap_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
+                                    double *acc, size_t acc_stride, double *jerk, size_t jerk_stride, double *snap, size_t snap_stride);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -206,6 +206,12 @@ def lib():
     sig("nbody_hermite6_block_advance", c_int, vp, c_i64, c_i64, ctypes.POINTER(HermiteBlockStats))
     sig("nbody_hermite6_block_get", c_int, vp, vp, vp)
     sig("nbody_jerk_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, sz, vp, sz)
+    sig("nbody_potential_at_f64", c_int, vp, vp, sz, c_i32, vp, sz)
+    sig("nbody_get_potentials_f64", c_int, vp, vp, sz)
+    sig("nbody_tidal_at_f64", c_int, vp, vp, sz, c_i32, vp, sz)
+    sig("nbody_get_tidal_f64", c_int, vp, vp, sz)
+    sig("nbody_tidal_time_f64", c_int, vp, dp, ctypes.POINTER(c_i32))
+    sig("nbody_snap_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, sz, vp, sz, vp, sz)
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

@@ -1,5 +1,5 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
-// fp64 tracers, beside the snap and the fp64 point queries they are built on.  Host C++ like capi.hip, whose helpers it shares
+// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip).  Host C++ like capi.hip, whose helpers it shares
 // (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
@@ -769,6 +769,60 @@ void gather_double4(double *dst, const double *src, size_t stride, size_t n) {
   }
 }
 
+// ---- the fp64 potential and tidal tensor (kernels_pot64.hip) ----
+constexpr int kPot64Width = 1, kTidal64Width = 4;   // the float4 of a partial row: one double (half a float4 unused), eight doubles
+
+// phi ([m]) or the tensors ([m][6]) into out (device) — at m points (ppos: double4 each, device) or, ppos == nullptr, at the bodies
+// themselves with each left out by index — from the LIVE positions: one pass under NBODY_KERNEL_FORCES, never queued into a staging
+// area that does not hold a slab's partial rows
+int pot64_pass(nbody_ctx *c, bool tidal, const void *ppos, int m, double *out) {
+  const int width = tidal ? kTidal64Width : kPot64Width;
+  if (int rc = ensure_probe_part(c, m, width)) return rc;
+  if (int rc = points64_part_holds(c, m, width, tidal ? "the fp64 tidal pass" : "the fp64 potential pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Pot64Launch L;
+    L.posm = c->posm; L.ppos = ppos; L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = out;
+    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, tidal ? nbody::launch_tidal_f64(L, c->stream) : nbody::launch_pot_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// nbody_potential_at_f64 / nbody_tidal_at_f64: n points in, `doubles` (1 / 6) per point out
+int pot64_at(nbody_ctx *c, const char *who, bool tidal, const double *pos, size_t pos_stride, int32_t n, double *out, size_t out_stride) {
+  const size_t doubles = tidal ? 6 : 1;
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || !out || out_stride < doubles * 8)
+    return fail(c, NBODY_ERR_INVALID, "%s: null buffer, n < 0, a point stride < 24 or an output stride < %d", who, (int)(doubles * 8));
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n;
+  if ((rc = ensure_stage(c, m * (4 + doubles) * sizeof(double)))) return rc;   // the points as double4, behind them the results
+  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
+  gather_double4(h, pos, pos_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(d, h, m * 32, hipMemcpyHostToDevice, c->stream));
+  if ((rc = pot64_pass(c, tidal, d, n, d + 4 * m))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + 4 * m, d + 4 * m, m * doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  scatter_records(out, out_stride, h + 4 * m, doubles * 8, m);
+  return NBODY_OK;
+}
+
+// nbody_get_potentials_f64 / nbody_get_tidal_f64: n_total rows
+int pot64_get(nbody_ctx *c, const char *who, bool tidal, double *out, size_t stride) {
+  const size_t doubles = tidal ? 6 : 1;
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!out || stride < doubles * 8) return fail(c, NBODY_ERR_INVALID, "%s: null buffer or stride < %d", who, (int)(doubles * 8));
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * doubles * 8))) return rc;
+  if ((rc = pot64_pass(c, tidal, nullptr, (int)n, (double *)c->d_stage))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  scatter_records(out, stride, c->h_stage, doubles * 8, n);
+  return NBODY_OK;
+}
+
 template <class O>
 int tracers_get(nbody_ctx *c, const char *who, double *out, size_t stride) {
   constexpr int kBytes = (O::kRow + 3 * O::kDerivs) * 8;
@@ -937,6 +991,63 @@ int nbody_jerk_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (acc) scatter_records(acc, acc_stride, h + 8 * m, 24, m, 48);
   if (jerk) scatter_records(jerk, jerk_stride, h + 8 * m + 3, 24, m, 48);
+  return NBODY_OK;
+}
+
+int nbody_potential_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double *phi, size_t phi_stride) {
+  return pot64_at(c, "nbody_potential_at_f64", false, pos, pos_stride, n, phi, phi_stride);
+}
+int nbody_get_potentials_f64(nbody_ctx *c, double *phi, size_t stride) { return pot64_get(c, "nbody_get_potentials_f64", false, phi, stride); }
+
+int nbody_tidal_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double *t6, size_t t_stride) {
+  return pot64_at(c, "nbody_tidal_at_f64", true, pos, pos_stride, n, t6, t_stride);
+}
+int nbody_get_tidal_f64(nbody_ctx *c, double *t6, size_t stride) { return pot64_get(c, "nbody_get_tidal_f64", true, t6, stride); }
+
+int nbody_tidal_time_f64(nbody_ctx *c, double *t_min, int32_t *body) {
+  const char *who = "nbody_tidal_time_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!t_min && !body) return fail(c, NBODY_ERR_INVALID, "%s: both outputs are null", who);
+  const int n = c->p.n_total;
+  if (!c->tidal64) HIP_TRY(c, hipMalloc(&c->tidal64, (6 * (size_t)n + 2 * (size_t)nbody::energy_fast_slots(n)) * sizeof(double)));
+  double *t64 = (double *)c->tidal64, *partials = t64 + 6 * (size_t)n;
+  if ((rc = pot64_pass(c, true, nullptr, n, t64))) return rc;
+  HIP_TRY(c, nbody::launch_tidal_time(t64, n, partials, (double *)c->scratch, c->stream));
+  double n2 = 0.0, at = 0.0;
+  if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
+  if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);   // nbody_tidal_time's rule
+  if (body) *body = (int32_t)at;
+  return NBODY_OK;
+}
+
+int nbody_snap_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n, double *acc,
+                      size_t acc_stride, double *jerk, size_t jerk_stride, double *snap, size_t snap_stride) {
+  const char *who = "nbody_snap_at_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || (vel && vel_stride < 24) || (!acc && !jerk && !snap) || (acc && acc_stride < 24) ||
+      (jerk && jerk_stride < 24) || (snap && snap_stride < 24))
+    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, all three outputs null, or a stride < 24", who);
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n;
+  if ((rc = ensure_probe_part(c, n, 3))) return rc;
+  if ((rc = ensure_probe_part(c, n, kSnapRowWidth))) return rc;
+  if ((rc = ensure_stage(c, m * 23 * sizeof(double)))) return rc;   // the points and their velocities as double4, six doubles (a, j), nine (a, j, s)
+  if ((rc = ensure_jerk64(c))) return rc;
+  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
+  gather_double4(h, pos, pos_stride, m);
+  gather_double4(h + 4 * m, vel, vel_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(d, h, m * 64, hipMemcpyHostToDevice, c->stream));
+  // the bodies' unrounded accelerations of the live state (as nbody_get_snap_f64 with acc_in == NULL), the points' own, then the snap
+  if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
+  if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
+  if ((rc = points64_snap(c, c->posm, c->vel, (const double *)c->jerk64, 6, d, d + 4 * m, d + 8 * m, 6, n, d + 14 * m))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + 14 * m, d + 14 * m, m * 72, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (acc) scatter_records(acc, acc_stride, h + 14 * m, 24, m, 72);
+  if (jerk) scatter_records(jerk, jerk_stride, h + 14 * m + 3, 24, m, 72);
+  if (snap) scatter_records(snap, snap_stride, h + 14 * m + 6, 24, m, 72);
   return NBODY_OK;
 }
 

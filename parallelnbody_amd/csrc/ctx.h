@@ -129,7 +129,7 @@ struct nbody_ctx {
   size_t probe_part_elems = 0;
   void *probe_dev = nullptr, *probe_host = nullptr;   // the point queries: probe_cap units of 32 bytes — the points as float4, behind them their results — on the device, and its pinned mirror
   size_t probe_cap = 0;
-  void *tidal64 = nullptr;     // nbody_tidal_time: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
+  void *tidal64 = nullptr;     // nbody_tidal_time / nbody_tidal_time_f64: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
   void *jerk64 = nullptr;      // nbody_get_jerk_f64 / nbody_jerk_time: [n_total][6] double, the bodies' unrounded (a, j), then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
   // Hermite stepping of fp64 contexts (capi_hermite.hip), every instance indexed by order: [0] fourth (nbody_hermite_*,

@@ -89,7 +89,7 @@ struct ProbeLaunch {
   void *clk = nullptr;          // two device uint64 the workgroups add their clock intervals to (pk_common.h)
 };
 void probe_geometry(int n_total, int *j_split, int *j_chunk);
-// width: the float4 a point has in a chunk's partial row at most (1: the field, the potential; 2: the tidal tensor, the jerk; 3: the fp64 jerk)
+// width: the float4 a point has in a chunk's partial row at most (1: the field, the potential; 2: the tidal tensor, the jerk; 3: the fp64 jerk; 4: the fp64 tidal tensor)
 size_t probe_slab_points(int n_total, int width = 1);         // points whose partial rows fit kProbePartBytes (a multiple of 1024)
 inline size_t probe_part_elems(int n_total, int m, int width = 1) {   // float4 elements `part` must hold for a launch of m points
   int js, jc;
@@ -332,6 +332,27 @@ hipError_t launch_snap_points_list_f64(const Points64Launch &L, const int *list,
 // in chunk order
 hipError_t launch_jerk_fold_f64(const void *part, int m, int j_split, double *aj64, hipStream_t s);
 hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *ajs64, hipStream_t s);
+
+// The potential and the tidal tensor of an fp64 state, at the bodies or at m points that are not bodies — kernels_pot64.hip: with
+// d = x_j - x, s^2 = |d|^2 + eps2, t = 1 / s:  phi = -sum_j G m_j t,  T_ab = sum_j G m_j [3 d_a d_b t^5 - delta_ab t^3], fp64 sums over
+// launch_jerk's chunks and tiles on fp64 state in the same order, with its s2 and rsq.  ppos == nullptr: the rows are the bodies
+// (m == n_total), each leaves itself out BY INDEX; else no pair is dropped by index: t = (s2 > 0) ? rsq(s2) : 0.  eps2 == 0: a pair at
+// distance 0 adds nothing; eps2 > 0: a point exactly on body i feels -G m_i / eps in phi and -G m_i / eps^3 on the diagonal of T.  A
+// row's sums depend on its point and the bodies alone; a zero-mass body adds exactly nothing.  A partial row is one double (the
+// potential: probe_slab_points(n_total, 1), half of it used) or eight (the tensor's seven sums and a pad: probe_slab_points(n_total, 4));
+// the rows go in slabs of that many and are folded from 0.0 in chunk order: phi = -P, T_aa = S_aa - Q.
+struct Pot64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1 / 4), or nothing is launched
+  double *out = nullptr;        // [m]: phi — the tensor: [m][6], xx, yy, zz, xy, xz, yz
+  int n_total = 0, m = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no sum (the bodies: always 2)
+  double G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_pot_f64(const Pot64Launch &L, hipStream_t s);
+hipError_t launch_tidal_f64(const Pot64Launch &L, hipStream_t s);
 
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.

@@ -624,6 +624,65 @@ class NBodyEngine:
                                               acc.ctypes.data, 24, jerk.ctypes.data, 24))
         return acc, jerk
 
+    # -- the fp64 potential, tidal tensor and snap at points (fp64 contexts) --
+    def potential_at_f64(self, points):
+        """The bodies' gravitational potential phi = -sum G m / s at every row of `points` (nbody_potential_at_f64): [n] float64, the
+        unrounded fp64 pair sums over ALL bodies from the live positions.  No pair is dropped by index: with eps == 0 a body asked about
+        at its own position gets potentials_f64()'s row in every bit and a point exactly on a body drops that pair; with eps > 0 such a
+        point feels -G m / eps of it.  precision="f64" contexts on one device owning all bodies; everything else: ERR_UNSUPPORTED.
+        Changes nothing a getter shows and leaves the Hermite caches, the fp64 tracers and any block session alone."""
+        p = self._rows64(points, "potential_at_f64", "points")
+        out = np.empty(p.shape[0], np.float64)
+        self._check(self._L.nbody_potential_at_f64(self._h, p.ctypes.data, 24, p.shape[0], out.ctypes.data, 8))
+        return out
+
+    def potentials_f64(self):
+        """Every body's potential from all OTHER bodies (itself left out by index; bodies on the same point are skipped when eps == 0,
+        felt when eps > 0) at the current positions (nbody_get_potentials_f64): [n_total] float64, unrounded.  Contexts and side
+        effects (none) as potential_at_f64()."""
+        out = np.empty(self.n_total, np.float64)
+        self._check(self._L.nbody_get_potentials_f64(self._h, out.ctypes.data, 8))
+        return out
+
+    def tidal_at_f64(self, points):
+        """The bodies' tidal tensor T_ab = d a_a / d x_b at every row of `points` (nbody_tidal_at_f64): [n,6] float64 — xx, yy, zz, xy,
+        xz, yz —, the unrounded fp64 pair sums over ALL bodies.  No pair is dropped by index: with eps == 0 a point exactly on a body
+        drops that pair; with eps > 0 it feels -G m / eps^3 of it on the diagonal.  Contexts and side effects (none) as
+        potential_at_f64()."""
+        p = self._rows64(points, "tidal_at_f64", "points")
+        out = np.empty((p.shape[0], 6), np.float64)
+        self._check(self._L.nbody_tidal_at_f64(self._h, p.ctypes.data, 24, p.shape[0], out.ctypes.data, 48))
+        return out
+
+    def tidal_f64(self):
+        """Every body's tidal tensor from all OTHER bodies at the current positions (nbody_get_tidal_f64): [n_total,6] float64,
+        unrounded.  Contexts and side effects (none) as potential_at_f64()."""
+        out = np.empty((self.n_total, 6), np.float64)
+        self._check(self._L.nbody_get_tidal_f64(self._h, out.ctypes.data, 48))
+        return out
+
+    def tidal_time_f64(self):
+        """(t_min, body): the smallest tidal time scale ||T_i||_F^(-1/2) over the bodies, from the tensors of tidal_f64(), and the lowest
+        body index that attains it (nbody_tidal_time_f64: tidal_time()'s rule); +inf for a single body.  Contexts and side effects
+        (none) as potential_at_f64()."""
+        t, body = ctypes.c_double(), ctypes.c_int32()
+        self._check(self._L.nbody_tidal_time_f64(self._h, ctypes.byref(t), ctypes.byref(body)))
+        return t.value, body.value
+
+    def snap_at_f64(self, points, vel=None):
+        """(acc, jerk, snap): the bodies' acceleration, jerk and physical snap s = d^2 a / dt^2 at every row of `points` moving with
+        `vel` (nbody_snap_at_f64): three [n,3] float64 arrays.  vel None = at rest (the bits an array of zeros gives).  Three passes: the
+        bodies' own accelerations (as snap() with acc_in None), the points' own, then the point snap pass; a body asked about at its
+        own (x, v) gets snap()'s row in every bit.  Contexts and side effects (none) as potential_at_f64()."""
+        p = self._rows64(points, "snap_at_f64", "points")
+        v = None if vel is None else self._rows64(vel, "snap_at_f64", "vel")
+        if v is not None and v.shape != p.shape:
+            raise ValueError("snap_at_f64: points and vel differ in shape")
+        out = [np.empty((p.shape[0], 3), np.float64) for _ in range(3)]
+        self._check(self._L.nbody_snap_at_f64(self._h, p.ctypes.data, 24, None if v is None else v.ctypes.data, 24, p.shape[0],
+                                              out[0].ctypes.data, 24, out[1].ctypes.data, 24, out[2].ctypes.data, 24))
+        return tuple(out)
+
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
         (nbody_set_tracers_f64); step(), tick() and compute_forces() leave them where they are.  pos, vel: [n, >= 3] float64; vel None =
