@@ -918,6 +918,51 @@ NBODY_AMD_API int nbody_tidal_time_f64(nbody_ctx *ctx, double *t_min, int32_t *b
 NBODY_AMD_API int nbody_snap_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
                                     double *acc, size_t acc_stride, double *jerk, size_t jerk_stride, double *snap, size_t snap_stride);
 
+/* The fp64 pair census (build-defined: the reference has none): per row the NEAREST body and the most-bound PARTNER, and the closest
+ * and the hardest pair of the system — which pairs are close and which are bound, the question a Hermite run starts with (one hard
+ * binary sets the shared step and drives block sessions to their level floor).  On the contexts that answer nbody_potential_at_f64;
+ * every other kind refuses with that call's refusals (fp32 state, slices, multi-device: NBODY_ERR_UNSUPPORTED; an open step:
+ * NBODY_ERR_STATE).  theta plays no part: an argmin over ALL pairs of the LIVE (posm, vel).
+ *
+ * Definitions.  For a row at (x, v) with mass term g (a body: g = G m_i; a point: g = 0) and body j, contraction off, every bracket
+ * one fp64 operation, G m_j formed once per body as in the jerk pass:
+ *     d = x_j - x;   d2 = fma(dx, dx, fma(dy, dy, dz dz))                  NEVER softened
+ *     s2 = d2 + eps^2 (d2 itself when eps == 0);   t = (s2 > 0 and j is not the row's own body) ? 1 / sqrt(s2) : 0   (the jerk's 1 / sqrt)
+ *     w = v_j - v;   w2 = fma(wx, wx, fma(wy, wy, wz wz))
+ *     e = fma(-(G m_j + g), t, 0.5 w2)                                     the pair's specific orbital energy under the context's pair law
+ *   Nearest: the body j, not the row's own, with the smallest d2 under strict <; the lowest index wins ties.  A coincident body
+ *     (d2 == 0) is a neighbour, and the nearest, at every eps.
+ *   Partner: the body j, not the row's own, with the smallest e under strict <; the lowest index wins ties.  Its d2 is reported too.
+ *   A candidate whose value is NaN is never chosen, and neither is one whose d2 is not finite (+inf or NaN — so a body whose position
+ *     is NaN is nobody's partner although its e, with t = 0, is the finite 0.5 w2).  No candidate chosen (N == 1, or none admissible):
+ *     index -1, d2 = +inf, e = +inf.
+ *   Zero-mass bodies are bodies and count.  Point forms (_at) drop nothing by index: a point exactly on a body gets that body at d2 = 0.
+ * e_ij and e_ji, d2_ij and d2_ji come from the same operations on negated operands and are equal in every bit, so "mutual" (index[index[i]]
+ * == i) is meaningful.  A row's result depends on the row and the bodies ALONE: not on n, the other rows, the slab of the staging area,
+ * the rows per lane or the device.
+ *
+ * nbody_get_nearest_f64 / nbody_get_partners_f64: every body's row — index, (energy,) d2: contiguous [n_total] arrays; each may be NULL,
+ *   not all (NBODY_ERR_INVALID).
+ * nbody_nearest_at_f64 / nbody_partner_at_f64: the rows of n points.  pos (vel): 3 doubles per point, stride >= 24 bytes; vel == NULL: at
+ *   rest, as nbody_snap_at_f64.  Outputs contiguous [n], each may be NULL, not all.  n == 0: a no-op.  NULL pos, n < 0, a stride too small:
+ *   NBODY_ERR_INVALID.
+ * nbody_closest_pair_f64 / nbody_hardest_pair_f64: the smallest d2 / e of the per-body pass, reduced on the device in a fixed order; the
+ *   lowest row i wins, j is that row's index — so i < j.  -1, -1, +inf (, +inf) when there is none.  Outputs may be NULL, not all.
+ * nbody_pair_time_f64: *t_min = sqrt(d2 sqrt(d2) / (G (m_i + m_j))) of the closest pair (i, j), formed on the host from that pair's d2 and
+ *   the two masses: the free-fall scale a host compares with dt_max 2^-levels.  +inf for a missing pair or G (m_i + m_j) <= 0.
+ * Each per-body or point pass is ONE pass under NBODY_KERNEL_FORCES (the pair calls: one, their reduction is not a pass).  All seven
+ * synchronise, read the live buffers, change nothing a getter shows, and leave both Hermite caches, the fp64 tracers and any block
+ * session alone — in a mid-frame session the rows describe each body at its own time, as nbody_get_potentials_f64's do.
+ */
+NBODY_AMD_API int nbody_get_nearest_f64(nbody_ctx *ctx, int32_t *index, double *d2);
+NBODY_AMD_API int nbody_nearest_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, int32_t *index, double *d2);
+NBODY_AMD_API int nbody_closest_pair_f64(nbody_ctx *ctx, int32_t *i, int32_t *j, double *d2);
+NBODY_AMD_API int nbody_get_partners_f64(nbody_ctx *ctx, int32_t *index, double *energy, double *d2);
+NBODY_AMD_API int nbody_partner_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
+                                       int32_t *index, double *energy, double *d2);
+NBODY_AMD_API int nbody_hardest_pair_f64(nbody_ctx *ctx, int32_t *i, int32_t *j, double *energy, double *d2);
+NBODY_AMD_API int nbody_pair_time_f64(nbody_ctx *ctx, double *t_min, int32_t *i, int32_t *j);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -212,6 +212,13 @@ def lib():
     sig("nbody_get_tidal_f64", c_int, vp, vp, sz)
     sig("nbody_tidal_time_f64", c_int, vp, dp, ctypes.POINTER(c_i32))
     sig("nbody_snap_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, sz, vp, sz, vp, sz)
+    sig("nbody_get_nearest_f64", c_int, vp, vp, vp)
+    sig("nbody_nearest_at_f64", c_int, vp, vp, sz, c_i32, vp, vp)
+    sig("nbody_closest_pair_f64", c_int, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), dp)
+    sig("nbody_get_partners_f64", c_int, vp, vp, vp, vp)
+    sig("nbody_partner_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, vp, vp)
+    sig("nbody_hardest_pair_f64", c_int, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), dp, dp)
+    sig("nbody_pair_time_f64", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

@@ -1,5 +1,5 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
-// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip).  Host C++ like capi.hip, whose helpers it shares
+// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip).  Host C++ like capi.hip, whose helpers it shares
 // (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
@@ -823,6 +823,97 @@ int pot64_get(nbody_ctx *c, const char *who, bool tidal, double *out, size_t str
   return NBODY_OK;
 }
 
+// ---- the fp64 pair census (kernels_census64.hip) ----
+constexpr int kNearest64Width = 1, kPartner64Width = 2;   // the float4 of a partial row: (d2, index), (e, d2, index, pad)
+
+// per row the nearest body (index, value = d2) or, bound, the most-bound partner (index, value = e, d2) into device arrays — at m points
+// (ppos, pvel: double4 each, device) or, ppos == nullptr, at the bodies themselves with each left out by index — from the LIVE state:
+// one pass under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial rows
+int census64_pass(nbody_ctx *c, bool bound, const void *ppos, const void *pvel, int m, int *index, double *value, double *d2) {
+  const int width = bound ? kPartner64Width : kNearest64Width;
+  if (int rc = ensure_probe_part(c, m, width)) return rc;
+  if (int rc = points64_part_holds(c, m, width, bound ? "the fp64 partner pass" : "the fp64 nearest pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Census64Launch L;
+    L.posm = c->posm; L.vel = c->vel; L.ppos = ppos; L.pvel = pvel; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
+    L.index = index; L.value = value; L.d2 = d2;
+    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
+    HIP_TRY(c, bound ? nbody::launch_partner_f64(L, c->stream) : nbody::launch_nearest_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// the results of m rows behind `skip` doubles of the staging pair: value [m], d2 [m], index [m] (int32)
+struct CensusRows { double *value, *d2; int *index; };
+CensusRows census_rows(void *stage, size_t skip, size_t m) {
+  double *v = (double *)stage + skip;
+  return CensusRows{v, v + m, (int *)(v + 2 * m)};
+}
+constexpr size_t kCensusRowBytes = 20;   // of the staging pair, per row
+
+// rows m of the staging pair to the caller's arrays: value and d2 are the nearest form's one array (d2), the partner form's two
+int census64_out(nbody_ctx *c, bool bound, size_t skip, size_t m, int32_t *index, double *energy, double *d2) {
+  HIP_TRY(c, hipMemcpyAsync((double *)c->h_stage + skip, (double *)c->d_stage + skip, m * kCensusRowBytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const CensusRows h = census_rows(c->h_stage, skip, m);
+  if (index) memcpy(index, h.index, m * 4);
+  if (bound) {
+    if (energy) memcpy(energy, h.value, m * 8);
+    if (d2) memcpy(d2, h.d2, m * 8);
+  } else if (d2) {
+    memcpy(d2, h.value, m * 8);
+  }
+  return NBODY_OK;
+}
+
+// nbody_get_nearest_f64 / nbody_get_partners_f64: n_total rows
+int census64_get(nbody_ctx *c, const char *who, bool bound, int32_t *index, double *energy, double *d2) {
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!index && !energy && !d2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * kCensusRowBytes))) return rc;
+  const CensusRows d = census_rows(c->d_stage, 0, n);
+  if ((rc = census64_pass(c, bound, nullptr, nullptr, (int)n, d.index, d.value, d.d2))) return rc;
+  return census64_out(c, bound, 0, n, index, energy, d2);
+}
+
+// nbody_nearest_at_f64 / nbody_partner_at_f64: n points in (bound: moving with vel, NULL = at rest)
+int census64_at(nbody_ctx *c, const char *who, bool bound, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
+                int32_t *index, double *energy, double *d2) {
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || (vel && vel_stride < 24) || (!index && !energy && !d2))
+    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, every output null, or a stride < 24", who);
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n, skip = (bound ? 8 : 4) * m;       // the points (and their velocities) as double4, behind them the results
+  if ((rc = ensure_stage(c, skip * sizeof(double) + m * kCensusRowBytes))) return rc;
+  double *h = (double *)c->h_stage, *dv = (double *)c->d_stage;
+  gather_double4(h, pos, pos_stride, m);
+  if (bound) gather_double4(h + 4 * m, vel, vel_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(dv, h, skip * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  const CensusRows d = census_rows(c->d_stage, skip, m);
+  if ((rc = census64_pass(c, bound, dv, bound ? dv + 4 * m : nullptr, n, d.index, d.value, d.d2))) return rc;
+  return census64_out(c, bound, skip, m, index, energy, d2);
+}
+
+// nbody_closest_pair_f64 / nbody_hardest_pair_f64: the per-body pass, then its smallest value and the lowest row that attains it,
+// reduced on the device in a fixed order — r = (value, i, j = that row's index, d2), (+inf, -1, -1, +inf) where there is none
+int census64_pair(nbody_ctx *c, bool bound, double (&r)[4]) {
+  const size_t n = (size_t)c->p.n_total, slots = (size_t)nbody::energy_fast_slots((int)n);
+  const size_t skip = 2 * slots + 4;                             // the reduction's partials and its four doubles, ahead of the rows
+  int rc = ensure_stage(c, skip * sizeof(double) + n * kCensusRowBytes);
+  if (rc) return rc;
+  double *partials = (double *)c->d_stage, *out = partials + 2 * slots;
+  const CensusRows d = census_rows(c->d_stage, skip, n);
+  if ((rc = census64_pass(c, bound, nullptr, nullptr, (int)n, d.index, d.value, d.d2))) return rc;
+  HIP_TRY(c, nbody::launch_census_pair(d.value, d.index, bound ? d.d2 : nullptr, (int)n, partials, out, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(r, c->h_stage, sizeof(r));
+  return NBODY_OK;
+}
+
 template <class O>
 int tracers_get(nbody_ctx *c, const char *who, double *out, size_t stride) {
   constexpr int kBytes = (O::kRow + 3 * O::kDerivs) * 8;
@@ -1018,6 +1109,68 @@ int nbody_tidal_time_f64(nbody_ctx *c, double *t_min, int32_t *body) {
   if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
   if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);   // nbody_tidal_time's rule
   if (body) *body = (int32_t)at;
+  return NBODY_OK;
+}
+
+int nbody_get_nearest_f64(nbody_ctx *c, int32_t *index, double *d2) { return census64_get(c, "nbody_get_nearest_f64", false, index, nullptr, d2); }
+int nbody_nearest_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, int32_t *index, double *d2) {
+  return census64_at(c, "nbody_nearest_at_f64", false, pos, pos_stride, nullptr, 0, n, index, nullptr, d2);
+}
+int nbody_get_partners_f64(nbody_ctx *c, int32_t *index, double *energy, double *d2) {
+  return census64_get(c, "nbody_get_partners_f64", true, index, energy, d2);
+}
+int nbody_partner_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n, int32_t *index,
+                         double *energy, double *d2) {
+  return census64_at(c, "nbody_partner_at_f64", true, pos, pos_stride, vel, vel_stride, n, index, energy, d2);
+}
+
+int nbody_closest_pair_f64(nbody_ctx *c, int32_t *i, int32_t *j, double *d2) {
+  const char *who = "nbody_closest_pair_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!i && !j && !d2) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
+  double r[4];
+  if ((rc = census64_pair(c, false, r))) return rc;
+  if (i) *i = (int32_t)r[1];
+  if (j) *j = (int32_t)r[2];
+  if (d2) *d2 = r[0];
+  return NBODY_OK;
+}
+
+int nbody_hardest_pair_f64(nbody_ctx *c, int32_t *i, int32_t *j, double *energy, double *d2) {
+  const char *who = "nbody_hardest_pair_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!i && !j && !energy && !d2) return fail(c, NBODY_ERR_INVALID, "%s: all four outputs are null", who);
+  double r[4];
+  if ((rc = census64_pair(c, true, r))) return rc;
+  if (i) *i = (int32_t)r[1];
+  if (j) *j = (int32_t)r[2];
+  if (energy) *energy = r[0];
+  if (d2) *d2 = r[3];
+  return NBODY_OK;
+}
+
+int nbody_pair_time_f64(nbody_ctx *c, double *t_min, int32_t *i, int32_t *j) {
+  const char *who = "nbody_pair_time_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!t_min && !i && !j) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
+  double r[4];
+  if ((rc = census64_pair(c, false, r))) return rc;
+  const int32_t bi = (int32_t)r[1], bj = (int32_t)r[2];
+  double t = HUGE_VAL;                                             // no pair, or a massless one
+  if (bi >= 0 && bj >= 0) {                                        // the free-fall scale of the closest pair, formed here from d2 and the two masses
+    double *h = (double *)c->h_stage;
+    HIP_TRY(c, hipMemcpyAsync(h, (const double *)c->posm + 4 * (size_t)bi + 3, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h + 1, (const double *)c->posm + 4 * (size_t)bj + 3, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double gm = c->p.G * (h[0] + h[1]);
+    if (gm > 0.0) t = std::sqrt(r[0] * std::sqrt(r[0]) / gm);
+  }
+  if (t_min) *t_min = t;
+  if (i) *i = bi;
+  if (j) *j = bj;
   return NBODY_OK;
 }
 

@@ -354,6 +354,37 @@ struct Pot64Launch {
 hipError_t launch_pot_f64(const Pot64Launch &L, hipStream_t s);
 hipError_t launch_tidal_f64(const Pot64Launch &L, hipStream_t s);
 
+// The pair census of an fp64 state, at the bodies or at m points that are not bodies — kernels_census64.hip: an argmin pass over
+// launch_pot_f64's chunks and tiles.  With d = x_j - x, w = v_j - v, d2 = |d|^2 (never softened), s2 = d2 + eps2, t = 1 / s and the
+// row's mass term g (a body: G m_i; a point: 0):
+//   launch_nearest_f64:  index = the body with the smallest d2, value = that d2 — no root; vel, pvel, d2 and eps2 are not read
+//   launch_partner_f64:  index = the body with the smallest e = fma(-(G m_j + g), t, 0.5 |w|^2), value = that e, d2 = that body's d2
+// under strict < in ascending j: the lowest index wins a tie; a value that is NaN and a body whose d2 is not finite are never chosen;
+// no body chosen: (-1, +inf, +inf).  ppos == nullptr: the rows are the bodies (m == n_total), each leaves itself out BY INDEX; else no
+// body is dropped by index.  The zero padding of a chunk's last tile is kept out by index (j < j1); a zero-mass body is a candidate.  A
+// row's result depends on the row and the bodies alone.  A partial row is (d2, index) — probe_slab_points(n_total, 1) — or (e, d2,
+// index, pad) — probe_slab_points(n_total, 2) —; the rows go in slabs of that many and are folded in chunk order under strict <.
+struct Census64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *vel = nullptr;    // [n_total] double4: vx, vy, vz, unused (the partner pass)
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
+  const void *pvel = nullptr;   // [m] double4: the points' velocities (the partner pass, ppos != nullptr)
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1 / 2), or nothing is launched
+  int *index = nullptr;         // [m]
+  double *value = nullptr;      // [m]: d2 (nearest), e (partner)
+  double *d2 = nullptr;         // [m]: the partner's d2 (the partner pass)
+  int n_total = 0, m = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
+  double G = 0.0, eps2 = 0.0;
+};
+hipError_t launch_nearest_f64(const Census64Launch &L, hipStream_t s);
+hipError_t launch_partner_f64(const Census64Launch &L, hipStream_t s);
+// out[0] = the smallest value[i] over the n rows, out[1] = the lowest row i that attains it, out[2] = index[i], out[3] = aux[i] (aux ==
+// nullptr: the value) — (+inf, -1, -1, +inf) where no value is below +inf: launch_tidal_time's two launches and fixed order, for a
+// minimum; `partials` holds 2 * energy_fast_slots(n) doubles
+hipError_t launch_census_pair(const double *value, const int *index, const double *aux, int n, double *partials, double *out, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

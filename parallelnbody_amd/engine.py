@@ -188,6 +188,7 @@ class NBodyEngine:
         self.i_begin = i_begin
         self.i_count = i_count if i_count else n_total - i_begin
         self.f64 = p.precision == _lib.PREC_F64
+        self._G = float(p.G)   # (binaries_f64's elements)
         self._keep = []   # externally bound tensors kept alive
 
     # -- plumbing --
@@ -682,6 +683,97 @@ class NBodyEngine:
         self._check(self._L.nbody_snap_at_f64(self._h, p.ctypes.data, 24, None if v is None else v.ctypes.data, 24, p.shape[0],
                                               out[0].ctypes.data, 24, out[1].ctypes.data, 24, out[2].ctypes.data, 24))
         return tuple(out)
+
+    # -- the fp64 pair census: nearest body, most-bound partner, binaries (fp64 contexts) --
+    def nearest_f64(self):
+        """(index, d2): every body's nearest OTHER body and the squared distance to it (nbody_get_nearest_f64): [n_total] int32 and
+        float64.  d2 = fma(dx, dx, fma(dy, dy, dz dz)) is never softened; the smallest under strict <, the lowest index among equals; a
+        coincident body (d2 == 0) is the nearest; zero-mass bodies count; a body whose d2 is NaN or +inf is never chosen.  Nobody to
+        choose (a single body): -1 and +inf.  d2[i] == d2[index[i]] in every bit where the two are mutual.  precision="f64" contexts on
+        one device owning all bodies; everything else: ERR_UNSUPPORTED.  One pass; changes nothing a getter shows and leaves the Hermite
+        caches, the fp64 tracers and any block session alone."""
+        index, d2 = np.empty(self.n_total, np.int32), np.empty(self.n_total, np.float64)
+        self._check(self._L.nbody_get_nearest_f64(self._h, index.ctypes.data, d2.ctypes.data))
+        return index, d2
+
+    def nearest_at_f64(self, points):
+        """(index, d2): the body nearest to every row of `points` (nbody_nearest_at_f64): [n] int32 and float64.  No body is dropped by
+        index: a point exactly on a body gets that body at d2 = 0.  A row depends on its point and the bodies alone.  Rules, contexts
+        and side effects (none) as nearest_f64()."""
+        p = self._rows64(points, "nearest_at_f64", "points")
+        index, d2 = np.empty(p.shape[0], np.int32), np.empty(p.shape[0], np.float64)
+        self._check(self._L.nbody_nearest_at_f64(self._h, p.ctypes.data, 24, p.shape[0], index.ctypes.data, d2.ctypes.data))
+        return index, d2
+
+    def closest_pair_f64(self):
+        """(i, j, d2): the closest pair of bodies, i < j (nbody_closest_pair_f64): the smallest d2 of nearest_f64() and the lowest body
+        that attains it, reduced on the device in a fixed order; (-1, -1, +inf) when there is none."""
+        i, j, d2 = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        self._check(self._L.nbody_closest_pair_f64(self._h, ctypes.byref(i), ctypes.byref(j), ctypes.byref(d2)))
+        return i.value, j.value, d2.value
+
+    def partners_f64(self):
+        """(index, energy, d2): every body's most-bound partner — the OTHER body j with the smallest specific orbital energy
+        e = 0.5 |v_j - v_i|^2 - G (m_i + m_j) / sqrt(d2 + eps^2) of the pair, under the context's own pair law —, that energy and the
+        pair's unsoftened d2 (nbody_get_partners_f64): [n_total] int32, float64, float64.  Strict <, the lowest index among equals; with
+        eps == 0 a coincident body contributes 0.5 |w|^2 alone; a candidate whose e is NaN or whose d2 is not finite is never chosen;
+        nobody to choose: -1, +inf, +inf.  e is symmetric in every bit, so index[index[i]] == i marks a mutual pair; e < 0: bound.
+        Contexts and side effects (none) as nearest_f64()."""
+        index, e, d2 = np.empty(self.n_total, np.int32), np.empty(self.n_total, np.float64), np.empty(self.n_total, np.float64)
+        self._check(self._L.nbody_get_partners_f64(self._h, index.ctypes.data, e.ctypes.data, d2.ctypes.data))
+        return index, e, d2
+
+    def partner_at_f64(self, points, vel=None):
+        """(index, energy, d2): the body every row of `points`, moving with `vel`, is most bound to as a massless point: the smallest
+        e = 0.5 |v_j - v|^2 - G m_j / sqrt(d2 + eps^2) (nbody_partner_at_f64).  vel None = at rest (the bits an array of zeros gives).
+        No body is dropped by index.  Rules, contexts and side effects (none) as partners_f64()."""
+        p = self._rows64(points, "partner_at_f64", "points")
+        v = None if vel is None else self._rows64(vel, "partner_at_f64", "vel")
+        if v is not None and v.shape != p.shape:
+            raise ValueError("partner_at_f64: points and vel differ in shape")
+        index, e, d2 = np.empty(p.shape[0], np.int32), np.empty(p.shape[0], np.float64), np.empty(p.shape[0], np.float64)
+        self._check(self._L.nbody_partner_at_f64(self._h, p.ctypes.data, 24, None if v is None else v.ctypes.data, 24, p.shape[0],
+                                                 index.ctypes.data, e.ctypes.data, d2.ctypes.data))
+        return index, e, d2
+
+    def hardest_pair_f64(self):
+        """(i, j, energy, d2): the pair with the lowest specific orbital energy, i < j (nbody_hardest_pair_f64): the smallest e of
+        partners_f64() and the lowest body that attains it, reduced on the device in a fixed order; (-1, -1, +inf, +inf) when there
+        is none."""
+        i, j, e, d2 = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.nbody_hardest_pair_f64(self._h, ctypes.byref(i), ctypes.byref(j), ctypes.byref(e), ctypes.byref(d2)))
+        return i.value, j.value, e.value, d2.value
+
+    def pair_time_f64(self):
+        """(t_min, i, j): the free-fall scale sqrt(d2 sqrt(d2) / (G (m_i + m_j))) of the closest pair (nbody_pair_time_f64) — what a
+        host compares with dt_max 2^-levels; +inf for a massless or missing pair."""
+        t, i, j = ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.nbody_pair_time_f64(self._h, ctypes.byref(t), ctypes.byref(i), ctypes.byref(j)))
+        return t.value, i.value, j.value
+
+    BINARY_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("energy", np.float64), ("a", np.float64), ("ecc", np.float64)])
+
+    def binaries_f64(self):
+        """The bound mutual pairs: a structured array (i, j, energy, a, ecc), i < j, of the pairs with partner[partner[i]] == i and
+        energy < 0 from partners_f64().  a = -G (m_i + m_j) / (2 energy); ecc = |(w x (r x w)) / (G (m_i + m_j)) - r / |r|| from the
+        relative state r = x_j - x_i, w = v_j - v_i of state(np.float64), in numpy.  Keplerian elements for eps == 0: with softening
+        the energy is the softened pair law's and a, ecc only approximate the orbit.  Python only; one pass and one state read."""
+        index, energy, _ = self.partners_f64()
+        i = np.arange(self.n_total, dtype=np.int32)
+        ok = index >= 0
+        mutual = np.zeros(self.n_total, bool)
+        mutual[ok] = (index[index[ok]] == i[ok]) & (i[ok] < index[ok]) & (energy[ok] < 0.0)
+        out = np.zeros(int(mutual.sum()), self.BINARY_DTYPE)
+        out["i"], out["j"], out["energy"] = i[mutual], index[mutual], energy[mutual]
+        if out.size:
+            posm, vel, _ = self.state(np.float64)
+            r = posm[out["j"], :3] - posm[out["i"], :3]
+            w = vel[out["j"], :3] - vel[out["i"], :3]
+            mu = self._G * (posm[out["i"], 3] + posm[out["j"], 3])
+            out["a"] = -mu / (2.0 * out["energy"])
+            ev = np.cross(w, np.cross(r, w)) / mu[:, None] - r / np.linalg.norm(r, axis=1)[:, None]
+            out["ecc"] = np.linalg.norm(ev, axis=1)
+        return out
 
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
