@@ -963,6 +963,56 @@ NBODY_AMD_API int nbody_partner_at_f64(nbody_ctx *ctx, const double *pos, size_t
 NBODY_AMD_API int nbody_hardest_pair_f64(nbody_ctx *ctx, int32_t *i, int32_t *j, double *energy, double *d2);
 NBODY_AMD_API int nbody_pair_time_f64(nbody_ctx *ctx, double *t_min, int32_t *i, int32_t *j);
 
+/* The fp64 neighbour census (build-defined: the reference has none): per row the k NEAREST bodies, and on top of them every body's local
+ * density and the system's density centre and core radius (Casertano & Hut 1985, in NBODY6's convention) — where the cluster is and
+ * how concentrated, which the centre of mass (escapers drag it) cannot say.  On the contexts that answer nbody_get_nearest_f64; every
+ * other kind refuses with that call's refusals.  An fp64 sibling of the pair census, with its conventions throughout.
+ *
+ * Lists.  d2 = fma(dx, dx, fma(dy, dy, dz dz)), d = x_j - x, NEVER softened.  A row's list holds the k bodies j, not the row's own, with
+ *   the smallest d2, sorted ascending in lexicographic (d2, index) order: strict <, the lowest index wins every tie.  A coincident body
+ *   (d2 == 0) is a neighbour and comes first; zero-mass bodies count; a candidate whose d2 is NaN or +inf is never listed.  Slots with
+ *   nobody to list (N <= k, or fewer admissible bodies) read index -1, d2 = +inf.  Point forms (_at) drop nothing by index: a point
+ *   exactly on a body gets that body at d2 = 0.  The answer for k is, byte for byte, the first k entries of the answer for any larger k,
+ *   and k = 1 is nbody_get_nearest_f64 / nbody_nearest_at_f64 in every byte.  A row depends on the row and the bodies ALONE: not on n,
+ *   the other rows, the slab of the staging area, the rows per lane, the compiled list width or the device.
+ * Density of a body with its k nearest listed (2 <= k), every bracket one correctly rounded fp64 operation:
+ *     msum = ((m_1 + m_2) + ...) + m_(k-1)      the raw masses of the k - 1 nearest, in neighbour order
+ *     r2 = d2_k;   rho = msum / ((4.0 * M_PI / 3.0) * (r2 * sqrt(r2)))
+ *   The k-th neighbour sets the sphere and is left out of the mass, as is the body itself.  The k-th missing (N <= k): rho = 0, r2 = +inf.
+ *   A NaN quotient becomes 0; r2 == 0 with msum > 0 gives +inf.
+ * Density centre and core radius, with w_i = rho_i where 0 < rho_i < +inf, else 0, summed on the device in a fixed order (no atomics:
+ *   the same bits every run):
+ *     rho_sum = sum w_i;    centre = (sum w_i x_i) / rho_sum
+ *     rho2_sum = sum w_i^2; core_radius = sqrt((sum w_i^2 |x_i - centre|^2) / rho2_sum)
+ *   rho_max, densest: the largest w and the lowest body that attains it; used: the bodies with w > 0.  used == 0: centre and
+ *   core_radius are NaN, densest -1, rho_max 0, and the call returns NBODY_OK.
+ *
+ * nbody_get_neighbours_f64: every body's list — index, d2: [n_total x k] each, row-major; either may be NULL, not both.
+ * nbody_neighbours_at_f64: the lists of n points.  pos: 3 doubles per point, stride >= 24 bytes.  index, d2: [n x k]; either may be NULL,
+ *   not both.  n == 0: a no-op.  NULL pos, n < 0, a stride too small: NBODY_ERR_INVALID.
+ * nbody_get_density_f64: rho and rk2 = d2_k per body, [n_total] each; either may be NULL, not both.
+ * nbody_density_centre_f64: set out->struct_size = sizeof(nbody_core) first; out == NULL or another size is NBODY_ERR_INVALID.
+ * k outside 1 .. NBODY_NEIGHBOURS_MAX (the lists) or 2 .. NBODY_NEIGHBOURS_MAX (the density calls): NBODY_ERR_INVALID.  No particles
+ * set: NBODY_ERR_STATE.  Each call is ONE pass under NBODY_KERNEL_FORCES (the reductions are not passes), synchronises, reads the live
+ * buffers, changes nothing a getter shows, and leaves both Hermite caches, the fp64 tracers and any block session alone.
+ */
+#define NBODY_NEIGHBOURS_MAX 8
+typedef struct nbody_core {
+  uint32_t struct_size;   /* caller sets sizeof(nbody_core) before the call */
+  int32_t k;              /* the k the densities were formed with */
+  int32_t used;           /* bodies with 0 < rho < +inf */
+  int32_t densest;        /* the lowest body with the largest such rho; -1: none */
+  double rho_max;         /* that rho; 0: none */
+  double centre[3];       /* the density centre; NaN: used == 0 */
+  double core_radius;     /* NaN: used == 0 */
+  double rho_sum;         /* sum w */
+  double rho2_sum;        /* sum w^2 */
+} nbody_core;
+NBODY_AMD_API int nbody_get_neighbours_f64(nbody_ctx *ctx, int32_t k, int32_t *index, double *d2);
+NBODY_AMD_API int nbody_neighbours_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, int32_t k, int32_t *index, double *d2);
+NBODY_AMD_API int nbody_get_density_f64(nbody_ctx *ctx, int32_t k, double *rho, double *rk2);
+NBODY_AMD_API int nbody_density_centre_f64(nbody_ctx *ctx, int32_t k, nbody_core *out);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -10,6 +10,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite-block --levels 12 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6-block --levels 12 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --core-every 5 --core-k 6       # density centre and core radius
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -73,6 +74,11 @@ def main(argv=None):
     ap.add_argument("--moments-every", type=int, default=0,
                     help="print |P|, |L|, the centre of mass, |net force|, |net torque| and the virial every K frames (one O(N) pass on "
                          "the device; force, torque and virial are those of the accelerations the last step stored)")
+    ap.add_argument("--core-every", type=int, default=0,
+                    help="print the density centre, the core radius, the densest body and the core mass every K frames (--precision f64 "
+                         "only: one neighbour pass over all pairs and two O(N) reductions on the device; Casertano & Hut's local "
+                         "densities in NBODY6's convention)")
+    ap.add_argument("--core-k", type=int, default=6, help="--core-every: the neighbour that sets a body's density sphere, 2 .. 8 (default 6)")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -94,6 +100,12 @@ def main(argv=None):
 
     if a.trajectory_every < 1:
         ap.error("--trajectory-every must be >= 1")
+    if a.core_every < 0:
+        ap.error("--core-every must be >= 0")
+    if a.core_every > 0 and a.precision != "f64":
+        ap.error("--core-every needs --precision f64: the neighbour census runs on fp64 contexts only")
+    if a.core_every > 0 and not 2 <= a.core_k <= 8:
+        ap.error("--core-k must be 2 .. 8")
     block6 = a.integrator == "hermite6-block"                        # the same demands and exclusions as hermite-block
     block = a.integrator == "hermite-block" or block6
     hermite = a.integrator == "hermite" or block
@@ -163,7 +175,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.moments_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -181,6 +193,11 @@ def main(argv=None):
                 print(json.dumps({"frame": frame, "moments": {"P": norm(m.p), "L": norm(m.l), "com": [float(c) for c in m.com],
                                                               "net_force": norm(m.force), "net_torque": norm(m.torque),
                                                               "virial": m.virial}}), flush=True)
+            if a.core_every > 0 and frame % a.core_every == 0:
+                c = e.core_f64(a.core_k)
+                print(json.dumps({"frame": frame, "core": {"k": c.k, "centre": [float(x) for x in c.centre], "core_radius": c.core_radius,
+                                                           "densest": c.densest, "rho_max": c.rho_max, "used": c.used,
+                                                           "core_mass": c.core_mass, "core_count": c.core_count}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

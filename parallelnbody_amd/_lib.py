@@ -111,7 +111,23 @@ class HermiteBlockTracerStats(ctypes.Structure):
     ]
 
 
+class Core(ctypes.Structure):
+    """struct nbody_core (include/nbody.h): the density centre and core radius of nbody_density_centre_f64."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("k", ctypes.c_int32),
+        ("used", ctypes.c_int32),
+        ("densest", ctypes.c_int32),
+        ("rho_max", ctypes.c_double),
+        ("centre", ctypes.c_double * 3),
+        ("core_radius", ctypes.c_double),
+        ("rho_sum", ctypes.c_double),
+        ("rho2_sum", ctypes.c_double),
+    ]
+
+
 MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
+NEIGHBOURS_MAX = 8        # NBODY_NEIGHBOURS_MAX: the longest list nbody_get_neighbours_f64 answers
 
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 DRAW_POINT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
@@ -219,6 +235,10 @@ def lib():
     sig("nbody_partner_at_f64", c_int, vp, vp, sz, vp, sz, c_i32, vp, vp, vp)
     sig("nbody_hardest_pair_f64", c_int, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), dp, dp)
     sig("nbody_pair_time_f64", c_int, vp, dp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32))
+    sig("nbody_get_neighbours_f64", c_int, vp, c_i32, vp, vp)
+    sig("nbody_neighbours_at_f64", c_int, vp, vp, sz, c_i32, c_i32, vp, vp)
+    sig("nbody_get_density_f64", c_int, vp, c_i32, vp, vp)
+    sig("nbody_density_centre_f64", c_int, vp, c_i32, ctypes.POINTER(Core))
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

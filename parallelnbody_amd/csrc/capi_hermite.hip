@@ -1,5 +1,5 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
-// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip).  Host C++ like capi.hip, whose helpers it shares
+// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip) and neighbour census (kernels_neighbours64.hip).  Host C++ like capi.hip, whose helpers it shares
 // (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
@@ -914,6 +914,44 @@ int census64_pair(nbody_ctx *c, bool bound, double (&r)[4]) {
   return NBODY_OK;
 }
 
+// ---- the fp64 neighbour census (kernels_neighbours64.hip) ----
+// per row the k nearest bodies (index, d2: rows of k) and, at the bodies with 2 <= k, the local density (rho, rk2) into device arrays
+// (each may be null) — at m points (ppos: double4, device) or, ppos == nullptr, at the bodies themselves with each left out by index —
+// from the LIVE state: one pass under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial rows
+int neighbours64_pass(nbody_ctx *c, int k, const void *ppos, int m, int *index, double *d2, double *rho, double *rk2) {
+  const int width = nbody::neighbours64_width(k);
+  if (int rc = ensure_probe_part(c, m, width)) return rc;
+  if (int rc = points64_part_holds(c, m, width, "the fp64 neighbour pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Neighbours64Launch L;
+    L.posm = c->posm; L.ppos = ppos; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
+    L.index = index; L.d2 = d2; L.rho = rho; L.rk2 = rk2;
+    L.n_total = c->p.n_total; L.m = m; L.k = k; L.G = c->p.G;
+    HIP_TRY(c, nbody::launch_neighbours_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
+// the lists of m rows behind `skip` doubles of the staging pair — d2 [m * k], index [m * k] (int32) — to the caller's arrays
+int neighbours64_lists(nbody_ctx *c, int k, const void *ppos, size_t skip, size_t m, int32_t *index, double *d2) {
+  double *dd2 = (double *)c->d_stage + skip;
+  int *dindex = (int *)(dd2 + m * k);
+  if (int rc = neighbours64_pass(c, k, ppos, (int)m, dindex, dd2, nullptr, nullptr)) return rc;
+  HIP_TRY(c, hipMemcpyAsync((double *)c->h_stage + skip, dd2, m * k * 12, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const double *hd2 = (const double *)c->h_stage + skip;
+  if (d2) memcpy(d2, hd2, m * k * 8);
+  if (index) memcpy(index, hd2 + m * k, m * k * 4);
+  return NBODY_OK;
+}
+
+// k within lo .. NBODY_NEIGHBOURS_MAX
+static_assert(nbody::kNeighbours64Max == NBODY_NEIGHBOURS_MAX, "the widest compiled list is the largest k of the C-ABI");
+int neighbours64_k(nbody_ctx *c, const char *who, int32_t k, int lo) {
+  if (k >= lo && k <= NBODY_NEIGHBOURS_MAX) return NBODY_OK;
+  return fail(c, NBODY_ERR_INVALID, "%s: k = %d is outside %d .. %d", who, (int)k, lo, NBODY_NEIGHBOURS_MAX);
+}
+
 template <class O>
 int tracers_get(nbody_ctx *c, const char *who, double *out, size_t stride) {
   constexpr int kBytes = (O::kRow + 3 * O::kDerivs) * 8;
@@ -1171,6 +1209,71 @@ int nbody_pair_time_f64(nbody_ctx *c, double *t_min, int32_t *i, int32_t *j) {
   if (t_min) *t_min = t;
   if (i) *i = bi;
   if (j) *j = bj;
+  return NBODY_OK;
+}
+
+int nbody_get_neighbours_f64(nbody_ctx *c, int32_t k, int32_t *index, double *d2) {
+  const char *who = "nbody_get_neighbours_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if ((rc = neighbours64_k(c, who, k, 1))) return rc;
+  if (!index && !d2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * k * 12))) return rc;
+  return neighbours64_lists(c, k, nullptr, 0, n, index, d2);
+}
+
+int nbody_neighbours_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, int32_t k, int32_t *index, double *d2) {
+  const char *who = "nbody_neighbours_at_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if ((rc = neighbours64_k(c, who, k, 1))) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || (!index && !d2))
+    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, every output null, or a stride < 24", who);
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n, skip = 4 * m;                        // the points as double4, behind them the lists
+  if ((rc = ensure_stage(c, skip * sizeof(double) + m * k * 12))) return rc;
+  gather_double4((double *)c->h_stage, pos, pos_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(c->d_stage, c->h_stage, skip * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return neighbours64_lists(c, k, c->d_stage, skip, m, index, d2);
+}
+
+int nbody_get_density_f64(nbody_ctx *c, int32_t k, double *rho, double *rk2) {
+  const char *who = "nbody_get_density_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if ((rc = neighbours64_k(c, who, k, 2))) return rc;
+  if (!rho && !rk2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * 16))) return rc;
+  double *d = (double *)c->d_stage;
+  if ((rc = neighbours64_pass(c, k, nullptr, (int)n, nullptr, nullptr, d, d + n))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, d, n * 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (rho) memcpy(rho, c->h_stage, n * 8);
+  if (rk2) memcpy(rk2, (const double *)c->h_stage + n, n * 8);
+  return NBODY_OK;
+}
+
+int nbody_density_centre_f64(nbody_ctx *c, int32_t k, nbody_core *out) {
+  const char *who = "nbody_density_centre_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if ((rc = neighbours64_k(c, who, k, 2))) return rc;
+  if (!out || out->struct_size != sizeof(nbody_core)) return fail(c, NBODY_ERR_INVALID, "%s: null output or struct_size != sizeof(nbody_core)", who);
+  const size_t n = (size_t)c->p.n_total, slots = (size_t)nbody::energy_fast_slots((int)n);
+  const size_t skip = 8 * slots + 16;                            // the reductions' partials and their nine doubles, ahead of the densities
+  if ((rc = ensure_stage(c, (skip + n) * sizeof(double)))) return rc;
+  double *partials = (double *)c->d_stage, *red = partials + 8 * slots, *rho = partials + skip;
+  if ((rc = neighbours64_pass(c, k, nullptr, (int)n, nullptr, nullptr, rho, nullptr))) return rc;
+  HIP_TRY(c, nbody::launch_density_centre(c->posm, rho, (int)n, partials, red, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, red, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const double *r = (const double *)c->h_stage;
+  out->k = k; out->used = (int32_t)r[4]; out->densest = (int32_t)r[6];
+  out->rho_max = r[5];
+  out->centre[0] = r[1]; out->centre[1] = r[2]; out->centre[2] = r[3];
+  out->core_radius = r[8]; out->rho_sum = r[0]; out->rho2_sum = r[7];
   return NBODY_OK;
 }
 

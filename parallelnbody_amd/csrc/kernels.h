@@ -385,6 +385,39 @@ hipError_t launch_partner_f64(const Census64Launch &L, hipStream_t s);
 // minimum; `partials` holds 2 * energy_fast_slots(n) doubles
 hipError_t launch_census_pair(const double *value, const int *index, const double *aux, int n, double *partials, double *out, hipStream_t s);
 
+// The neighbour census of an fp64 state, at the bodies or at m points that are not bodies — kernels_neighbours64.hip: launch_nearest_f64's
+// pass with a sorted list of K (d2, index) per row where that keeps one.  Per row the k bodies with the smallest d2 (never softened), in
+// lexicographic (d2, index) order: strict < in ascending j, so the lowest index wins every tie; a d2 that is NaN or +inf is never
+// listed; the empty slots read (-1, +inf).  ppos == nullptr: the rows are the bodies (m == n_total), each leaves itself out BY INDEX;
+// else no body is dropped by index.  The padding of a chunk's last tile is kept out by index; a zero-mass body is a candidate.  The
+// compiled width is neighbours64_width(k) (4, 6 or 8); the answer for k is the first k entries of the list whichever width ran, and a
+// row's list depends on the row and the bodies alone.  A partial row is K x (d2, index) — probe_slab_points(n_total, K) —; the rows go
+// in slabs of that many and are merged in chunk order under strict <.
+//   index, d2:  [m * k] each, rows of k; either may be null
+//   rho, rk2:   [m] each, the bodies' form with 2 <= k only; either may be null.  The Casertano-Hut density: rho = msum / ((4 pi / 3)
+//               (r2 sqrt(r2))) with msum the raw masses of the k - 1 nearest added in neighbour order and r2 = rk2 = d2 of the k-th;
+//               rho = 0 where the k-th is missing (rk2 = +inf) or the quotient is NaN
+constexpr int kNeighbours64Max = 8;   // == NBODY_NEIGHBOURS_MAX
+struct Neighbours64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, neighbours64_width(k)), or nothing is launched
+  int *index = nullptr;
+  double *d2 = nullptr, *rho = nullptr, *rk2 = nullptr;
+  int n_total = 0, m = 0, k = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
+  double G = 0.0;               // the tiles hold G m as the census's do; no result reads it
+};
+int neighbours64_width(int k);
+hipError_t launch_neighbours_f64(const Neighbours64Launch &L, hipStream_t s);
+// The density centre and core radius of n bodies from their densities rho (weights w = rho where 0 < rho < +inf, else 0), two O(N)
+// passes in launch_energy_fast's fixed order, no atomics: out[0] = S0 = sum w, out[1 .. 3] = centre = (sum w x) / S0, out[4] = used (the
+// bodies with w > 0), out[5] = the largest w, out[6] = the lowest body that attains it, out[7] = Q0 = sum w^2, out[8] = core radius =
+// sqrt(sum w^2 |x - centre|^2 / Q0).  used == 0: centre and radius NaN, out[5] = 0, out[6] = -1.  `partials` holds
+// 8 * energy_fast_slots(n) doubles.
+hipError_t launch_density_centre(const void *posm, const double *rho, int n, double *partials, double *out, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

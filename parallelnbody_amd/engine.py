@@ -111,6 +111,12 @@ MOMENT_FIELDS = ("mass", "mx", "p", "l", "second", "kinetic", "virial", "force",
 MomentsResult = collections.namedtuple("MomentsResult", ("count",) + MOMENT_FIELDS + ("com", "com_velocity", "l_about_com"))
 
 
+# NBodyEngine.core_f64(): the fields of struct nbody_core (centre a float64 array of 3), then — Python only — the mass and the number
+# of bodies within core_radius of the centre, from mass_within()
+CoreResult = collections.namedtuple("CoreResult", ("k", "used", "densest", "rho_max", "centre", "core_radius", "rho_sum", "rho2_sum",
+                                                   "core_mass", "core_count"))
+
+
 def moments_result(count, sums):
     """MomentsResult from the bodies' count and the raw sums (a mapping of MOMENT_FIELDS) — also of sums added over ranks or slices."""
     raw = {k: (float(sums[k]) if k in ("mass", "kinetic", "virial") else np.array(sums[k], np.float64)) for k in MOMENT_FIELDS}
@@ -774,6 +780,67 @@ class NBodyEngine:
             ev = np.cross(w, np.cross(r, w)) / mu[:, None] - r / np.linalg.norm(r, axis=1)[:, None]
             out["ecc"] = np.linalg.norm(ev, axis=1)
         return out
+
+    # -- the fp64 neighbour census: k nearest bodies, local density, density centre and core radius (fp64 contexts) --
+    @staticmethod
+    def _k(k):
+        """(k, the columns to allocate): a k out of range is the library's to refuse (ERR_INVALID), before it writes anything"""
+        k = int(k)
+        return k, min(max(k, 1), _lib.NEIGHBOURS_MAX)
+
+    def neighbours_f64(self, k=6):
+        """(index, d2): every body's k nearest OTHER bodies and the squared distances to them (nbody_get_neighbours_f64): [n_total, k]
+        int32 and float64, each row sorted ascending in lexicographic (d2, index) order.  d2 = fma(dx, dx, fma(dy, dy, dz dz)) is never
+        softened; strict <, the lowest index among equals; coincident bodies (d2 == 0) come first; zero-mass bodies count; a body whose
+        d2 is NaN or +inf is never listed.  Slots with nobody to list (n_total <= k): -1 and +inf.  k = 1 .. 8; the answer for k is the
+        first k columns of the answer for any larger k in every byte, and k = 1 is nearest_f64()'s.  precision="f64" contexts on one
+        device owning all bodies; everything else: ERR_UNSUPPORTED.  One pass; changes nothing a getter shows and leaves the Hermite
+        caches, the fp64 tracers and any block session alone."""
+        k, cols = self._k(k)
+        index, d2 = np.empty((self.n_total, cols), np.int32), np.empty((self.n_total, cols), np.float64)
+        self._check(self._L.nbody_get_neighbours_f64(self._h, k, index.ctypes.data, d2.ctypes.data))
+        return index, d2
+
+    def neighbours_at_f64(self, points, k=6):
+        """(index, d2): the k bodies nearest to every row of `points` (nbody_neighbours_at_f64): [n, k] int32 and float64.  No body is
+        dropped by index: a point exactly on a body gets that body at d2 = 0.  A row depends on its point and the bodies alone.  Rules,
+        contexts and side effects (none) as neighbours_f64()."""
+        k, cols = self._k(k)
+        p = self._rows64(points, "neighbours_at_f64", "points")
+        index, d2 = np.empty((p.shape[0], cols), np.int32), np.empty((p.shape[0], cols), np.float64)
+        self._check(self._L.nbody_neighbours_at_f64(self._h, p.ctypes.data, 24, p.shape[0], k, index.ctypes.data, d2.ctypes.data))
+        return index, d2
+
+    def density_f64(self, k=6):
+        """(rho, rk2): every body's local density after Casertano & Hut (1985) and the squared distance of its k-th neighbour
+        (nbody_get_density_f64): [n_total] float64 each.  rho = msum / ((4 pi / 3) (rk2 sqrt(rk2))) with msum the raw masses of the
+        k - 1 nearest added in neighbour order — the k-th sets the sphere and is left out of the mass, as is the body itself; every
+        bracket one rounded fp64 operation, so numpy reproduces rho in every bit from neighbours_f64(k) and the masses.  k = 2 .. 8.
+        n_total <= k: rho = 0, rk2 = +inf; a NaN quotient becomes 0; rk2 == 0 with msum > 0 gives +inf.  Contexts and side effects
+        (none) as neighbours_f64()."""
+        k, _ = self._k(k)
+        rho, rk2 = np.empty(self.n_total, np.float64), np.empty(self.n_total, np.float64)
+        self._check(self._L.nbody_get_density_f64(self._h, k, rho.ctypes.data, rk2.ctypes.data))
+        return rho, rk2
+
+    def core_f64(self, k=6):
+        """The density centre and core radius in NBODY6's convention (nbody_density_centre_f64): a CoreResult.  With w = rho of
+        density_f64(k) where 0 < rho < +inf, else 0: centre = sum w x / sum w, core_radius = sqrt(sum w^2 |x - centre|^2 / sum w^2), both
+        sums on the device in a fixed order (the same bits every run); rho_sum = sum w, rho2_sum = sum w^2; rho_max, densest: the largest
+        w and the lowest body that attains it; used: the bodies with w > 0.  used == 0: centre and core_radius NaN, densest -1,
+        rho_max 0.  core_mass, core_count (Python only): the mass and the bodies within core_radius of the centre, from mass_within()
+        (0 and 0 when used == 0).  One pass; contexts and side effects (none) as neighbours_f64()."""
+        k, _ = self._k(k)
+        c = _lib.Core()
+        c.struct_size = ctypes.sizeof(c)
+        self._check(self._L.nbody_density_centre_f64(self._h, k, ctypes.byref(c)))
+        centre = np.array(list(c.centre), np.float64)
+        mass, count = 0.0, 0
+        if c.used > 0:
+            ms, ns = self.mass_within(centre, [c.core_radius])
+            mass, count = float(ms[0]), int(ns[0])
+        return CoreResult(k=c.k, used=c.used, densest=c.densest, rho_max=c.rho_max, centre=centre, core_radius=c.core_radius,
+                          rho_sum=c.rho_sum, rho2_sum=c.rho2_sum, core_mass=mass, core_count=count)
 
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
