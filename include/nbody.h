@@ -1013,6 +1013,55 @@ NBODY_AMD_API int nbody_neighbours_at_f64(nbody_ctx *ctx, const double *pos, siz
 NBODY_AMD_API int nbody_get_density_f64(nbody_ctx *ctx, int32_t k, double *rho, double *rk2);
 NBODY_AMD_API int nbody_density_centre_f64(nbody_ctx *ctx, int32_t k, nbody_core *out);
 
+/* The fp64 radial census (build-defined: the reference has none): the bodies in radial order about a centre — usually the density centre
+ * above —, the cumulative mass in that order, and the LAGRANGIAN RADII read from it: the distance of the body at which the cumulative
+ * mass reaches a given fraction of the total, the half-mass radius (f = 0.5) among them.  One sort on the device (eight stable radix
+ * passes on the bit patterns of d2) instead of a bisection with nbody_mass_within or a host argsort of the whole state.  On the contexts
+ * that answer nbody_get_nearest_f64; every other kind refuses with that call's refusals.  Every line below is reproducible in numpy.
+ *
+ * d2.  dx = x - centre[0] (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz, contraction off: nbody_mass_within's expression in every
+ *   operation.  So for any r the count of nbody_mass_within(centre, r) equals the number of sorted d2 <= r*r, and a row's r2 compares
+ *   with that call's threshold exactly.
+ * Order.  Ascending in lexicographic (d2, index): the lowest index wins every tie; coincident and zero-mass bodies count.  The finite
+ *   d2 come first, then d2 == +inf, then NaN, each group in index order; *n_finite is the number of finite d2.  (The device sorts
+ *   key = isnan(d2) ? ~0 : bits(d2): d2 is never negative and never -0, so the bit pattern orders as the value does.)  d2[p] is the
+ *   sorted value; a NaN's payload is unspecified.  The order is total, so the answer is unique — np.argsort(d2, kind="stable") on the
+ *   finite part — and does not depend on how it was sorted.
+ * Cumulative mass — a function of the sorted masses and n_total ALONE: the grid, the device and the run never change its bits.  With
+ *   w_p = the raw mass of order[p] where its d2 is finite, else +0.0, in blocks of 256 consecutive positions (p = 256 b + t; the last
+ *   block padded with +0.0), every + one correctly rounded fp64 addition:
+ *     loc[b][t] = ((w_0 + w_1) + ...) + w_t             left to right inside block b
+ *     off[0] = 0.0;   off[b + 1] = off[b] + loc[b][255]
+ *     mass_cum[p] = off[b] + loc[b][t]
+ *   (numpy: loc = np.cumsum(w.reshape(-1, 256), axis=1); off = np.cumsum(np.concatenate(([0.0], loc[:-1, -1]))); off[:, None] + loc.)
+ *   It is non-decreasing for non-negative masses.  total_mass = mass_cum[n_total - 1].
+ * Selection.  For each fraction f (finite, 0 < f <= 1): target = f * total_mass (one multiply); p = the FIRST position with
+ *   mass_cum[p] >= target, searched linearly, so that negative masses still have an answer; the row is (f, d2[p], sqrt(d2[p]) correctly
+ *   rounded, mass_cum[p], order[p], p + 1).  No position qualifies unless total_mass > 0 — not when it is <= 0 or NaN, so not when no d2
+ *   is finite —: the row is then (f, NaN, NaN, NaN, -1, 0) and the call still returns NBODY_OK.  A row depends neither on the other
+ *   fractions nor on their order.  f = 1 selects the last position that adds mass.
+ *
+ * nbody_radial_order_f64: order, d2, mass_cum: [n_total] each; n_finite: one value.  Each output may be NULL, not all four.
+ * nbody_lagrange_radii_f64: k rows for k fractions, 1 <= k <= NBODY_LAGRANGE_MAX; total_mass may be NULL.
+ * NULL centre, fractions or rows, a centre that is not finite, k out of range, a fraction outside (0, 1]: NBODY_ERR_INVALID.  No
+ * particles set: NBODY_ERR_STATE.  Both calls read the live buffers and synchronise, change nothing a getter shows, and leave both
+ * Hermite caches, the fp64 tracers and any block session of either order alone; tracers are never listed.  This is no pair pass: it is
+ * counted neither under NBODY_KERNEL_FORCES nor under NBODY_KERNEL_UPDATE, as nbody_get_moments is not.
+ */
+#define NBODY_LAGRANGE_MAX 64
+typedef struct nbody_lagrange {   /* 40 bytes, one row per fraction */
+  double fraction;        /* echoed */
+  double r2;              /* d2 of the selected body: exact, compares with nbody_mass_within's threshold */
+  double radius;          /* sqrt(r2), correctly rounded */
+  double mass;            /* mass_cum at the selected position */
+  int32_t body;           /* order[p]; -1: none */
+  int32_t count;          /* p + 1; 0: none */
+} nbody_lagrange;
+NBODY_AMD_API int nbody_radial_order_f64(nbody_ctx *ctx, const double centre[3], int32_t *order, double *d2, double *mass_cum,
+                                         int32_t *n_finite);
+NBODY_AMD_API int nbody_lagrange_radii_f64(nbody_ctx *ctx, const double centre[3], const double *fractions, int32_t k,
+                                           nbody_lagrange *rows, double *total_mass);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 
@@ -1082,7 +1131,7 @@ NBODY_AMD_API int nbody_energy(nbody_ctx *ctx, double *ke, double *pe);
  *   the same fixed order).  d2 is computed in fp64 with contraction off: dx = (double)x - centre[0] (dy, dz alike), d2 = (dx*dx + dy*dy)
  *   + dz*dz; the threshold is one fp64 multiply.  Membership is therefore reproducible in plain C or numpy, and the counts are exact.
  *   A radius' results depend neither on the other radii nor on their order.  Either output may be NULL, not both.  One pass over the
- *   positions answers all k radii; Lagrangian radii (a selection) stay with the caller — 64 radii a call make that a few calls.
+ *   positions answers all k radii; Lagrangian radii (a selection) are nbody_lagrange_radii_f64's on fp64 contexts, with this d2.
  *   Slices, multi-device contexts (counts and masses add in part order), precisions, tracers and side effects: as nbody_get_moments.
  *   NULL centre / radii, k outside 1 .. 64, a negative or non-finite radius: NBODY_ERR_INVALID.
  */

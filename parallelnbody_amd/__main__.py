@@ -11,6 +11,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6-block --levels 12 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --core-every 5 --core-k 6       # density centre and core radius
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --lagrange-every 5 --lagrange-fractions 0.1,0.5,0.9   # Lagrangian radii
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -23,6 +24,7 @@ import time
 import numpy as np
 
 from . import NBodyEngine, ic_plummer, ic_reference_box
+from .engine import LAGRANGE_FRACTIONS
 
 
 TRJ_MAGIC = b"NBDYTRJ1"
@@ -79,6 +81,13 @@ def main(argv=None):
                          "only: one neighbour pass over all pairs and two O(N) reductions on the device; Casertano & Hut's local "
                          "densities in NBODY6's convention)")
     ap.add_argument("--core-k", type=int, default=6, help="--core-every: the neighbour that sets a body's density sphere, 2 .. 8 (default 6)")
+    ap.add_argument("--lagrange-every", type=int, default=0,
+                    help="print the Lagrangian radii about the density centre every K frames (--precision f64 only: the neighbour pass "
+                         "of --core-every for the centre — --core-k is shared —, then one sort by distance and a cumulative mass on the "
+                         "device)")
+    ap.add_argument("--lagrange-fractions", default=None,
+                    help="--lagrange-every: the mass fractions, f,f,... each in (0, 1], at most 64 (default "
+                         "0.01,0.02,0.05,0.1,0.2,0.3,0.5,0.7,0.9)")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -106,6 +115,22 @@ def main(argv=None):
         ap.error("--core-every needs --precision f64: the neighbour census runs on fp64 contexts only")
     if a.core_every > 0 and not 2 <= a.core_k <= 8:
         ap.error("--core-k must be 2 .. 8")
+    if a.lagrange_every < 0:
+        ap.error("--lagrange-every must be >= 0")
+    if a.lagrange_every > 0 and a.precision != "f64":
+        ap.error("--lagrange-every needs --precision f64: the radial census runs on fp64 contexts only")
+    if a.lagrange_every > 0 and not 2 <= a.core_k <= 8:
+        ap.error("--core-k must be 2 .. 8")
+    if a.lagrange_fractions is not None and a.lagrange_every == 0:
+        ap.error("--lagrange-fractions belongs to --lagrange-every")
+    fractions = LAGRANGE_FRACTIONS
+    if a.lagrange_fractions is not None:
+        try:
+            fractions = tuple(float(f) for f in a.lagrange_fractions.split(","))
+        except ValueError:
+            fractions = ()
+        if not 1 <= len(fractions) <= 64 or not all(0.0 < f <= 1.0 for f in fractions):
+            ap.error("--lagrange-fractions must be 1 .. 64 numbers f,f,... each in (0, 1]")
     block6 = a.integrator == "hermite6-block"                        # the same demands and exclusions as hermite-block
     block = a.integrator == "hermite-block" or block6
     hermite = a.integrator == "hermite" or block
@@ -175,7 +200,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -198,6 +223,13 @@ def main(argv=None):
                 print(json.dumps({"frame": frame, "core": {"k": c.k, "centre": [float(x) for x in c.centre], "core_radius": c.core_radius,
                                                            "densest": c.densest, "rho_max": c.rho_max, "used": c.used,
                                                            "core_mass": c.core_mass, "core_count": c.core_count}}), flush=True)
+            if a.lagrange_every > 0 and frame % a.lagrange_every == 0:
+                g = e.lagrange_f64(fractions, k=a.core_k)
+                print(json.dumps({"frame": frame, "lagrange": {"centre": [float(x) for x in g.centre], "total_mass": g.total_mass,
+                                                               "fractions": [float(f) for f in g.fraction],
+                                                               "radii": [float(r) for r in g.radius],
+                                                               "bodies": [int(b) for b in g.body],
+                                                               "counts": [int(c) for c in g.count]}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

@@ -126,8 +126,21 @@ class Core(ctypes.Structure):
     ]
 
 
+class Lagrange(ctypes.Structure):
+    """struct nbody_lagrange (include/nbody.h): one row of nbody_lagrange_radii_f64, 40 bytes."""
+    _fields_ = [
+        ("fraction", ctypes.c_double),
+        ("r2", ctypes.c_double),
+        ("radius", ctypes.c_double),
+        ("mass", ctypes.c_double),
+        ("body", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+    ]
+
+
 MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
 NEIGHBOURS_MAX = 8        # NBODY_NEIGHBOURS_MAX: the longest list nbody_get_neighbours_f64 answers
+LAGRANGE_MAX = 64         # NBODY_LAGRANGE_MAX: fractions one nbody_lagrange_radii_f64 call answers
 
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 DRAW_POINT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
@@ -239,6 +252,8 @@ def lib():
     sig("nbody_neighbours_at_f64", c_int, vp, vp, sz, c_i32, c_i32, vp, vp)
     sig("nbody_get_density_f64", c_int, vp, c_i32, vp, vp)
     sig("nbody_density_centre_f64", c_int, vp, c_i32, ctypes.POINTER(Core))
+    sig("nbody_radial_order_f64", c_int, vp, dp, vp, vp, vp, ctypes.POINTER(c_i32))
+    sig("nbody_lagrange_radii_f64", c_int, vp, dp, dp, c_i32, ctypes.POINTER(Lagrange), dp)
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

@@ -557,5 +557,17 @@ template <bool HOP, bool SOFT, bool BODY>
 __global__ __launch_bounds__(kB) void bh_tidal_walk_kernel(SmallTree T, const float4 *__restrict__ pts, double *__restrict__ t64,
                                                            float *__restrict__ tf, int m, double G, float eps2);
 
+// The launch rule of bh_radix_pass_kernel, for every host that launches it (bh_create, launch_radial_f64): its workgroups spin on earlier
+// tiles' look-back words, so a pass takes min(tiles, *resident) workgroups — all of them on the device at once — and never more: a
+// larger grid can wait for a workgroup that has no place to start.  *resident = what the current device holds of that kernel.
+inline hipError_t radix_pass_resident(int *resident) {
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bh_radix_pass_kernel, kRxT, 0)) return e;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+  *resident = per_cu * cus > 1 ? per_cu * cus : 1;
+  return hipSuccess;
+}
+
 }  // namespace bh
 }  // namespace nbody

@@ -186,11 +186,7 @@ static hipError_t bh_alloc_large(BhState *b) {
     BH_TRY(hipMalloc(&b->slice_hist, sizeof(unsigned int) * kRxSlices * kRxHists * kRxBins));
     b->rx_desc_bytes = sizeof(unsigned int) * tiles * kRxHists * kRxBins;
     BH_TRY(hipMalloc(&b->rx_desc, b->rx_desc_bytes));
-    int per_cu = 0, dev = 0, cus = 0;
-    BH_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bh_radix_pass_kernel, kRxT, 0));
-    BH_TRY(hipGetDevice(&dev));
-    BH_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    b->rx_resident = std::max(1, per_cu * cus);
+    BH_TRY(radix_pass_resident(&b->rx_resident));
   }
   b->nb = (n + kWarmMu - 1) / kWarmMu;
   BH_TRY(hipMalloc(&b->slot_hi, sizeof(unsigned long long) * (size_t)b->nb * kWarmCap));

@@ -4,6 +4,8 @@
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "capi_common.h"
@@ -978,6 +980,44 @@ int tracers_timescale(nbody_ctx *c, const char *who, double *t_min, int32_t *tra
   return scale_out<O>(c, tracer_view<O>(c), t_min, tracer, kind);
 }
 
+// ---- the fp64 radial census (kernels_radial64.hip) ----
+static_assert(sizeof(nbody_lagrange) == 40 && nbody::kRadialFractionsMax == NBODY_LAGRANGE_MAX, "include/nbody.h and kernels.h agree");
+
+// The order about `centre`, the cumulative mass in it and, k > 0, the rows of k fractions, queued on the stream from the LIVE positions
+// and left in the staging area on the device: *W says where.  Not a pair pass: no kernel timer counts it (as nbody_get_moments').
+// NBODY_RADIAL_PHASES=1 (read at every call; tools/radial_f64_measure.py): event pairs round the four phases, waited for and printed
+// to stderr.
+int radial64_run(nbody_ctx *c, const double centre[3], const double *fractions, int k, nbody::Radial64Work *W) {
+  *W = nbody::radial64_work(c->p.n_total);
+  if (int rc = ensure_stage(c, W->bytes)) return rc;
+  if (c->radial_resident == 0) HIP_TRY(c, nbody::radial64_resident(&c->radial_resident));
+  nbody::Radial64Launch L;
+  L.posm = c->posm; L.n_total = c->p.n_total;
+  L.centre[0] = centre[0]; L.centre[1] = centre[1]; L.centre[2] = centre[2];
+  L.fractions = fractions; L.k = k; L.resident = c->radial_resident; L.work = c->d_stage;
+  const char *env = getenv("NBODY_RADIAL_PHASES");
+  if (!(env && env[0] == '1')) {
+    HIP_TRY(c, nbody::launch_radial_f64(L, c->stream));
+    return NBODY_OK;
+  }
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipError_t err = hipSuccess;
+  for (int q = 0; q < 5 && err == hipSuccess; ++q) err = hipEventCreate(&ev[q]);
+  L.events = ev;
+  if (err == hipSuccess) err = nbody::launch_radial_f64(L, c->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+  float ms[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4 && err == hipSuccess; ++q) err = hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]);
+  for (int q = 0; q < 5; ++q) if (ev[q]) (void)hipEventDestroy(ev[q]);
+  HIP_TRY(c, err);
+  fprintf(stderr, "radial_f64 phases: n %d k %d keys %.4f sort %.4f scan %.4f select %.4f ms\n", c->p.n_total, k, ms[0], ms[1], ms[2], ms[3]);
+  return NBODY_OK;
+}
+
+bool radial64_centre_ok(const double centre[3]) {
+  return centre && std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1274,6 +1314,52 @@ int nbody_density_centre_f64(nbody_ctx *c, int32_t k, nbody_core *out) {
   out->rho_max = r[5];
   out->centre[0] = r[1]; out->centre[1] = r[2]; out->centre[2] = r[3];
   out->core_radius = r[8]; out->rho_sum = r[0]; out->rho2_sum = r[7];
+  return NBODY_OK;
+}
+
+int nbody_radial_order_f64(nbody_ctx *c, const double centre[3], int32_t *order, double *d2, double *mass_cum, int32_t *n_finite) {
+  const char *who = "nbody_radial_order_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!radial64_centre_ok(centre)) return fail(c, NBODY_ERR_INVALID, "%s: null centre or a centre that is not finite", who);
+  if (!order && !d2 && !mass_cum && !n_finite) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  nbody::Radial64Work W;
+  if ((rc = radial64_run(c, centre, nullptr, 0, &W))) return rc;
+  const size_t n = (size_t)c->p.n_total;
+  const char *d = (const char *)c->d_stage;
+  char *h = (char *)c->h_stage;
+  if (order) HIP_TRY(c, hipMemcpyAsync(h + W.idx[0], d + W.idx[0], n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (d2) HIP_TRY(c, hipMemcpyAsync(h + W.key[0], d + W.key[0], n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (mass_cum) HIP_TRY(c, hipMemcpyAsync(h + W.cum, d + W.cum, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (n_finite) HIP_TRY(c, hipMemcpyAsync(h + W.n_finite, d + W.n_finite, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (order) memcpy(order, h + W.idx[0], n * 4);
+  if (d2) memcpy(d2, h + W.key[0], n * 8);                         // (the sorted keys are the bit patterns of d2; a NaN reads all ones)
+  if (mass_cum) memcpy(mass_cum, h + W.cum, n * 8);
+  if (n_finite) memcpy(n_finite, h + W.n_finite, 4);
+  return NBODY_OK;
+}
+
+int nbody_lagrange_radii_f64(nbody_ctx *c, const double centre[3], const double *fractions, int32_t k, nbody_lagrange *rows,
+                             double *total_mass) {
+  const char *who = "nbody_lagrange_radii_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!radial64_centre_ok(centre)) return fail(c, NBODY_ERR_INVALID, "%s: null centre or a centre that is not finite", who);
+  if (!fractions || !rows) return fail(c, NBODY_ERR_INVALID, "%s: null fractions or rows", who);
+  if (k < 1 || k > NBODY_LAGRANGE_MAX) return fail(c, NBODY_ERR_INVALID, "%s: k = %d outside 1 .. %d", who, k, NBODY_LAGRANGE_MAX);
+  for (int q = 0; q < k; ++q)
+    if (!(fractions[q] > 0.0 && fractions[q] <= 1.0))              // (a NaN fails both)
+      return fail(c, NBODY_ERR_INVALID, "%s: fraction %d is outside (0, 1]", who, q);
+  nbody::Radial64Work W;
+  if ((rc = radial64_run(c, centre, fractions, k, &W))) return rc;
+  const char *d = (const char *)c->d_stage;
+  char *h = (char *)c->h_stage;
+  HIP_TRY(c, hipMemcpyAsync(h + W.rows, d + W.rows, (size_t)k * sizeof(nbody_lagrange), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h + W.total, d + W.total, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(rows, h + W.rows, (size_t)k * sizeof(nbody_lagrange));
+  if (total_mass) memcpy(total_mass, h + W.total, 8);
   return NBODY_OK;
 }
 

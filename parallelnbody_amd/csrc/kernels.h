@@ -418,6 +418,38 @@ hipError_t launch_neighbours_f64(const Neighbours64Launch &L, hipStream_t s);
 // 8 * energy_fast_slots(n) doubles.
 hipError_t launch_density_centre(const void *posm, const double *rho, int n, double *partials, double *out, hipStream_t s);
 
+// The radial census of an fp64 state about a centre — kernels_radial64.hip: the bodies in ascending (d2, index) order with d2 in
+// nbody_mass_within's convention (finite d2, then +inf, then NaN, each group in index order), the cumulative mass in that order in blocks
+// of 256 (include/nbody.h: a function of the sorted masses and n alone), and for k fractions f of the total mass the first position whose
+// cumulative mass reaches f * total.  The order comes from the Barnes-Hut radix passes (kernels_bh_sort.hip) on the bit patterns of d2.
+// Everything lives in one work area of radial64_work(n).bytes bytes; the offsets of the results in it (bytes, multiples of 256):
+constexpr int kRadialFractionsMax = 64;   // == NBODY_LAGRANGE_MAX
+struct Radial64Work {
+  size_t key[2], idx[2];   // the passes' two key and two index arrays; behind the launch key[0] holds the sorted keys — read as doubles the
+                           // sorted d2, a NaN as all ones — and idx[0] the order
+  size_t cum;              // [n] doubles: mass_cum
+  size_t part_hist, slice_hist, desc, status, blk_sum, off, fin_part, sel_part;
+  size_t rows;             // [k] nbody_lagrange
+  size_t total;            // one double: mass_cum[n - 1]
+  size_t n_finite;         // one int
+  size_t clear_bytes;      // desc .. status, cleared before the first pass
+  size_t bytes;
+};
+Radial64Work radial64_work(int n);
+// workgroups of the radix pass the current device holds at once: a pass is never launched with more (its workgroups wait for each other)
+hipError_t radial64_resident(int *resident);
+struct Radial64Launch {
+  const void *posm = nullptr;        // [n_total] double4: x, y, z, m
+  int n_total = 0;
+  double centre[3] = {0.0, 0.0, 0.0};
+  const double *fractions = nullptr; // [k], host; k == 0: the order and the cumulative mass alone
+  int k = 0;
+  int resident = 0;                  // radial64_resident's answer
+  void *work = nullptr;              // device, radial64_work(n_total).bytes
+  const hipEvent_t *events = nullptr;   // five events recorded ahead of the keys, the sort, the scan, the selection and behind it; or null
+};
+hipError_t launch_radial_f64(const Radial64Launch &L, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

@@ -117,6 +117,62 @@ CoreResult = collections.namedtuple("CoreResult", ("k", "used", "densest", "rho_
                                                    "core_mass", "core_count"))
 
 
+# NBodyEngine.lagrange_f64(): the centre used (float64[3]), the total mass, then one entry per fraction — the columns of struct
+# nbody_lagrange: fraction, r2, radius, mass (float64), body, count (int32)
+LagrangeResult = collections.namedtuple("LagrangeResult", ("centre", "total_mass", "fraction", "r2", "radius", "mass", "body", "count"))
+
+# NBodyEngine.radial_profile_f64(): per shell between consecutive Lagrangian positions (radial_profile())
+RadialProfileResult = collections.namedtuple("RadialProfileResult", ("centre", "total_mass", "fraction", "count", "mass", "r_in", "r_out",
+                                                                     "density", "v_r", "sigma_r2", "sigma_t2", "beta"))
+
+LAGRANGE_FRACTIONS = (0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5, 0.7, 0.9)
+
+
+def radial_profile(order, posm, vel, centre, counts, radii, vcentre=None):
+    """The shells of a radial order, in numpy: count, mass, r_in, r_out, density, v_r, sigma_r2, sigma_t2, beta — float64 arrays with
+    one entry per shell (count int64).  order: the bodies in radial order about `centre`; posm, vel: [n, >= 4] and [n, >= 3] float64
+    in body order; counts: ascending positions c_0 <= c_1 <= ... (a Lagrangian row's `count`), radii: the rows' `radius`.  Shell s
+    holds the sorted positions c_(s-1) <= p < c_s (c_(-1) = 0) — its last body is the one the s-th row selected — and lies between
+    r_in = radii[s-1] (0 for s = 0) and r_out = radii[s].  With m_i the shell's masses, M = sum m_i, r_i = x_i - centre,
+    e_i = r_i / |r_i| (0 where |r_i| = 0), u_i = v_i - vc, vc = `vcentre` or, None, the shell's own (sum m_i v_i) / M:
+        density  = M / ((4 pi / 3) (r_out^3 - r_in^3))
+        v_r      = (sum m_i (u_i . e_i)) / M                            the mass-weighted mean radial velocity
+        sigma_r2 = (sum m_i ((u_i . e_i) - v_r)^2) / M
+        sigma_t2 = (sum m_i (|u_i|^2 - (u_i . e_i)^2)) / M              both tangential components together
+        beta     = 1 - sigma_t2 / (2 sigma_r2)                         0: isotropic, 1: radial, -inf: circular orbits
+    A shell without mass has mass 0 and NaN for what divides by M."""
+    order = np.asarray(order, np.int64)
+    posm, vel = np.asarray(posm, np.float64), np.asarray(vel, np.float64)
+    centre = np.asarray(centre, np.float64).reshape(3)
+    counts, radii = np.asarray(counts, np.int64), np.asarray(radii, np.float64)
+    k = counts.shape[0]
+    out = {f: np.full(k, np.nan) for f in ("mass", "r_in", "r_out", "density", "v_r", "sigma_r2", "sigma_t2", "beta")}
+    count = np.zeros(k, np.int64)
+    lo, r_in = 0, 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for s in range(k):
+            hi = max(int(counts[s]), lo)
+            ids = order[lo:hi]
+            m = posm[ids, 3]
+            M = np.float64(m.sum())                               # (a numpy scalar: a shell without mass divides to NaN)
+            r = posm[ids, :3] - centre
+            d = np.linalg.norm(r, axis=1)
+            e = np.where(d[:, None] > 0.0, r / d[:, None], 0.0)
+            vc = np.asarray(vcentre, np.float64).reshape(3) if vcentre is not None else (m[:, None] * vel[ids, :3]).sum(axis=0) / M
+            u = vel[ids, :3] - vc
+            ur = (u * e).sum(axis=1)
+            v_r = (m * ur).sum() / M
+            count[s] = hi - lo
+            out["mass"][s], out["r_in"][s], out["r_out"][s] = M, r_in, radii[s]
+            out["density"][s] = M / ((4.0 * np.pi / 3.0) * (radii[s] ** 3 - r_in ** 3))
+            out["v_r"][s] = v_r
+            out["sigma_r2"][s] = (m * (ur - v_r) ** 2).sum() / M
+            out["sigma_t2"][s] = (m * ((u * u).sum(axis=1) - ur * ur)).sum() / M
+            out["beta"][s] = 1.0 - out["sigma_t2"][s] / (2.0 * out["sigma_r2"][s])
+            lo, r_in = hi, radii[s]
+    return count, out
+
+
 def moments_result(count, sums):
     """MomentsResult from the bodies' count and the raw sums (a mapping of MOMENT_FIELDS) — also of sums added over ranks or slices."""
     raw = {k: (float(sums[k]) if k in ("mass", "kinetic", "virial") else np.array(sums[k], np.float64)) for k in MOMENT_FIELDS}
@@ -841,6 +897,66 @@ class NBodyEngine:
             mass, count = float(ms[0]), int(ns[0])
         return CoreResult(k=c.k, used=c.used, densest=c.densest, rho_max=c.rho_max, centre=centre, core_radius=c.core_radius,
                           rho_sum=c.rho_sum, rho2_sum=c.rho2_sum, core_mass=mass, core_count=count)
+
+    # -- the fp64 radial census: the bodies in radial order, the cumulative mass, Lagrangian radii (fp64 contexts) --
+    @staticmethod
+    def _centre(centre, who):
+        c = np.ascontiguousarray(np.asarray(centre, np.float64).reshape(-1))
+        if c.shape != (3,):
+            raise ValueError(f"{who}: centre must be 3 numbers")
+        return c
+
+    def radial_order_f64(self, centre):
+        """(order, d2, mass_cum, n_finite): the bodies in radial order about `centre` (nbody_radial_order_f64): int32[n_total],
+        float64[n_total], float64[n_total] and an int.  d2 = (dx*dx + dy*dy) + dz*dz without contraction — mass_within()'s; the order
+        is ascending in lexicographic (d2, index): np.argsort(d2, kind="stable"), finite d2 first, then +inf, then NaN (n_finite: the
+        finite ones).  mass_cum adds the raw masses in that order in blocks of 256, left to right inside a block, then the blocks'
+        offsets in order (include/nbody.h: numpy reproduces every bit); a non-finite d2 adds nothing.  precision="f64" contexts on one
+        device owning all bodies; everything else: ERR_UNSUPPORTED.  A sort on the device, no pair pass; changes nothing a getter shows
+        and leaves the Hermite caches, the fp64 tracers and any block session alone."""
+        c = self._centre(centre, "radial_order_f64")
+        order, d2, cum = np.empty(self.n_total, np.int32), np.empty(self.n_total, np.float64), np.empty(self.n_total, np.float64)
+        nf = ctypes.c_int32()
+        self._check(self._L.nbody_radial_order_f64(self._h, _dp(c), order.ctypes.data, d2.ctypes.data, cum.ctypes.data, ctypes.byref(nf)))
+        return order, d2, cum, nf.value
+
+    def _default_centre(self, k):
+        core = self.core_f64(k)
+        return core.centre if core.used > 0 else np.array(self.moments().com, np.float64)
+
+    def lagrange_f64(self, fractions=LAGRANGE_FRACTIONS, centre=None, k=6):
+        """The Lagrangian radii about `centre` (nbody_lagrange_radii_f64): a LagrangeResult — the centre used, total_mass and, per
+        fraction f (each in (0, 1], at most 64, any order), the row (fraction, r2, radius, mass, body, count): the FIRST position p of
+        radial_order_f64() with mass_cum[p] >= f * total_mass, r2 = d2[p] (exact: compares with mass_within()'s threshold), radius =
+        sqrt(r2), mass = mass_cum[p], body = order[p], count = p + 1.  Where total_mass is not > 0: (f, NaN, NaN, NaN, -1, 0).
+        centre=None: core_f64(k).centre, or — when that has used == 0 — the centre of mass from moments().  Contexts and side effects
+        (none) as radial_order_f64()."""
+        f = np.ascontiguousarray(np.asarray(fractions, np.float64).reshape(-1))
+        c = self._default_centre(k) if centre is None else self._centre(centre, "lagrange_f64")
+        rows = (_lib.Lagrange * min(max(f.shape[0], 1), _lib.LAGRANGE_MAX))()
+        total = ctypes.c_double()
+        self._check(self._L.nbody_lagrange_radii_f64(self._h, _dp(c), _dp(f), f.shape[0], rows, ctypes.byref(total)))
+        a = np.frombuffer(rows, np.dtype([("fraction", "<f8"), ("r2", "<f8"), ("radius", "<f8"), ("mass", "<f8"), ("body", "<i4"),
+                                          ("count", "<i4")]))
+        return LagrangeResult(centre=c, total_mass=total.value, **{n: a[n].copy() for n in a.dtype.names})
+
+    def radial_profile_f64(self, fractions=LAGRANGE_FRACTIONS, centre=None, vcentre=None, k=6):
+        """The shells between consecutive Lagrangian positions: a RadialProfileResult with, per fraction (strictly increasing), the
+        shell that ENDS at its row — count, mass, r_in, r_out, density, v_r, sigma_r2, sigma_t2, beta; the formulas are
+        radial_profile()'s, in numpy on radial_order_f64() and state(np.float64):
+            density = mass / ((4 pi / 3) (r_out^3 - r_in^3));  v_r = <u . e>;  sigma_r2 = <(u . e - v_r)^2>;
+            sigma_t2 = <|u|^2 - (u . e)^2>;  beta = 1 - sigma_t2 / (2 sigma_r2)
+        with <.> the mass-weighted mean over the shell, e the unit vector from the centre, u = v - vcentre; vcentre=None: the shell's
+        own mass-weighted mean velocity.  centre=None as lagrange_f64().  Python only; one sort and one state read."""
+        f = np.asarray(fractions, np.float64).reshape(-1)
+        if f.shape[0] > 1 and not np.all(np.diff(f) > 0.0):
+            raise ValueError("radial_profile_f64: fractions must be strictly increasing")
+        c = self._default_centre(k) if centre is None else self._centre(centre, "radial_profile_f64")
+        lag = self.lagrange_f64(f, c)
+        order, _, _, _ = self.radial_order_f64(c)
+        posm, vel, _ = self.state(np.float64)
+        count, cols = radial_profile(order, posm, vel, c, lag.count, lag.radius, vcentre)
+        return RadialProfileResult(centre=c, total_mass=lag.total_mass, fraction=lag.fraction, count=count, **cols)
 
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
