@@ -38,7 +38,8 @@ enum {
   NBODY_ERR_HIP = -3,         /* a HIP runtime call failed; see nbody_last_error */
   NBODY_ERR_STATE = -4,       /* call made in the wrong state (e.g. no particles set) */
   NBODY_ERR_NOMEM = -5,
-  NBODY_ERR_UNSUPPORTED = -6
+  NBODY_ERR_UNSUPPORTED = -6,
+  NBODY_ERR_INTERNAL = -7     /* a bound the library proves was passed (nbody_get_groups_f64: more rounds than bodies) */
 };
 
 /* Arithmetic of the force accumulation. */
@@ -1061,6 +1062,51 @@ NBODY_AMD_API int nbody_radial_order_f64(nbody_ctx *ctx, const double centre[3],
                                          int32_t *n_finite);
 NBODY_AMD_API int nbody_lagrange_radii_f64(nbody_ctx *ctx, const double centre[3], const double *fractions, int32_t k,
                                            nbody_lagrange *rows, double *total_mass);
+
+/* The fp64 group census (build-defined: the reference has none): how many bodies lie within a distance of each body or point — the
+ * radius counts —, and WHICH BODIES BELONG TOGETHER: the connected components of the graph "closer than a linking length", which is
+ * friends-of-friends (FoF) — the multiples around the binaries of the pair census, the clumps of a fractal or merging initial condition,
+ * a remnant against its tail.  On the contexts that answer nbody_get_nearest_f64 (fp64 state, one device, all bodies, no open step);
+ * every other kind refuses with that call's refusals.  theta and eps play no part: nothing is softened.  The calls read the live
+ * positions.  Every line below is reproducible in numpy, bit for bit; nothing but `rounds` depends on how it was computed.
+ *
+ * Distance.  dx = x_j - x_i (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz, contraction off: nbody_mass_within's expression, not the pair
+ *   census's fma form.  The threshold is r2 = radius * radius, one fp64 multiply.  d2_ij == d2_ji in every bit (the differences are
+ *   exact negations), so the graph is undirected by construction, and nbody_radius_counts_at_f64 at one point c equals the count of
+ *   nbody_mass_within(c, radius) exactly.  radius must be finite and >= 0 and r2 finite, else NBODY_ERR_INVALID with nothing written;
+ *   radius == 0 links coincident bodies only.
+ * Link.  Bodies i != j are linked iff d2 <= r2.  A NaN coordinate gives a NaN d2 and no link: that body is a group of one.  A +inf d2
+ *   never passes a finite r2.  A zero-mass body links like any other.
+ * Per body.  degree[i] = the number of j != i linked to i;  label[i] = the lowest index among the bodies of i's connected component;
+ *   members[i] = the size of that component.
+ * Summary.  groups = the number of i with label[i] == i;  multiples = those with members >= 2;  largest = the label of the group with
+ *   the most members, the lowest label among ties;  largest_members = its size;  links = sum of degree / 2;  rounds = the N^2 passes
+ *   the device took: each round every body learns the smallest label among its linked bodies, the ROOT of its tree is hooked to it by an
+ *   integer minimum, and every tree is flattened; the first round that changes nothing is the last and is counted.  rounds <= n_total;
+ *   NBODY_ERR_INTERNAL beyond.
+ *
+ * nbody_get_radius_counts_f64: count[n_total] = degree, one pass.
+ * nbody_radius_counts_at_f64: count[n] for n points of three doubles, pos_stride (>= 24) bytes apart; NO body is dropped by index: a
+ *   point on a body counts that body.  n == 0: NBODY_OK.
+ * nbody_get_groups_f64: label, members, degree: [n_total] each; any output may be NULL, not all four.
+ * NULL count or points, n < 0, a stride < 24: NBODY_ERR_INVALID.  No particles set: NBODY_ERR_STATE.  The calls synchronise, change
+ * nothing a getter shows, and leave both Hermite caches, the fp64 tracers and any block session of either order alone; nothing is kept
+ * per context between calls.  Each N^2 pass counts once under NBODY_KERNEL_FORCES — one for a radius-count call, summary.rounds for a
+ * groups call —, nothing under NBODY_KERNEL_UPDATE.
+ */
+typedef struct nbody_groups {   /* 32 bytes */
+  int32_t groups;           /* connected components, singles included */
+  int32_t multiples;        /* those of two or more bodies */
+  int32_t largest;          /* the label of the group with the most members, the lowest label among ties */
+  int32_t largest_members;  /* its size */
+  int32_t rounds;           /* N^2 passes taken */
+  int32_t reserved;         /* 0 */
+  int64_t links;            /* linked pairs: sum of degree / 2 */
+} nbody_groups;
+NBODY_AMD_API int nbody_get_radius_counts_f64(nbody_ctx *ctx, double radius, int32_t *count);
+NBODY_AMD_API int nbody_radius_counts_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, double radius, int32_t *count);
+NBODY_AMD_API int nbody_get_groups_f64(nbody_ctx *ctx, double radius, int32_t *label, int32_t *members, int32_t *degree,
+                                       nbody_groups *summary);
 
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);

@@ -12,6 +12,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --integrator hermite6-block --levels 12 --eta 0.5 --dt 0.05 --steps 20 --energy-every 5
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --core-every 5 --core-k 6       # density centre and core radius
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --lagrange-every 5 --lagrange-fractions 0.1,0.5,0.9   # Lagrangian radii
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --groups-every 5 --linking-length 0.02   # friends-of-friends groups
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -88,6 +89,12 @@ def main(argv=None):
     ap.add_argument("--lagrange-fractions", default=None,
                     help="--lagrange-every: the mass fractions, f,f,... each in (0, 1], at most 64 (default "
                          "0.01,0.02,0.05,0.1,0.2,0.3,0.5,0.7,0.9)")
+    ap.add_argument("--groups-every", type=int, default=0,
+                    help="print the friends-of-friends groups at --linking-length every K frames: their number, the multiples, the "
+                         "largest group's label and size, and the links (--precision f64 only: a few passes over all pairs on the "
+                         "device, one per round of the group finder)")
+    ap.add_argument("--linking-length", type=float, default=None,
+                    help="--groups-every: bodies closer than this are linked, finite and >= 0")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -123,6 +130,16 @@ def main(argv=None):
         ap.error("--core-k must be 2 .. 8")
     if a.lagrange_fractions is not None and a.lagrange_every == 0:
         ap.error("--lagrange-fractions belongs to --lagrange-every")
+    if a.groups_every < 0:
+        ap.error("--groups-every must be >= 0")
+    if a.groups_every > 0 and a.precision != "f64":
+        ap.error("--groups-every needs --precision f64: the group census runs on fp64 contexts only")
+    if a.groups_every > 0 and a.linking_length is None:
+        ap.error("--groups-every needs --linking-length")
+    if a.linking_length is not None and a.groups_every == 0:
+        ap.error("--linking-length belongs to --groups-every")
+    if a.linking_length is not None and not (0.0 <= a.linking_length < float("inf")):
+        ap.error("--linking-length must be finite and >= 0")
     fractions = LAGRANGE_FRACTIONS
     if a.lagrange_fractions is not None:
         try:
@@ -200,7 +217,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.groups_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -230,6 +247,11 @@ def main(argv=None):
                                                                "radii": [float(r) for r in g.radius],
                                                                "bodies": [int(b) for b in g.body],
                                                                "counts": [int(c) for c in g.count]}}), flush=True)
+            if a.groups_every > 0 and frame % a.groups_every == 0:
+                g = e.groups_f64(a.linking_length).summary
+                print(json.dumps({"frame": frame, "groups": {"linking_length": a.linking_length, "groups": g.groups,
+                                                             "multiples": g.multiples, "largest": g.largest,
+                                                             "largest_members": g.largest_members, "links": g.links}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

@@ -14,6 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
+ERR_INTERNAL = -7
 PREC_F32, PREC_F32_KAHAN, PREC_F64 = 0, 1, 2
 BUF_POSM, BUF_VEL, BUF_ACC = 0, 1, 2
 KERNEL_FORCES, KERNEL_UPDATE = 0, 1
@@ -138,6 +139,19 @@ class Lagrange(ctypes.Structure):
     ]
 
 
+class Groups(ctypes.Structure):
+    """struct nbody_groups (include/nbody.h): the summary of nbody_get_groups_f64, 32 bytes."""
+    _fields_ = [
+        ("groups", ctypes.c_int32),
+        ("multiples", ctypes.c_int32),
+        ("largest", ctypes.c_int32),
+        ("largest_members", ctypes.c_int32),
+        ("rounds", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("links", ctypes.c_int64),
+    ]
+
+
 MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
 NEIGHBOURS_MAX = 8        # NBODY_NEIGHBOURS_MAX: the longest list nbody_get_neighbours_f64 answers
 LAGRANGE_MAX = 64         # NBODY_LAGRANGE_MAX: fractions one nbody_lagrange_radii_f64 call answers
@@ -254,6 +268,9 @@ def lib():
     sig("nbody_density_centre_f64", c_int, vp, c_i32, ctypes.POINTER(Core))
     sig("nbody_radial_order_f64", c_int, vp, dp, vp, vp, vp, ctypes.POINTER(c_i32))
     sig("nbody_lagrange_radii_f64", c_int, vp, dp, dp, c_i32, ctypes.POINTER(Lagrange), dp)
+    sig("nbody_get_radius_counts_f64", c_int, vp, c_d, vp)
+    sig("nbody_radius_counts_at_f64", c_int, vp, vp, sz, c_i32, c_d, vp)
+    sig("nbody_get_groups_f64", c_int, vp, c_d, vp, vp, vp, ctypes.POINTER(Groups))
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

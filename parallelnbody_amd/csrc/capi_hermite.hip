@@ -1,5 +1,5 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
-// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip) and neighbour census (kernels_neighbours64.hip).  Host C++ like capi.hip, whose helpers it shares
+// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip) and neighbour census (kernels_neighbours64.hip), the radial census (kernels_radial64.hip) and the group census (kernels_groups64.hip).  Host C++ like capi.hip, whose helpers it shares
 // (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
@@ -1018,6 +1018,32 @@ bool radial64_centre_ok(const double centre[3]) {
   return centre && std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]);
 }
 
+// ---- the fp64 group census (kernels_groups64.hip) ----
+static_assert(sizeof(nbody_groups) == 32, "include/nbody.h: 32 bytes");
+constexpr int kGroups64Width = 1;   // the float4 of a partial row: two int32, half a float4 unused
+
+// radius finite and >= 0, r2 = radius * radius (one fp64 multiply) finite
+int groups64_r2(nbody_ctx *c, const char *who, double radius, double *r2) {
+  *r2 = radius * radius;
+  if (std::isfinite(radius) && radius >= 0.0 && std::isfinite(*r2)) return NBODY_OK;
+  return fail(c, NBODY_ERR_INVALID, "%s: the radius must be finite and >= 0 and its square finite", who);
+}
+
+// one N^2 pass from the LIVE positions under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial
+// rows: parent == nullptr: count = the linked bodies per row — at m points (ppos: double4 each, device) or, ppos == nullptr, at the
+// bodies themselves with each left out by index —; else the bodies' minimum parent into mn and, first round, their degree into count
+int groups64_pass(nbody_ctx *c, double r2, const void *ppos, int m, const int *parent, bool first_round, int *mn, int *count) {
+  if (int rc = ensure_probe_part(c, m, kGroups64Width)) return rc;
+  if (int rc = points64_part_holds(c, m, kGroups64Width, parent ? "the fp64 groups pass" : "the fp64 radius-count pass")) return rc;
+  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
+    nbody::Groups64Launch L;
+    L.posm = c->posm; L.ppos = ppos; L.parent = parent; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
+    L.mn = mn; L.count = count; L.n_total = c->p.n_total; L.m = m; L.r2 = r2;
+    HIP_TRY(c, parent ? nbody::launch_groups_pass_f64(L, first_round, c->stream) : nbody::launch_radius_counts_f64(L, c->stream));
+    return NBODY_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1360,6 +1386,86 @@ int nbody_lagrange_radii_f64(nbody_ctx *c, const double centre[3], const double 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   memcpy(rows, h + W.rows, (size_t)k * sizeof(nbody_lagrange));
   if (total_mass) memcpy(total_mass, h + W.total, 8);
+  return NBODY_OK;
+}
+
+int nbody_get_radius_counts_f64(nbody_ctx *c, double radius, int32_t *count) {
+  const char *who = "nbody_get_radius_counts_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  double r2;
+  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
+  if (!count) return fail(c, NBODY_ERR_INVALID, "%s: null output", who);
+  const size_t n = (size_t)c->p.n_total;
+  if ((rc = ensure_stage(c, n * 4))) return rc;
+  if ((rc = groups64_pass(c, r2, nullptr, (int)n, nullptr, false, nullptr, (int *)c->d_stage))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(count, c->h_stage, n * 4);
+  return NBODY_OK;
+}
+
+int nbody_radius_counts_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double radius, int32_t *count) {
+  const char *who = "nbody_radius_counts_at_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  double r2;
+  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
+  if (n < 0 || !pos || pos_stride < 24 || !count) return fail(c, NBODY_ERR_INVALID, "%s: null points or output, n < 0, or a stride < 24", who);
+  if (n == 0) return NBODY_OK;
+  const size_t m = (size_t)n;                                      // the points as double4, behind them the counts
+  if ((rc = ensure_stage(c, m * 36))) return rc;
+  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
+  gather_double4(h, pos, pos_stride, m);
+  HIP_TRY(c, hipMemcpyAsync(d, h, m * 32, hipMemcpyHostToDevice, c->stream));
+  if ((rc = groups64_pass(c, r2, d, n, nullptr, false, nullptr, (int *)(d + 4 * m)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + 4 * m, d + 4 * m, m * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(count, h + 4 * m, m * 4);
+  return NBODY_OK;
+}
+
+// The rounds are driven from here: pass and fold, hook, compress, then a 4-byte read-back of `changed`.  The first round that changes
+// nothing is the last.  Every round but the last merges at least two components, so there are at most n of them.
+int nbody_get_groups_f64(nbody_ctx *c, double radius, int32_t *label, int32_t *members, int32_t *degree, nbody_groups *summary) {
+  const char *who = "nbody_get_groups_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  double r2;
+  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
+  if (!label && !members && !degree && !summary) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  const size_t n = (size_t)c->p.n_total;
+  // ints of the staging pair: label, members, degree (read back together), hooked, mn, size; then four 64-bit sums and `changed`
+  const size_t sums = (6 * n + 1) / 2 * 2, flag = sums + 8, ints = flag + 2;
+  if ((rc = ensure_stage(c, ints * 4))) return rc;
+  int *d = (int *)c->d_stage, *h = (int *)c->h_stage;
+  int *parent = d, *dmembers = d + n, *ddegree = d + 2 * n, *hooked = d + 3 * n, *mn = d + 4 * n, *size = d + 5 * n;
+  HIP_TRY(c, nbody::launch_groups_identity(parent, (int)n, c->stream));
+  size_t rounds = 0;
+  for (;;) {
+    if (rounds == n) return fail(c, NBODY_ERR_INTERNAL, "%s: no fixed point after %zu rounds of %zu bodies", who, rounds, n);
+    if ((rc = groups64_pass(c, r2, nullptr, (int)n, parent, rounds == 0, mn, ddegree))) return rc;
+    ++rounds;
+    HIP_TRY(c, nbody::launch_groups_merge(parent, mn, hooked, (int)n, d + flag, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h + flag, d + flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (h[flag] == 0) break;
+  }
+  HIP_TRY(c, nbody::launch_groups_members(parent, ddegree, (int)n, size, dmembers, (unsigned long long *)(d + sums), c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h, d, 3 * n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h + sums, d + sums, 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (label) memcpy(label, h, n * 4);
+  if (members) memcpy(members, h + n, n * 4);
+  if (degree) memcpy(degree, h + 2 * n, n * 4);
+  if (summary) {
+    unsigned long long s[4];
+    memcpy(s, h + sums, 32);
+    summary->groups = (int32_t)s[0]; summary->multiples = (int32_t)s[1];
+    summary->largest = (int32_t)(0x7fffffffull - (s[3] & 0xffffffffull)); summary->largest_members = (int32_t)(s[3] >> 32);
+    summary->rounds = (int32_t)rounds; summary->reserved = 0;
+    summary->links = (int64_t)(s[2] / 2);
+  }
   return NBODY_OK;
 }
 

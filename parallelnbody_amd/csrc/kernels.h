@@ -450,6 +450,38 @@ struct Radial64Launch {
 };
 hipError_t launch_radial_f64(const Radial64Launch &L, hipStream_t s);
 
+// The group census of an fp64 state, at the bodies or at m points that are not bodies — kernels_groups64.hip: a pass over
+// launch_nearest_f64's chunks and tiles that counts and takes an integer minimum where that one takes an argmin.  With d = x_j - x and
+// contraction off, d2 = (dx*dx + dy*dy) + dz*dz (nbody_mass_within's expression); row and body j are LINKED iff d2 <= r2 — a NaN d2 and a
+// +inf d2 never are.  ppos == nullptr: the rows are the bodies (m == n_total), each leaves itself out BY INDEX; else no body is dropped by
+// index.  The padding of a chunk's last tile is kept out by index; a zero-mass body links like any other.  A partial row is two int32
+// (minimum, count) in a width-1 slot — probe_slab_points(n_total, 1) —; the rows go in slabs of that many and are folded in chunk order.
+//   launch_radius_counts_f64:  count = the number of linked bodies per row; parent and mn are not read
+//   launch_groups_pass_f64:    the bodies only: mn[i] = min(parent[i], parent[j] over the linked j) and, first_round, count as above
+struct Groups64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
+  const int *parent = nullptr;  // [n_total]: every body's current parent label (the groups' pass)
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1), or nothing is launched
+  int *mn = nullptr;            // [m]: the smallest parent among the row's own and its linked bodies' (the groups' pass)
+  int *count = nullptr;         // [m]: the linked bodies
+  int n_total = 0, m = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
+  double r2 = 0.0;              // radius * radius: finite and >= 0, or nothing is launched
+};
+hipError_t launch_radius_counts_f64(const Groups64Launch &L, hipStream_t s);
+hipError_t launch_groups_pass_f64(const Groups64Launch &L, bool first_round, hipStream_t s);
+// The O(N) kernels of the groups, the connected components of the links.  parent[i] = i (identity); then per round, after a pass:
+// launch_groups_merge copies parent to `hooked`, lowers hooked[parent[i]] to mn[i] where mn[i] < parent[i] (integer atomicMin: the
+// result does not depend on the order), writes parent[i] = the fixed point of hooked from i (hooked is read-only meanwhile and never
+// ascends) and sets *changed to 1 where a parent changed, else 0.  Converged parents are the labels: the lowest index of each group.
+hipError_t launch_groups_identity(int *parent, int n, hipStream_t s);
+hipError_t launch_groups_merge(int *parent, const int *mn, int *hooked, int n, int *changed, hipStream_t s);
+// members[i] = the size of label[i]'s group (`size`: [n] work), and sum[4]: the groups, those of two or more, sum of degree, and
+// max over the groups of (size << 32 | 0x7fffffff - label) — integer atomics on cleared words, the same values whatever the order
+hipError_t launch_groups_members(const int *label, const int *degree, int n, int *size, int *members, unsigned long long *sum, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

@@ -125,7 +125,40 @@ LagrangeResult = collections.namedtuple("LagrangeResult", ("centre", "total_mass
 RadialProfileResult = collections.namedtuple("RadialProfileResult", ("centre", "total_mass", "fraction", "count", "mass", "r_in", "r_out",
                                                                      "density", "v_r", "sigma_r2", "sigma_t2", "beta"))
 
-LAGRANGE_FRACTIONS = (0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5, 0.7, 0.9)
+# NBodyEngine.groups_f64(): the fields of struct nbody_groups
+GroupsSummary = collections.namedtuple("GroupsSummary", ("groups", "multiples", "largest", "largest_members", "rounds", "links"))
+
+# NBodyEngine.groups_f64(): per body label, members, degree (int32[n_total]), then the summary
+GroupsResult = collections.namedtuple("GroupsResult", ("label", "members", "degree", "summary"))
+
+# NBodyEngine.group_table_f64(): one row per group (group_table())
+GROUP_TABLE_DTYPE = np.dtype([("label", np.int32), ("count", np.int32), ("mass", np.float64), ("com", np.float64, 3),
+                              ("velocity", np.float64, 3), ("r_rms", np.float64), ("sigma", np.float64)])
+
+
+def group_table(label, posm, vel, min_members=2):
+    """The groups of at least `min_members` bodies in label order, a structured array (GROUP_TABLE_DTYPE), from the labels and the
+    fp64 state, in numpy.  Over the bodies i of a group, in index order:
+        count = their number;  mass = M = sum m_i;  com = sum m_i x_i / M;  velocity = sum m_i v_i / M
+        r_rms = sqrt(sum m_i |x_i - com|^2 / M);  sigma = sqrt(sum m_i |v_i - velocity|^2 / M)      (the three-dimensional dispersion)
+    A group whose mass is 0 has NaN com, velocity, r_rms and sigma."""
+    label = np.asarray(label)
+    labels, counts = np.unique(label, return_counts=True)
+    keep = counts >= int(min_members)
+    out = np.zeros(int(keep.sum()), GROUP_TABLE_DTYPE)
+    for row, (l, k) in zip(out, zip(labels[keep], counts[keep])):
+        at = np.flatnonzero(label == l)
+        m, x, v = posm[at, 3], posm[at, :3], vel[at, :3]
+        mass = m.sum()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            com, vm = (m[:, None] * x).sum(0) / mass, (m[:, None] * v).sum(0) / mass
+            r_rms = np.sqrt((m * ((x - com) ** 2).sum(1)).sum() / mass)
+            sigma = np.sqrt((m * ((v - vm) ** 2).sum(1)).sum() / mass)
+        row["label"], row["count"], row["mass"], row["com"], row["velocity"], row["r_rms"], row["sigma"] = l, k, mass, com, vm, r_rms, sigma
+    return out
+
+
+LAGRANGE_FRACTIONS = (0.01,0.02, 0.05, 0.1, 0.2, 0.3, 0.5, 0.7, 0.9)
 
 
 def radial_profile(order, posm, vel, centre, counts, radii, vcentre=None):
@@ -957,6 +990,50 @@ class NBodyEngine:
         posm, vel, _ = self.state(np.float64)
         count, cols = radial_profile(order, posm, vel, c, lag.count, lag.radius, vcentre)
         return RadialProfileResult(centre=c, total_mass=lag.total_mass, fraction=lag.fraction, count=count, **cols)
+
+    # -- the fp64 group census: radius counts and friends-of-friends groups (fp64 contexts) --
+    def radius_counts_f64(self, radius):
+        """count: the number of OTHER bodies within `radius` of every body (nbody_get_radius_counts_f64): int32[n_total].  Body j is
+        counted iff d2 <= radius * radius with d2 = (dx*dx + dy*dy) + dz*dz without contraction — mass_within()'s expression; a NaN or
+        +inf d2 never is; zero-mass bodies count.  radius finite and >= 0 with a finite square, else ERR_INVALID.  precision="f64"
+        contexts on one device owning all bodies; everything else: ERR_UNSUPPORTED.  One pass; changes nothing a getter shows and
+        leaves the Hermite caches, the fp64 tracers and any block session alone."""
+        count = np.empty(self.n_total, np.int32)
+        self._check(self._L.nbody_get_radius_counts_f64(self._h, float(radius), count.ctypes.data))
+        return count
+
+    def radius_counts_at_f64(self, points, radius):
+        """count: the number of bodies within `radius` of every row of `points` (nbody_radius_counts_at_f64): int32[n].  No body is
+        dropped by index: a point exactly on a body counts that body, and one point c gives mass_within(c, [radius])'s count exactly.
+        Rules, contexts and side effects (none) as radius_counts_f64()."""
+        p = self._rows64(points, "radius_counts_at_f64", "points")
+        count = np.empty(p.shape[0], np.int32)
+        self._check(self._L.nbody_radius_counts_at_f64(self._h, p.ctypes.data, 24, p.shape[0], float(radius), count.ctypes.data))
+        return count
+
+    def groups_f64(self, radius):
+        """The friends-of-friends groups at linking length `radius` (nbody_get_groups_f64): a GroupsResult (label, members, degree,
+        summary).  Bodies i != j are linked iff d2 <= radius * radius (d2 as radius_counts_f64()); degree[i] = the bodies linked to
+        i; label[i] = the lowest index of i's connected component; members[i] = its size: int32[n_total] each.  summary: groups (the
+        components, singles included), multiples (those of two or more), largest (the label of the one with the most members, the
+        lowest among ties), largest_members, rounds (the pair passes the device took), links (sum of degree / 2).  Everything but
+        rounds is a function of the positions and the radius alone.  Contexts and side effects (none) as radius_counts_f64()."""
+        label, members, degree = (np.empty(self.n_total, np.int32) for _ in range(3))
+        s = _lib.Groups()
+        self._check(self._L.nbody_get_groups_f64(self._h, float(radius), label.ctypes.data, members.ctypes.data, degree.ctypes.data,
+                                                 ctypes.byref(s)))
+        return GroupsResult(label, members, degree, GroupsSummary(*(int(getattr(s, f)) for f in GroupsSummary._fields)))
+
+    def group_table_f64(self, radius, min_members=2):
+        """One row per group of at least `min_members` bodies, in label order: a structured array (label, count, mass, com, velocity,
+        r_rms, sigma) from groups_f64(radius) and state(np.float64), in numpy.  Over the bodies i of a group:
+            mass = M = sum m_i;  com = sum m_i x_i / M;  velocity = sum m_i v_i / M
+            r_rms = sqrt(sum m_i |x_i - com|^2 / M);  sigma = sqrt(sum m_i |v_i - velocity|^2 / M)
+        (sigma is the three-dimensional dispersion; a group of zero mass has NaN there).  Python only; the passes of groups_f64() and
+        one state read."""
+        label = self.groups_f64(radius).label
+        posm, vel, _ = self.state(np.float64)
+        return group_table(label, posm, vel, min_members)
 
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
