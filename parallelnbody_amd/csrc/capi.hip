@@ -1,4 +1,4 @@
-// C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches (the Hermite calls: capi_hermite.hip).  Host C++ over the
+// C-ABI of libnbody_amd.so (include/nbody.h): context, device state, launches (the Hermite calls: capi_hermite.hip; the fp64 queries: capi_query64.hip).  Host C++ over the
 // HIP runtime; no torch types, no exceptions across the boundary (the entry points that allocate host memory catch
 // std::bad_alloc), no CPU fallback.  Which kernel, geometry and plan a context gets — every size threshold — is decided in
 // launch_policy.{h,cpp} (host only, CPU-tested); nbody_create asks the device its CU count and memory and carries the answer out.
@@ -14,7 +14,7 @@
 #include "ctx.h"
 #include "launch_policy.h"
 
-// ---- what capi_hermite.hip calls as well (capi_common.h) ----
+// ---- what capi_hermite.hip and capi_query64.hip call as well (capi_common.h) ----
 namespace nbody {
 int multi_unsupported(nbody_ctx *c, const char *who) {
   return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not available on a multi-device context (nbody_create_multi); use one context per device", who);

@@ -1,11 +1,9 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
-// fp64 tracers, beside the snap and the fp64 point queries they are built on, and the fp64 potential and tidal tensor (kernels_pot64.hip) and the fp64 pair census (kernels_census64.hip) and neighbour census (kernels_neighbours64.hip), the radial census (kernels_radial64.hip) and the group census (kernels_groups64.hip).  Host C++ like capi.hip, whose helpers it shares
-// (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
+// fp64 tracers, beside the snap and the jerk and snap at fp64 points they are built on (the other fp64 queries: capi_query64.hip).  Host
+// C++ like capi.hip, whose helpers it shares (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "capi_common.h"
@@ -14,7 +12,7 @@
 
 namespace {
 
-using nbody::check_ready; using nbody::ensure_jerk64; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::fail; using nbody::hermite_invalidate; using nbody::hermite_invalidate_order; using nbody::HermiteBlockSession; using nbody::HermiteCache; using nbody::kSnapRowWidth; using nbody::multi_unsupported; using nbody::queue_body_jerk; using nbody::read_energy; using nbody::scatter_records; using nbody::timed_launch;
+using nbody::check_ready; using nbody::ensure_jerk64; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::fail; using nbody::gather_double4; using nbody::points64_part_holds; using nbody::points64_ready; using nbody::stage_points64; using nbody::stage_to_host; using nbody::Staged64; using nbody::hermite_invalidate; using nbody::hermite_invalidate_order; using nbody::HermiteBlockSession; using nbody::HermiteCache; using nbody::kSnapRowWidth; using nbody::multi_unsupported; using nbody::queue_body_jerk; using nbody::read_energy; using nbody::scatter_records; using nbody::timed_launch;
 
 // where the stepping exists — fp64 state, one device, all bodies (such contexts are at theta == 0) — and when: a state set, no step half done
 int hermite_ready(nbody_ctx *c, const char *who) {
@@ -37,12 +35,6 @@ int probe_part_holds(nbody_ctx *c, int width, const char *what) {
   const size_t need = nbody::probe_part_elems(c->p.n_total, c->p.n_total, width);
   if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
   return fail(c, NBODY_ERR_STATE, "%s: the partial rows need %zu float4, the staging area holds %zu", what, need, c->probe_part_elems);
-}
-// a point pass is never queued into a staging area that does not hold a slab's partial rows
-int points64_part_holds(nbody_ctx *c, int m, int width, const char *what) {
-  const size_t need = nbody::probe_part_elems(c->p.n_total, m, width);
-  if (c->probe_part && c->probe_part_elems >= need) return NBODY_OK;
-  return fail(c, NBODY_ERR_STATE, "%s: the partial rows of %d points need %zu float4, the staging area holds %zu", what, m, need, c->probe_part_elems);
 }
 
 // (a, j) of the bodies at (posm, vel) — the live state or the predicted one — into aj64: nbody_get_jerk_f64's pass and fold with the same
@@ -748,212 +740,6 @@ int snap_supported(nbody_ctx *c, const char *who) {
   return NBODY_OK;
 }
 
-// where the points exist — the contexts that answer nbody_hermite_step: fp64 state, one device, all bodies — and when: a state set, no step half done
-int points64_ready(nbody_ctx *c, const char *who) {
-  if (!c) return NBODY_ERR_INVALID;
-  if (c->multi) return multi_unsupported(c, who);
-  if (c->p.precision != NBODY_PREC_F64)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context whose state is fp32 (NBODY_PREC_F32, NBODY_PREC_F32_KAHAN): its points are doubles "
-                "in the field of fp64 bodies; create the context with NBODY_PREC_F64 (fp32 contexts have nbody_jerk_at and nbody_set_tracers)", who);
-  if (c->p.i_count != c->p.n_total)
-    return fail(c, NBODY_ERR_UNSUPPORTED, "%s: not on a context that owns a slice of the bodies (i_count < n_total)", who);
-  if (int rc = check_ready(c)) return rc;
-  if (c->step_open || c->step_local) return fail(c, NBODY_ERR_STATE, "%s: a step is open (nbody_step_end first)", who);
-  return NBODY_OK;
-}
-
-// n records of three doubles, `stride` bytes apart (NULL: zeros), as double4 rows with a fourth component of 0
-void gather_double4(double *dst, const double *src, size_t stride, size_t n) {
-  for (size_t k = 0; k < n; ++k) {
-    if (src) memcpy(dst + 4 * k, (const char *)src + k * stride, 24);
-    else     dst[4 * k] = dst[4 * k + 1] = dst[4 * k + 2] = 0.0;
-    dst[4 * k + 3] = 0.0;
-  }
-}
-
-// ---- the fp64 potential and tidal tensor (kernels_pot64.hip) ----
-constexpr int kPot64Width = 1, kTidal64Width = 4;   // the float4 of a partial row: one double (half a float4 unused), eight doubles
-
-// phi ([m]) or the tensors ([m][6]) into out (device) — at m points (ppos: double4 each, device) or, ppos == nullptr, at the bodies
-// themselves with each left out by index — from the LIVE positions: one pass under NBODY_KERNEL_FORCES, never queued into a staging
-// area that does not hold a slab's partial rows
-int pot64_pass(nbody_ctx *c, bool tidal, const void *ppos, int m, double *out) {
-  const int width = tidal ? kTidal64Width : kPot64Width;
-  if (int rc = ensure_probe_part(c, m, width)) return rc;
-  if (int rc = points64_part_holds(c, m, width, tidal ? "the fp64 tidal pass" : "the fp64 potential pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Pot64Launch L;
-    L.posm = c->posm; L.ppos = ppos; L.part = c->probe_part; L.part_elems = c->probe_part_elems; L.out = out;
-    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, tidal ? nbody::launch_tidal_f64(L, c->stream) : nbody::launch_pot_f64(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// nbody_potential_at_f64 / nbody_tidal_at_f64: n points in, `doubles` (1 / 6) per point out
-int pot64_at(nbody_ctx *c, const char *who, bool tidal, const double *pos, size_t pos_stride, int32_t n, double *out, size_t out_stride) {
-  const size_t doubles = tidal ? 6 : 1;
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (n < 0 || !pos || pos_stride < 24 || !out || out_stride < doubles * 8)
-    return fail(c, NBODY_ERR_INVALID, "%s: null buffer, n < 0, a point stride < 24 or an output stride < %d", who, (int)(doubles * 8));
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n;
-  if ((rc = ensure_stage(c, m * (4 + doubles) * sizeof(double)))) return rc;   // the points as double4, behind them the results
-  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(d, h, m * 32, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pot64_pass(c, tidal, d, n, d + 4 * m))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + 4 * m, d + 4 * m, m * doubles * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  scatter_records(out, out_stride, h + 4 * m, doubles * 8, m);
-  return NBODY_OK;
-}
-
-// nbody_get_potentials_f64 / nbody_get_tidal_f64: n_total rows
-int pot64_get(nbody_ctx *c, const char *who, bool tidal, double *out, size_t stride) {
-  const size_t doubles = tidal ? 6 : 1;
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!out || stride < doubles * 8) return fail(c, NBODY_ERR_INVALID, "%s: null buffer or stride < %d", who, (int)(doubles * 8));
-  const size_t n = (size_t)c->p.n_total;
-  if ((rc = ensure_stage(c, n * doubles * 8))) return rc;
-  if ((rc = pot64_pass(c, tidal, nullptr, (int)n, (double *)c->d_stage))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * doubles * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  scatter_records(out, stride, c->h_stage, doubles * 8, n);
-  return NBODY_OK;
-}
-
-// ---- the fp64 pair census (kernels_census64.hip) ----
-constexpr int kNearest64Width = 1, kPartner64Width = 2;   // the float4 of a partial row: (d2, index), (e, d2, index, pad)
-
-// per row the nearest body (index, value = d2) or, bound, the most-bound partner (index, value = e, d2) into device arrays — at m points
-// (ppos, pvel: double4 each, device) or, ppos == nullptr, at the bodies themselves with each left out by index — from the LIVE state:
-// one pass under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial rows
-int census64_pass(nbody_ctx *c, bool bound, const void *ppos, const void *pvel, int m, int *index, double *value, double *d2) {
-  const int width = bound ? kPartner64Width : kNearest64Width;
-  if (int rc = ensure_probe_part(c, m, width)) return rc;
-  if (int rc = points64_part_holds(c, m, width, bound ? "the fp64 partner pass" : "the fp64 nearest pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Census64Launch L;
-    L.posm = c->posm; L.vel = c->vel; L.ppos = ppos; L.pvel = pvel; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
-    L.index = index; L.value = value; L.d2 = d2;
-    L.n_total = c->p.n_total; L.m = m; L.G = c->p.G; L.eps2 = c->p.eps * c->p.eps;
-    HIP_TRY(c, bound ? nbody::launch_partner_f64(L, c->stream) : nbody::launch_nearest_f64(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// the results of m rows behind `skip` doubles of the staging pair: value [m], d2 [m], index [m] (int32)
-struct CensusRows { double *value, *d2; int *index; };
-CensusRows census_rows(void *stage, size_t skip, size_t m) {
-  double *v = (double *)stage + skip;
-  return CensusRows{v, v + m, (int *)(v + 2 * m)};
-}
-constexpr size_t kCensusRowBytes = 20;   // of the staging pair, per row
-
-// rows m of the staging pair to the caller's arrays: value and d2 are the nearest form's one array (d2), the partner form's two
-int census64_out(nbody_ctx *c, bool bound, size_t skip, size_t m, int32_t *index, double *energy, double *d2) {
-  HIP_TRY(c, hipMemcpyAsync((double *)c->h_stage + skip, (double *)c->d_stage + skip, m * kCensusRowBytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const CensusRows h = census_rows(c->h_stage, skip, m);
-  if (index) memcpy(index, h.index, m * 4);
-  if (bound) {
-    if (energy) memcpy(energy, h.value, m * 8);
-    if (d2) memcpy(d2, h.d2, m * 8);
-  } else if (d2) {
-    memcpy(d2, h.value, m * 8);
-  }
-  return NBODY_OK;
-}
-
-// nbody_get_nearest_f64 / nbody_get_partners_f64: n_total rows
-int census64_get(nbody_ctx *c, const char *who, bool bound, int32_t *index, double *energy, double *d2) {
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!index && !energy && !d2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
-  const size_t n = (size_t)c->p.n_total;
-  if ((rc = ensure_stage(c, n * kCensusRowBytes))) return rc;
-  const CensusRows d = census_rows(c->d_stage, 0, n);
-  if ((rc = census64_pass(c, bound, nullptr, nullptr, (int)n, d.index, d.value, d.d2))) return rc;
-  return census64_out(c, bound, 0, n, index, energy, d2);
-}
-
-// nbody_nearest_at_f64 / nbody_partner_at_f64: n points in (bound: moving with vel, NULL = at rest)
-int census64_at(nbody_ctx *c, const char *who, bool bound, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n,
-                int32_t *index, double *energy, double *d2) {
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (n < 0 || !pos || pos_stride < 24 || (vel && vel_stride < 24) || (!index && !energy && !d2))
-    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, every output null, or a stride < 24", who);
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n, skip = (bound ? 8 : 4) * m;       // the points (and their velocities) as double4, behind them the results
-  if ((rc = ensure_stage(c, skip * sizeof(double) + m * kCensusRowBytes))) return rc;
-  double *h = (double *)c->h_stage, *dv = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  if (bound) gather_double4(h + 4 * m, vel, vel_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(dv, h, skip * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  const CensusRows d = census_rows(c->d_stage, skip, m);
-  if ((rc = census64_pass(c, bound, dv, bound ? dv + 4 * m : nullptr, n, d.index, d.value, d.d2))) return rc;
-  return census64_out(c, bound, skip, m, index, energy, d2);
-}
-
-// nbody_closest_pair_f64 / nbody_hardest_pair_f64: the per-body pass, then its smallest value and the lowest row that attains it,
-// reduced on the device in a fixed order — r = (value, i, j = that row's index, d2), (+inf, -1, -1, +inf) where there is none
-int census64_pair(nbody_ctx *c, bool bound, double (&r)[4]) {
-  const size_t n = (size_t)c->p.n_total, slots = (size_t)nbody::energy_fast_slots((int)n);
-  const size_t skip = 2 * slots + 4;                             // the reduction's partials and its four doubles, ahead of the rows
-  int rc = ensure_stage(c, skip * sizeof(double) + n * kCensusRowBytes);
-  if (rc) return rc;
-  double *partials = (double *)c->d_stage, *out = partials + 2 * slots;
-  const CensusRows d = census_rows(c->d_stage, skip, n);
-  if ((rc = census64_pass(c, bound, nullptr, nullptr, (int)n, d.index, d.value, d.d2))) return rc;
-  HIP_TRY(c, nbody::launch_census_pair(d.value, d.index, bound ? d.d2 : nullptr, (int)n, partials, out, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(r, c->h_stage, sizeof(r));
-  return NBODY_OK;
-}
-
-// ---- the fp64 neighbour census (kernels_neighbours64.hip) ----
-// per row the k nearest bodies (index, d2: rows of k) and, at the bodies with 2 <= k, the local density (rho, rk2) into device arrays
-// (each may be null) — at m points (ppos: double4, device) or, ppos == nullptr, at the bodies themselves with each left out by index —
-// from the LIVE state: one pass under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial rows
-int neighbours64_pass(nbody_ctx *c, int k, const void *ppos, int m, int *index, double *d2, double *rho, double *rk2) {
-  const int width = nbody::neighbours64_width(k);
-  if (int rc = ensure_probe_part(c, m, width)) return rc;
-  if (int rc = points64_part_holds(c, m, width, "the fp64 neighbour pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Neighbours64Launch L;
-    L.posm = c->posm; L.ppos = ppos; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
-    L.index = index; L.d2 = d2; L.rho = rho; L.rk2 = rk2;
-    L.n_total = c->p.n_total; L.m = m; L.k = k; L.G = c->p.G;
-    HIP_TRY(c, nbody::launch_neighbours_f64(L, c->stream));
-    return NBODY_OK;
-  });
-}
-
-// the lists of m rows behind `skip` doubles of the staging pair — d2 [m * k], index [m * k] (int32) — to the caller's arrays
-int neighbours64_lists(nbody_ctx *c, int k, const void *ppos, size_t skip, size_t m, int32_t *index, double *d2) {
-  double *dd2 = (double *)c->d_stage + skip;
-  int *dindex = (int *)(dd2 + m * k);
-  if (int rc = neighbours64_pass(c, k, ppos, (int)m, dindex, dd2, nullptr, nullptr)) return rc;
-  HIP_TRY(c, hipMemcpyAsync((double *)c->h_stage + skip, dd2, m * k * 12, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const double *hd2 = (const double *)c->h_stage + skip;
-  if (d2) memcpy(d2, hd2, m * k * 8);
-  if (index) memcpy(index, hd2 + m * k, m * k * 4);
-  return NBODY_OK;
-}
-
-// k within lo .. NBODY_NEIGHBOURS_MAX
-static_assert(nbody::kNeighbours64Max == NBODY_NEIGHBOURS_MAX, "the widest compiled list is the largest k of the C-ABI");
-int neighbours64_k(nbody_ctx *c, const char *who, int32_t k, int lo) {
-  if (k >= lo && k <= NBODY_NEIGHBOURS_MAX) return NBODY_OK;
-  return fail(c, NBODY_ERR_INVALID, "%s: k = %d is outside %d .. %d", who, (int)k, lo, NBODY_NEIGHBOURS_MAX);
-}
-
 template <class O>
 int tracers_get(nbody_ctx *c, const char *who, double *out, size_t stride) {
   constexpr int kBytes = (O::kRow + 3 * O::kDerivs) * 8;
@@ -978,70 +764,6 @@ int tracers_timescale(nbody_ctx *c, const char *who, double *t_min, int32_t *tra
   else if (c->hm_external) hermite_invalidate(c);                  // (the rule enter applies, where the bodies' cache is not needed)
   if ((rc = tracers_enter<O>(c))) return rc;
   return scale_out<O>(c, tracer_view<O>(c), t_min, tracer, kind);
-}
-
-// ---- the fp64 radial census (kernels_radial64.hip) ----
-static_assert(sizeof(nbody_lagrange) == 40 && nbody::kRadialFractionsMax == NBODY_LAGRANGE_MAX, "include/nbody.h and kernels.h agree");
-
-// The order about `centre`, the cumulative mass in it and, k > 0, the rows of k fractions, queued on the stream from the LIVE positions
-// and left in the staging area on the device: *W says where.  Not a pair pass: no kernel timer counts it (as nbody_get_moments').
-// NBODY_RADIAL_PHASES=1 (read at every call; tools/radial_f64_measure.py): event pairs round the four phases, waited for and printed
-// to stderr.
-int radial64_run(nbody_ctx *c, const double centre[3], const double *fractions, int k, nbody::Radial64Work *W) {
-  *W = nbody::radial64_work(c->p.n_total);
-  if (int rc = ensure_stage(c, W->bytes)) return rc;
-  if (c->radial_resident == 0) HIP_TRY(c, nbody::radial64_resident(&c->radial_resident));
-  nbody::Radial64Launch L;
-  L.posm = c->posm; L.n_total = c->p.n_total;
-  L.centre[0] = centre[0]; L.centre[1] = centre[1]; L.centre[2] = centre[2];
-  L.fractions = fractions; L.k = k; L.resident = c->radial_resident; L.work = c->d_stage;
-  const char *env = getenv("NBODY_RADIAL_PHASES");
-  if (!(env && env[0] == '1')) {
-    HIP_TRY(c, nbody::launch_radial_f64(L, c->stream));
-    return NBODY_OK;
-  }
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipError_t err = hipSuccess;
-  for (int q = 0; q < 5 && err == hipSuccess; ++q) err = hipEventCreate(&ev[q]);
-  L.events = ev;
-  if (err == hipSuccess) err = nbody::launch_radial_f64(L, c->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-  float ms[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int q = 0; q < 4 && err == hipSuccess; ++q) err = hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]);
-  for (int q = 0; q < 5; ++q) if (ev[q]) (void)hipEventDestroy(ev[q]);
-  HIP_TRY(c, err);
-  fprintf(stderr, "radial_f64 phases: n %d k %d keys %.4f sort %.4f scan %.4f select %.4f ms\n", c->p.n_total, k, ms[0], ms[1], ms[2], ms[3]);
-  return NBODY_OK;
-}
-
-bool radial64_centre_ok(const double centre[3]) {
-  return centre && std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]);
-}
-
-// ---- the fp64 group census (kernels_groups64.hip) ----
-static_assert(sizeof(nbody_groups) == 32, "include/nbody.h: 32 bytes");
-constexpr int kGroups64Width = 1;   // the float4 of a partial row: two int32, half a float4 unused
-
-// radius finite and >= 0, r2 = radius * radius (one fp64 multiply) finite
-int groups64_r2(nbody_ctx *c, const char *who, double radius, double *r2) {
-  *r2 = radius * radius;
-  if (std::isfinite(radius) && radius >= 0.0 && std::isfinite(*r2)) return NBODY_OK;
-  return fail(c, NBODY_ERR_INVALID, "%s: the radius must be finite and >= 0 and its square finite", who);
-}
-
-// one N^2 pass from the LIVE positions under NBODY_KERNEL_FORCES, never queued into a staging area that does not hold a slab's partial
-// rows: parent == nullptr: count = the linked bodies per row — at m points (ppos: double4 each, device) or, ppos == nullptr, at the
-// bodies themselves with each left out by index —; else the bodies' minimum parent into mn and, first round, their degree into count
-int groups64_pass(nbody_ctx *c, double r2, const void *ppos, int m, const int *parent, bool first_round, int *mn, int *count) {
-  if (int rc = ensure_probe_part(c, m, kGroups64Width)) return rc;
-  if (int rc = points64_part_holds(c, m, kGroups64Width, parent ? "the fp64 groups pass" : "the fp64 radius-count pass")) return rc;
-  return timed_launch(c, NBODY_KERNEL_FORCES, [&]() -> int {
-    nbody::Groups64Launch L;
-    L.posm = c->posm; L.ppos = ppos; L.parent = parent; L.part = c->probe_part; L.part_elems = c->probe_part_elems;
-    L.mn = mn; L.count = count; L.n_total = c->p.n_total; L.m = m; L.r2 = r2;
-    HIP_TRY(c, parent ? nbody::launch_groups_pass_f64(L, first_round, c->stream) : nbody::launch_radius_counts_f64(L, c->stream));
-    return NBODY_OK;
-  });
 }
 
 }  // namespace
@@ -1176,296 +898,13 @@ int nbody_jerk_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   if (n == 0) return NBODY_OK;
   const size_t m = (size_t)n;
   if ((rc = ensure_probe_part(c, n, 3))) return rc;
-  if ((rc = ensure_stage(c, m * 14 * sizeof(double)))) return rc;   // the points and their velocities as double4, behind them six doubles per point
-  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  gather_double4(h + 4 * m, vel, vel_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(d, h, m * 64, hipMemcpyHostToDevice, c->stream));
+  Staged64 s;                                                      // the points and their velocities, behind them six doubles per point
+  if ((rc = stage_points64(c, pos, pos_stride, vel, vel_stride, true, m, m * 48, &s))) return rc;
+  double *d = s.d, *h = s.h + s.skip;
   if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + 8 * m, d + 8 * m, m * 48, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (acc) scatter_records(acc, acc_stride, h + 8 * m, 24, m, 48);
-  if (jerk) scatter_records(jerk, jerk_stride, h + 8 * m + 3, 24, m, 48);
-  return NBODY_OK;
-}
-
-int nbody_potential_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double *phi, size_t phi_stride) {
-  return pot64_at(c, "nbody_potential_at_f64", false, pos, pos_stride, n, phi, phi_stride);
-}
-int nbody_get_potentials_f64(nbody_ctx *c, double *phi, size_t stride) { return pot64_get(c, "nbody_get_potentials_f64", false, phi, stride); }
-
-int nbody_tidal_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double *t6, size_t t_stride) {
-  return pot64_at(c, "nbody_tidal_at_f64", true, pos, pos_stride, n, t6, t_stride);
-}
-int nbody_get_tidal_f64(nbody_ctx *c, double *t6, size_t stride) { return pot64_get(c, "nbody_get_tidal_f64", true, t6, stride); }
-
-int nbody_tidal_time_f64(nbody_ctx *c, double *t_min, int32_t *body) {
-  const char *who = "nbody_tidal_time_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!t_min && !body) return fail(c, NBODY_ERR_INVALID, "%s: both outputs are null", who);
-  const int n = c->p.n_total;
-  if (!c->tidal64) HIP_TRY(c, hipMalloc(&c->tidal64, (6 * (size_t)n + 2 * (size_t)nbody::energy_fast_slots(n)) * sizeof(double)));
-  double *t64 = (double *)c->tidal64, *partials = t64 + 6 * (size_t)n;
-  if ((rc = pot64_pass(c, true, nullptr, n, t64))) return rc;
-  HIP_TRY(c, nbody::launch_tidal_time(t64, n, partials, (double *)c->scratch, c->stream));
-  double n2 = 0.0, at = 0.0;
-  if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
-  if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);   // nbody_tidal_time's rule
-  if (body) *body = (int32_t)at;
-  return NBODY_OK;
-}
-
-int nbody_get_nearest_f64(nbody_ctx *c, int32_t *index, double *d2) { return census64_get(c, "nbody_get_nearest_f64", false, index, nullptr, d2); }
-int nbody_nearest_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, int32_t *index, double *d2) {
-  return census64_at(c, "nbody_nearest_at_f64", false, pos, pos_stride, nullptr, 0, n, index, nullptr, d2);
-}
-int nbody_get_partners_f64(nbody_ctx *c, int32_t *index, double *energy, double *d2) {
-  return census64_get(c, "nbody_get_partners_f64", true, index, energy, d2);
-}
-int nbody_partner_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, int32_t n, int32_t *index,
-                         double *energy, double *d2) {
-  return census64_at(c, "nbody_partner_at_f64", true, pos, pos_stride, vel, vel_stride, n, index, energy, d2);
-}
-
-int nbody_closest_pair_f64(nbody_ctx *c, int32_t *i, int32_t *j, double *d2) {
-  const char *who = "nbody_closest_pair_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!i && !j && !d2) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
-  double r[4];
-  if ((rc = census64_pair(c, false, r))) return rc;
-  if (i) *i = (int32_t)r[1];
-  if (j) *j = (int32_t)r[2];
-  if (d2) *d2 = r[0];
-  return NBODY_OK;
-}
-
-int nbody_hardest_pair_f64(nbody_ctx *c, int32_t *i, int32_t *j, double *energy, double *d2) {
-  const char *who = "nbody_hardest_pair_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!i && !j && !energy && !d2) return fail(c, NBODY_ERR_INVALID, "%s: all four outputs are null", who);
-  double r[4];
-  if ((rc = census64_pair(c, true, r))) return rc;
-  if (i) *i = (int32_t)r[1];
-  if (j) *j = (int32_t)r[2];
-  if (energy) *energy = r[0];
-  if (d2) *d2 = r[3];
-  return NBODY_OK;
-}
-
-int nbody_pair_time_f64(nbody_ctx *c, double *t_min, int32_t *i, int32_t *j) {
-  const char *who = "nbody_pair_time_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!t_min && !i && !j) return fail(c, NBODY_ERR_INVALID, "%s: all three outputs are null", who);
-  double r[4];
-  if ((rc = census64_pair(c, false, r))) return rc;
-  const int32_t bi = (int32_t)r[1], bj = (int32_t)r[2];
-  double t = HUGE_VAL;                                             // no pair, or a massless one
-  if (bi >= 0 && bj >= 0) {                                        // the free-fall scale of the closest pair, formed here from d2 and the two masses
-    double *h = (double *)c->h_stage;
-    HIP_TRY(c, hipMemcpyAsync(h, (const double *)c->posm + 4 * (size_t)bi + 3, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h + 1, (const double *)c->posm + 4 * (size_t)bj + 3, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const double gm = c->p.G * (h[0] + h[1]);
-    if (gm > 0.0) t = std::sqrt(r[0] * std::sqrt(r[0]) / gm);
-  }
-  if (t_min) *t_min = t;
-  if (i) *i = bi;
-  if (j) *j = bj;
-  return NBODY_OK;
-}
-
-int nbody_get_neighbours_f64(nbody_ctx *c, int32_t k, int32_t *index, double *d2) {
-  const char *who = "nbody_get_neighbours_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if ((rc = neighbours64_k(c, who, k, 1))) return rc;
-  if (!index && !d2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
-  const size_t n = (size_t)c->p.n_total;
-  if ((rc = ensure_stage(c, n * k * 12))) return rc;
-  return neighbours64_lists(c, k, nullptr, 0, n, index, d2);
-}
-
-int nbody_neighbours_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, int32_t k, int32_t *index, double *d2) {
-  const char *who = "nbody_neighbours_at_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if ((rc = neighbours64_k(c, who, k, 1))) return rc;
-  if (n < 0 || !pos || pos_stride < 24 || (!index && !d2))
-    return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, every output null, or a stride < 24", who);
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n, skip = 4 * m;                        // the points as double4, behind them the lists
-  if ((rc = ensure_stage(c, skip * sizeof(double) + m * k * 12))) return rc;
-  gather_double4((double *)c->h_stage, pos, pos_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(c->d_stage, c->h_stage, skip * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  return neighbours64_lists(c, k, c->d_stage, skip, m, index, d2);
-}
-
-int nbody_get_density_f64(nbody_ctx *c, int32_t k, double *rho, double *rk2) {
-  const char *who = "nbody_get_density_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if ((rc = neighbours64_k(c, who, k, 2))) return rc;
-  if (!rho && !rk2) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
-  const size_t n = (size_t)c->p.n_total;
-  if ((rc = ensure_stage(c, n * 16))) return rc;
-  double *d = (double *)c->d_stage;
-  if ((rc = neighbours64_pass(c, k, nullptr, (int)n, nullptr, nullptr, d, d + n))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, d, n * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (rho) memcpy(rho, c->h_stage, n * 8);
-  if (rk2) memcpy(rk2, (const double *)c->h_stage + n, n * 8);
-  return NBODY_OK;
-}
-
-int nbody_density_centre_f64(nbody_ctx *c, int32_t k, nbody_core *out) {
-  const char *who = "nbody_density_centre_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if ((rc = neighbours64_k(c, who, k, 2))) return rc;
-  if (!out || out->struct_size != sizeof(nbody_core)) return fail(c, NBODY_ERR_INVALID, "%s: null output or struct_size != sizeof(nbody_core)", who);
-  const size_t n = (size_t)c->p.n_total, slots = (size_t)nbody::energy_fast_slots((int)n);
-  const size_t skip = 8 * slots + 16;                            // the reductions' partials and their nine doubles, ahead of the densities
-  if ((rc = ensure_stage(c, (skip + n) * sizeof(double)))) return rc;
-  double *partials = (double *)c->d_stage, *red = partials + 8 * slots, *rho = partials + skip;
-  if ((rc = neighbours64_pass(c, k, nullptr, (int)n, nullptr, nullptr, rho, nullptr))) return rc;
-  HIP_TRY(c, nbody::launch_density_centre(c->posm, rho, (int)n, partials, red, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, red, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const double *r = (const double *)c->h_stage;
-  out->k = k; out->used = (int32_t)r[4]; out->densest = (int32_t)r[6];
-  out->rho_max = r[5];
-  out->centre[0] = r[1]; out->centre[1] = r[2]; out->centre[2] = r[3];
-  out->core_radius = r[8]; out->rho_sum = r[0]; out->rho2_sum = r[7];
-  return NBODY_OK;
-}
-
-int nbody_radial_order_f64(nbody_ctx *c, const double centre[3], int32_t *order, double *d2, double *mass_cum, int32_t *n_finite) {
-  const char *who = "nbody_radial_order_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!radial64_centre_ok(centre)) return fail(c, NBODY_ERR_INVALID, "%s: null centre or a centre that is not finite", who);
-  if (!order && !d2 && !mass_cum && !n_finite) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
-  nbody::Radial64Work W;
-  if ((rc = radial64_run(c, centre, nullptr, 0, &W))) return rc;
-  const size_t n = (size_t)c->p.n_total;
-  const char *d = (const char *)c->d_stage;
-  char *h = (char *)c->h_stage;
-  if (order) HIP_TRY(c, hipMemcpyAsync(h + W.idx[0], d + W.idx[0], n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (d2) HIP_TRY(c, hipMemcpyAsync(h + W.key[0], d + W.key[0], n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (mass_cum) HIP_TRY(c, hipMemcpyAsync(h + W.cum, d + W.cum, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (n_finite) HIP_TRY(c, hipMemcpyAsync(h + W.n_finite, d + W.n_finite, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (order) memcpy(order, h + W.idx[0], n * 4);
-  if (d2) memcpy(d2, h + W.key[0], n * 8);                         // (the sorted keys are the bit patterns of d2; a NaN reads all ones)
-  if (mass_cum) memcpy(mass_cum, h + W.cum, n * 8);
-  if (n_finite) memcpy(n_finite, h + W.n_finite, 4);
-  return NBODY_OK;
-}
-
-int nbody_lagrange_radii_f64(nbody_ctx *c, const double centre[3], const double *fractions, int32_t k, nbody_lagrange *rows,
-                             double *total_mass) {
-  const char *who = "nbody_lagrange_radii_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  if (!radial64_centre_ok(centre)) return fail(c, NBODY_ERR_INVALID, "%s: null centre or a centre that is not finite", who);
-  if (!fractions || !rows) return fail(c, NBODY_ERR_INVALID, "%s: null fractions or rows", who);
-  if (k < 1 || k > NBODY_LAGRANGE_MAX) return fail(c, NBODY_ERR_INVALID, "%s: k = %d outside 1 .. %d", who, k, NBODY_LAGRANGE_MAX);
-  for (int q = 0; q < k; ++q)
-    if (!(fractions[q] > 0.0 && fractions[q] <= 1.0))              // (a NaN fails both)
-      return fail(c, NBODY_ERR_INVALID, "%s: fraction %d is outside (0, 1]", who, q);
-  nbody::Radial64Work W;
-  if ((rc = radial64_run(c, centre, fractions, k, &W))) return rc;
-  const char *d = (const char *)c->d_stage;
-  char *h = (char *)c->h_stage;
-  HIP_TRY(c, hipMemcpyAsync(h + W.rows, d + W.rows, (size_t)k * sizeof(nbody_lagrange), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h + W.total, d + W.total, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(rows, h + W.rows, (size_t)k * sizeof(nbody_lagrange));
-  if (total_mass) memcpy(total_mass, h + W.total, 8);
-  return NBODY_OK;
-}
-
-int nbody_get_radius_counts_f64(nbody_ctx *c, double radius, int32_t *count) {
-  const char *who = "nbody_get_radius_counts_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  double r2;
-  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
-  if (!count) return fail(c, NBODY_ERR_INVALID, "%s: null output", who);
-  const size_t n = (size_t)c->p.n_total;
-  if ((rc = ensure_stage(c, n * 4))) return rc;
-  if ((rc = groups64_pass(c, r2, nullptr, (int)n, nullptr, false, nullptr, (int *)c->d_stage))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_stage, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(count, c->h_stage, n * 4);
-  return NBODY_OK;
-}
-
-int nbody_radius_counts_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, double radius, int32_t *count) {
-  const char *who = "nbody_radius_counts_at_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  double r2;
-  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
-  if (n < 0 || !pos || pos_stride < 24 || !count) return fail(c, NBODY_ERR_INVALID, "%s: null points or output, n < 0, or a stride < 24", who);
-  if (n == 0) return NBODY_OK;
-  const size_t m = (size_t)n;                                      // the points as double4, behind them the counts
-  if ((rc = ensure_stage(c, m * 36))) return rc;
-  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(d, h, m * 32, hipMemcpyHostToDevice, c->stream));
-  if ((rc = groups64_pass(c, r2, d, n, nullptr, false, nullptr, (int *)(d + 4 * m)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + 4 * m, d + 4 * m, m * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(count, h + 4 * m, m * 4);
-  return NBODY_OK;
-}
-
-// The rounds are driven from here: pass and fold, hook, compress, then a 4-byte read-back of `changed`.  The first round that changes
-// nothing is the last.  Every round but the last merges at least two components, so there are at most n of them.
-int nbody_get_groups_f64(nbody_ctx *c, double radius, int32_t *label, int32_t *members, int32_t *degree, nbody_groups *summary) {
-  const char *who = "nbody_get_groups_f64";
-  int rc = points64_ready(c, who);
-  if (rc) return rc;
-  double r2;
-  if ((rc = groups64_r2(c, who, radius, &r2))) return rc;
-  if (!label && !members && !degree && !summary) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
-  const size_t n = (size_t)c->p.n_total;
-  // ints of the staging pair: label, members, degree (read back together), hooked, mn, size; then four 64-bit sums and `changed`
-  const size_t sums = (6 * n + 1) / 2 * 2, flag = sums + 8, ints = flag + 2;
-  if ((rc = ensure_stage(c, ints * 4))) return rc;
-  int *d = (int *)c->d_stage, *h = (int *)c->h_stage;
-  int *parent = d, *dmembers = d + n, *ddegree = d + 2 * n, *hooked = d + 3 * n, *mn = d + 4 * n, *size = d + 5 * n;
-  HIP_TRY(c, nbody::launch_groups_identity(parent, (int)n, c->stream));
-  size_t rounds = 0;
-  for (;;) {
-    if (rounds == n) return fail(c, NBODY_ERR_INTERNAL, "%s: no fixed point after %zu rounds of %zu bodies", who, rounds, n);
-    if ((rc = groups64_pass(c, r2, nullptr, (int)n, parent, rounds == 0, mn, ddegree))) return rc;
-    ++rounds;
-    HIP_TRY(c, nbody::launch_groups_merge(parent, mn, hooked, (int)n, d + flag, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h + flag, d + flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (h[flag] == 0) break;
-  }
-  HIP_TRY(c, nbody::launch_groups_members(parent, ddegree, (int)n, size, dmembers, (unsigned long long *)(d + sums), c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h, d, 3 * n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h + sums, d + sums, 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (label) memcpy(label, h, n * 4);
-  if (members) memcpy(members, h + n, n * 4);
-  if (degree) memcpy(degree, h + 2 * n, n * 4);
-  if (summary) {
-    unsigned long long s[4];
-    memcpy(s, h + sums, 32);
-    summary->groups = (int32_t)s[0]; summary->multiples = (int32_t)s[1];
-    summary->largest = (int32_t)(0x7fffffffull - (s[3] & 0xffffffffull)); summary->largest_members = (int32_t)(s[3] >> 32);
-    summary->rounds = (int32_t)rounds; summary->reserved = 0;
-    summary->links = (int64_t)(s[2] / 2);
-  }
+  if ((rc = stage_to_host(c, s.skip, m * 48))) return rc;
+  if (acc) scatter_records(acc, acc_stride, h, 24, m, 48);
+  if (jerk) scatter_records(jerk, jerk_stride, h + 3, 24, m, 48);
   return NBODY_OK;
 }
 
@@ -1481,21 +920,18 @@ int nbody_snap_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   const size_t m = (size_t)n;
   if ((rc = ensure_probe_part(c, n, 3))) return rc;
   if ((rc = ensure_probe_part(c, n, kSnapRowWidth))) return rc;
-  if ((rc = ensure_stage(c, m * 23 * sizeof(double)))) return rc;   // the points and their velocities as double4, six doubles (a, j), nine (a, j, s)
   if ((rc = ensure_jerk64(c))) return rc;
-  double *h = (double *)c->h_stage, *d = (double *)c->d_stage;
-  gather_double4(h, pos, pos_stride, m);
-  gather_double4(h + 4 * m, vel, vel_stride, m);
-  HIP_TRY(c, hipMemcpyAsync(d, h, m * 64, hipMemcpyHostToDevice, c->stream));
+  Staged64 s;                                                      // the points and their velocities, behind them six doubles (a, j), nine (a, j, s)
+  if ((rc = stage_points64(c, pos, pos_stride, vel, vel_stride, true, m, m * 120, &s))) return rc;
+  double *d = s.d, *h = s.h + 14 * m;
   // the bodies' unrounded accelerations of the live state (as nbody_get_snap_f64 with acc_in == NULL), the points' own, then the snap
   if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
   if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
   if ((rc = points64_snap(c, c->posm, c->vel, (const double *)c->jerk64, 6, d, d + 4 * m, d + 8 * m, 6, n, d + 14 * m))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + 14 * m, d + 14 * m, m * 72, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (acc) scatter_records(acc, acc_stride, h + 14 * m, 24, m, 72);
-  if (jerk) scatter_records(jerk, jerk_stride, h + 14 * m + 3, 24, m, 72);
-  if (snap) scatter_records(snap, snap_stride, h + 14 * m + 6, 24, m, 72);
+  if ((rc = stage_to_host(c, 14 * m, m * 72))) return rc;
+  if (acc) scatter_records(acc, acc_stride, h, 24, m, 72);
+  if (jerk) scatter_records(jerk, jerk_stride, h + 3, 24, m, 72);
+  if (snap) scatter_records(snap, snap_stride, h + 6, 24, m, 72);
   return NBODY_OK;
 }
 

@@ -1,4 +1,4 @@
-// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, capi_hermite.hip, bh_driver.hip) share: error
+// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, capi_hermite.hip, capi_query64.hip, bh_driver.hip) share: error
 // texts, the device made current, the kernel timers.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -333,6 +333,17 @@ hipError_t launch_snap_points_list_f64(const Points64Launch &L, const int *list,
 hipError_t launch_jerk_fold_f64(const void *part, int m, int j_split, double *aj64, hipStream_t s);
 hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *ajs64, hipStream_t s);
 
+// What every fp64 row scan is launched with (scan_tile64.h: the potential and the tidal tensor, the pair, neighbour and group censuses):
+// rows — the bodies themselves or m points that are not bodies — against all bodies, a slab's partial rows in `part`.
+struct RowScan64Launch {
+  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves (m == n_total)
+  void *part = nullptr;         // the partial rows of one slab
+  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, the pass's width), or nothing is launched
+  int n_total = 0, m = 0;
+  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
+};
+
 // The potential and the tidal tensor of an fp64 state, at the bodies or at m points that are not bodies — kernels_pot64.hip: with
 // d = x_j - x, s^2 = |d|^2 + eps2, t = 1 / s:  phi = -sum_j G m_j t,  T_ab = sum_j G m_j [3 d_a d_b t^5 - delta_ab t^3], fp64 sums over
 // launch_jerk's chunks and tiles on fp64 state in the same order, with its s2 and rsq.  ppos == nullptr: the rows are the bodies
@@ -341,14 +352,9 @@ hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *aj
 // row's sums depend on its point and the bodies alone; a zero-mass body adds exactly nothing.  A partial row is one double (the
 // potential: probe_slab_points(n_total, 1), half of it used) or eight (the tensor's seven sums and a pad: probe_slab_points(n_total, 4));
 // the rows go in slabs of that many and are folded from 0.0 in chunk order: phi = -P, T_aa = S_aa - Q.
-struct Pot64Launch {
-  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
-  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
-  void *part = nullptr;         // the partial rows of one slab
-  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1 / 4), or nothing is launched
+constexpr int kPot64Width = 1, kTidal64Width = 4;   // the float4 of a partial row: one double (half a float4 unused), eight doubles
+struct Pot64Launch : RowScan64Launch {
   double *out = nullptr;        // [m]: phi — the tensor: [m][6], xx, yy, zz, xy, xz, yz
-  int n_total = 0, m = 0;
-  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no sum (the bodies: always 2)
   double G = 0.0, eps2 = 0.0;
 };
 hipError_t launch_pot_f64(const Pot64Launch &L, hipStream_t s);
@@ -364,18 +370,13 @@ hipError_t launch_tidal_f64(const Pot64Launch &L, hipStream_t s);
 // body is dropped by index.  The zero padding of a chunk's last tile is kept out by index (j < j1); a zero-mass body is a candidate.  A
 // row's result depends on the row and the bodies alone.  A partial row is (d2, index) — probe_slab_points(n_total, 1) — or (e, d2,
 // index, pad) — probe_slab_points(n_total, 2) —; the rows go in slabs of that many and are folded in chunk order under strict <.
-struct Census64Launch {
-  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
+constexpr int kNearest64Width = 1, kPartner64Width = 2;   // the float4 of a partial row: (d2, index), (e, d2, index, pad)
+struct Census64Launch : RowScan64Launch {
   const void *vel = nullptr;    // [n_total] double4: vx, vy, vz, unused (the partner pass)
-  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
   const void *pvel = nullptr;   // [m] double4: the points' velocities (the partner pass, ppos != nullptr)
-  void *part = nullptr;         // the partial rows of one slab
-  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1 / 2), or nothing is launched
   int *index = nullptr;         // [m]
   double *value = nullptr;      // [m]: d2 (nearest), e (partner)
   double *d2 = nullptr;         // [m]: the partner's d2 (the partner pass)
-  int n_total = 0, m = 0;
-  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
   double G = 0.0, eps2 = 0.0;
 };
 hipError_t launch_nearest_f64(const Census64Launch &L, hipStream_t s);
@@ -398,15 +399,10 @@ hipError_t launch_census_pair(const double *value, const int *index, const doubl
 //               (r2 sqrt(r2))) with msum the raw masses of the k - 1 nearest added in neighbour order and r2 = rk2 = d2 of the k-th;
 //               rho = 0 where the k-th is missing (rk2 = +inf) or the quotient is NaN
 constexpr int kNeighbours64Max = 8;   // == NBODY_NEIGHBOURS_MAX
-struct Neighbours64Launch {
-  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
-  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
-  void *part = nullptr;         // the partial rows of one slab
-  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, neighbours64_width(k)), or nothing is launched
+struct Neighbours64Launch : RowScan64Launch {   // (the partial rows' width: neighbours64_width(k))
   int *index = nullptr;
   double *d2 = nullptr, *rho = nullptr, *rk2 = nullptr;
-  int n_total = 0, m = 0, k = 0;
-  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
+  int k = 0;
   double G = 0.0;               // the tiles hold G m as the census's do; no result reads it
 };
 int neighbours64_width(int k);
@@ -458,16 +454,11 @@ hipError_t launch_radial_f64(const Radial64Launch &L, hipStream_t s);
 // (minimum, count) in a width-1 slot — probe_slab_points(n_total, 1) —; the rows go in slabs of that many and are folded in chunk order.
 //   launch_radius_counts_f64:  count = the number of linked bodies per row; parent and mn are not read
 //   launch_groups_pass_f64:    the bodies only: mn[i] = min(parent[i], parent[j] over the linked j) and, first_round, count as above
-struct Groups64Launch {
-  const void *posm = nullptr;   // [n_total] double4: x, y, z, m
-  const void *ppos = nullptr;   // [m] double4: x, y, z, unused; nullptr: the bodies themselves
+constexpr int kGroups64Width = 1;   // the float4 of a partial row: two int32, half a float4 unused
+struct Groups64Launch : RowScan64Launch {
   const int *parent = nullptr;  // [n_total]: every body's current parent label (the groups' pass)
-  void *part = nullptr;         // the partial rows of one slab
-  size_t part_elems = 0;        // the float4 `part` holds: at least probe_part_elems(n_total, m, 1), or nothing is launched
   int *mn = nullptr;            // [m]: the smallest parent among the row's own and its linked bodies' (the groups' pass)
   int *count = nullptr;         // [m]: the linked bodies
-  int n_total = 0, m = 0;
-  int lanes = 0;                // points per lane: 1 or 2; 0: hermite_block_lanes(m, 0).  It enters no result (the bodies: always 2)
   double r2 = 0.0;              // radius * radius: finite and >= 0, or nothing is launched
 };
 hipError_t launch_radius_counts_f64(const Groups64Launch &L, hipStream_t s);

@@ -10,11 +10,7 @@
 //   <., ., ., SELF = false>                 <- the rows are caller points (ipos[il], ivel[il]); NO body is dropped by index
 //   census_fold_f64_kernel<BOUND>           <- the chunks' rows taken in chunk order with strict <, from (+inf, -1)
 //   census_pair_parts / _fold_kernel        <- the smallest value over the rows and the lowest row that attains it, in a fixed order
-// A SIBLING of the potential's tile loop (kernels_pot64.hip), not a further form of it: jerk_tile64.h, snap_tile64.h,
-// kernels_points64.hip and kernels_pot64.hip stay as they are, and so does every kernel built from them
-// (profiles/census_f64_isa_compare.txt).  What it shares with pot_tile_f64_kernel is written out again here, operation for operation:
-// the chunks of probe_geometry(n_total), the double-buffered 256-body LDS tiles of (x, y, z, G m) — PARTNER: the velocity tile beside
-// it, 32 KiB a workgroup as the jerk —, two j-bodies per staged group read by broadcast, one or two rows per lane.
+// A row scan (scan_tile64.h) over tiles of (x, y, z, G m) — PARTNER: the velocity tile beside it, 32 KiB of LDS a workgroup as the jerk.
 // Each lane keeps (best, index) — PARTNER: and d2 — per row and updates them with compare and select in ASCENDING j, under strict <:
 // the lowest index wins a tie, a NaN is never chosen (< is false), nor is a d2 that is not finite (NEAREST: +inf < +inf is false;
 // PARTNER: the candidate must have d2 < +inf, which also keeps out the body whose position is NaN — its s2 > 0 is false, so its t
@@ -27,18 +23,13 @@
 // double (exact).  No scratch, no atomics.
 #include "kernels.h"
 
-#include <algorithm>
-
-#include "jerk_tile64.h"
+#include "scan_tile64.h"
 
 #pragma clang fp contract(off)
 
 namespace nbody {
 
 namespace {
-
-constexpr int kCensus64Ipt = 2;    // bodies per lane of the per-body forms, as the potential pass
-constexpr int kNearestRowWidth = 1, kPartnerRowWidth = 2;   // the float4 of a partial row: two doubles, four doubles
 
 // local row il = blockIdx.x * (kBlock * IPT) + t + k * kBlock — the lanes past m repeat row m - 1 and write nothing — is
 // SELF: body i_first + il of (ipos, ivel) (== posm, vel);  else: point il of (ipos, ivel) — against the bodies of chunk blockIdx.y
@@ -232,33 +223,28 @@ __global__ __launch_bounds__(kBlock) void census_pair_fold_kernel(const double *
 // bodies, or the staging area does not hold a slab's partial rows
 template <bool BOUND>
 hipError_t launch(const Census64Launch &L, hipStream_t s) {
-  constexpr int W = BOUND ? kPartnerRowWidth : kNearestRowWidth;
+  constexpr int W = BOUND ? kPartner64Width : kNearest64Width;
   const bool self = L.ppos == nullptr;
   if (L.m <= 0 || L.n_total <= 0 || !L.posm || !L.part || !L.index || !L.value || (self && L.m != L.n_total)) return hipErrorInvalidValue;
   if (BOUND && (!L.vel || !L.d2 || (!self && !L.pvel))) return hipErrorInvalidValue;
   if (L.part_elems < probe_part_elems(L.n_total, L.m, W)) return hipErrorInvalidValue;
   const bool soft = BOUND && L.eps2 > 0.0;                     // eps == 0: s2 is d2 itself
-  const int ipt = self ? kCensus64Ipt : hermite_block_lanes(L.m, L.lanes);
-  int j_split, j_chunk;
-  probe_geometry(L.n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(L.n_total, W);
-  for (size_t first = 0; first < (size_t)L.m; first += slab) {
-    const int m = (int)std::min(slab, (size_t)L.m - first);
-    const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
-    const double4 *posm = (const double4 *)L.posm, *vel = (const double4 *)L.vel;
+  const double4 *posm = (const double4 *)L.posm, *vel = (const double4 *)L.vel;
+  for_row_slabs64(L.n_total, L.m, W, self, L.lanes, [&](const RowSlab64 &b) {
     if (self) {
-      auto kernel = census_tile_f64_kernel<false, kCensus64Ipt, BOUND, true>;
-      if constexpr (BOUND) { if (soft) kernel = census_tile_f64_kernel<true, kCensus64Ipt, true, true>; }
-      hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, posm, vel, posm, vel, (double *)L.part, L.n_total, m, (int)first, j_chunk, L.G, L.eps2);
+      auto kernel = census_tile_f64_kernel<false, kScan64Ipt, BOUND, true>;
+      if constexpr (BOUND) { if (soft) kernel = census_tile_f64_kernel<true, kScan64Ipt, true, true>; }
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, posm, vel, posm, vel, (double *)L.part, L.n_total, b.m, (int)b.first, b.j_chunk,
+                         L.G, L.eps2);
     } else {
-      auto kernel = ipt == 2 ? census_tile_f64_kernel<false, 2, BOUND, false> : census_tile_f64_kernel<false, 1, BOUND, false>;
-      if constexpr (BOUND) { if (soft) kernel = ipt == 2 ? census_tile_f64_kernel<true, 2, true, false> : census_tile_f64_kernel<true, 1, true, false>; }
-      hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, posm, vel, (const double4 *)L.ppos + first,
-                         BOUND ? (const double4 *)L.pvel + first : nullptr, (double *)L.part, L.n_total, m, 0, j_chunk, L.G, L.eps2);
+      auto kernel = b.ipt == 2 ? census_tile_f64_kernel<false, 2, BOUND, false> : census_tile_f64_kernel<false, 1, BOUND, false>;
+      if constexpr (BOUND) { if (soft) kernel = b.ipt == 2 ? census_tile_f64_kernel<true, 2, true, false> : census_tile_f64_kernel<true, 1, true, false>; }
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, posm, vel, (const double4 *)L.ppos + b.first,
+                         BOUND ? (const double4 *)L.pvel + b.first : nullptr, (double *)L.part, L.n_total, b.m, 0, b.j_chunk, L.G, L.eps2);
     }
-    hipLaunchKernelGGL(census_fold_f64_kernel<BOUND>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
-                       L.index + first, L.value + first, BOUND ? L.d2 + first : nullptr);
-  }
+    hipLaunchKernelGGL(census_fold_f64_kernel<BOUND>, b.fold, dim3(kBlock), 0, s, (const double *)L.part, b.m, b.j_split, L.index + b.first,
+                       L.value + b.first, BOUND ? L.d2 + b.first : nullptr);
+  });
   return hipGetLastError();
 }
 

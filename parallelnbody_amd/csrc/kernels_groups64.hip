@@ -9,17 +9,14 @@
 //   <., ., ., SELF = false>                 <- the rows are caller points (ipos[il]); NO body is dropped by index
 //   groups_fold_f64_kernel                  <- the chunks' rows in chunk order: min of the minima, sum of the counts
 //   groups_iota / _hook / _compress / _members_count / _members_summary_kernel   <- the O(N) kernels of a round and of the summary
-// A SIBLING of the pair census's tile loop (kernels_census64.hip), not a further form of it: that file stays as it is, and so does every
-// kernel built from it (profiles/groups_f64_isa_compare.txt).  What it shares with census_tile_f64_kernel is written out again here: the
-// chunks of probe_geometry(n_total), the double-buffered 256-body LDS tiles, two j-bodies per staged group read by broadcast, one or two
-// rows per lane.  The tile's fourth component carries body j's current parent label (the low word of the double's bits, never computed
+// A row scan (scan_tile64.h).  The tile's fourth component carries body j's current parent label (the low word of the double's bits, never computed
 // with) where the census carries G m.  Each lane keeps per row an int32 minimum of the linked bodies' parents — from the row's own parent
 // — and an int32 count, updated with compare and select.  A NaN d2 fails <=, a +inf d2 never passes a finite r2: neither links.  The
 // candidates are the bodies j0 <= j < j1 of the chunk: the zero padding of a chunk's last tile is kept out BY INDEX (j < j1).  A
 // zero-mass body links like any other.  d2_ij and d2_ji come from the same operations on negated operands: the graph is undirected in
 // every bit.  A chunk's partial row is two int32 (minimum, count), 8 of the 16 bytes of a width-1 slot.  No scratch, no fp atomics.
 //
-// The groups are the connected components of the links, found in rounds the HOST drives (capi_hermite.hip): a pass and its fold give
+// The groups are the connected components of the links, found in rounds the HOST drives (capi_query64.hip): a pass and its fold give
 // every body the smallest parent among its linked bodies; the hook lowers the parent of the body's ROOT to it with an integer atomicMin
 // on a COPY of the parent array (integer min is order-independent: the same array whatever the order); the compression chases that copy
 // — read-only while it runs — to its fixed point for every body and writes the other array.  Parents never ascend (parent[i] <= i), so
@@ -27,18 +24,13 @@
 // another thread sets.
 #include "kernels.h"
 
-#include <algorithm>
-
-#include "jerk_tile64.h"
+#include "scan_tile64.h"
 
 #pragma clang fp contract(off)
 
 namespace nbody {
 
 namespace {
-
-constexpr int kGroups64Ipt = 2;      // bodies per lane of the per-body forms, as the census
-constexpr int kGroups64RowWidth = 1; // the float4 of a partial row: two int32, half a float4 unused
 
 // local row il = blockIdx.x * (kBlock * IPT) + t + k * kBlock — the lanes past m repeat row m - 1 and write nothing — is
 // SELF: body i_first + il of ipos (== posm);  else: point il of ipos — against the bodies of chunk blockIdx.y
@@ -203,52 +195,38 @@ __global__ __launch_bounds__(kBlock) void groups_members_summary_kernel(const in
 }
 
 bool bad(const Groups64Launch &L) {
-  return L.m <= 0 || L.n_total <= 0 || !L.posm || !L.part || !(L.r2 >= 0.0) || L.part_elems < probe_part_elems(L.n_total, L.m, kGroups64RowWidth);
+  return L.m <= 0 || L.n_total <= 0 || !L.posm || !L.part || !(L.r2 >= 0.0) || L.part_elems < probe_part_elems(L.n_total, L.m, kGroups64Width);
 }
 
-// the pass over the slabs and its fold; nothing is launched where an argument is missing, the bodies' form is asked for other than all
-// bodies, or the staging area does not hold a slab's partial rows
+// the pass over the slabs and its fold — at the bodies (MIN: their smallest linked parent; COUNT: their links) or, ppos given, the counts
+// at points; nothing is launched where an argument is missing, the bodies' form is asked for other than all bodies, or the staging area
+// does not hold a slab's partial rows
 template <bool MIN, bool COUNT>
-hipError_t launch_bodies(const Groups64Launch &L, hipStream_t s) {
-  if (bad(L) || L.ppos || L.m != L.n_total || (MIN && (!L.parent || !L.mn)) || (COUNT && !L.count)) return hipErrorInvalidValue;
-  int j_split, j_chunk;
-  probe_geometry(L.n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(L.n_total, kGroups64RowWidth);
+hipError_t launch(const Groups64Launch &L, hipStream_t s) {
+  const bool self = L.ppos == nullptr;
+  if (bad(L) || (self && L.m != L.n_total) || (MIN && (!self || !L.parent || !L.mn)) || (COUNT && !L.count)) return hipErrorInvalidValue;
   const double4 *posm = (const double4 *)L.posm;
-  for (size_t first = 0; first < (size_t)L.m; first += slab) {
-    const int m = (int)std::min(slab, (size_t)L.m - first);
-    const dim3 grid((m + kBlock * kGroups64Ipt - 1) / (kBlock * kGroups64Ipt), j_split);
-    hipLaunchKernelGGL((groups_tile_f64_kernel<kGroups64Ipt, MIN, COUNT, true>), grid, dim3(kBlock), 0, s, posm, L.parent, posm, (int *)L.part,
-                       L.n_total, m, (int)first, j_chunk, L.r2);
-    hipLaunchKernelGGL(groups_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const int *)L.part, m, j_split,
-                       MIN ? L.mn + first : nullptr, COUNT ? L.count + first : nullptr);
-  }
+  for_row_slabs64(L.n_total, L.m, kGroups64Width, self, L.lanes, [&](const RowSlab64 &b) {
+    if (self) {
+      hipLaunchKernelGGL((groups_tile_f64_kernel<kScan64Ipt, MIN, COUNT, true>), b.grid, dim3(kBlock), 0, s, posm, L.parent, posm, (int *)L.part,
+                         L.n_total, b.m, (int)b.first, b.j_chunk, L.r2);
+    } else if constexpr (!MIN) {
+      auto kernel = b.ipt == 2 ? groups_tile_f64_kernel<2, false, true, false> : groups_tile_f64_kernel<1, false, true, false>;
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, posm, (const int *)nullptr, (const double4 *)L.ppos + b.first, (int *)L.part,
+                         L.n_total, b.m, 0, b.j_chunk, L.r2);
+    }
+    hipLaunchKernelGGL(groups_fold_f64_kernel, b.fold, dim3(kBlock), 0, s, (const int *)L.part, b.m, b.j_split, MIN ? L.mn + b.first : nullptr,
+                       COUNT ? L.count + b.first : nullptr);
+  });
   return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_radius_counts_f64(const Groups64Launch &L, hipStream_t s) {
-  if (!L.ppos) return launch_bodies<false, true>(L, s);
-  if (bad(L) || !L.count) return hipErrorInvalidValue;
-  const int ipt = hermite_block_lanes(L.m, L.lanes);
-  int j_split, j_chunk;
-  probe_geometry(L.n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(L.n_total, kGroups64RowWidth);
-  for (size_t first = 0; first < (size_t)L.m; first += slab) {
-    const int m = (int)std::min(slab, (size_t)L.m - first);
-    const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
-    auto kernel = ipt == 2 ? groups_tile_f64_kernel<2, false, true, false> : groups_tile_f64_kernel<1, false, true, false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const int *)nullptr, (const double4 *)L.ppos + first,
-                       (int *)L.part, L.n_total, m, 0, j_chunk, L.r2);
-    hipLaunchKernelGGL(groups_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const int *)L.part, m, j_split,
-                       (int *)nullptr, L.count + first);
-  }
-  return hipGetLastError();
-}
+hipError_t launch_radius_counts_f64(const Groups64Launch &L, hipStream_t s) { return launch<false, true>(L, s); }
 
 hipError_t launch_groups_pass_f64(const Groups64Launch &L, bool first_round, hipStream_t s) {
-  return first_round ? launch_bodies<true, true>(L, s) : launch_bodies<true, false>(L, s);
+  return first_round ? launch<true, true>(L, s) : launch<true, false>(L, s);
 }
 
 hipError_t launch_groups_identity(int *parent, int n, hipStream_t s) {

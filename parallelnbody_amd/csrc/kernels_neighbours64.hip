@@ -7,11 +7,8 @@
 //   neighbours_fold_f64_kernel<K>                     <- the chunks' lists merged in chunk order under strict <, from K x (+inf, -1); the
 //                                                        first k entries out, and (rho, d2_k) of the density where asked for
 //   core_centre_parts / _fold, core_radius_parts / _fold_kernel   <- the two O(N) reductions of the density centre, in a fixed order
-// A SIBLING of census_tile_f64_kernel<., ., false, .> (the NEAREST form, kernels_census64.hip), not a further form of it: that file,
-// jerk_tile64.h, snap_tile64.h, kernels_points64.hip and kernels_pot64.hip stay as they are, and so does every kernel built from them
-// (profiles/neighbours_f64_isa_compare.txt).  What it shares with the nearest form is written out again here, operation for operation:
-// the chunks of probe_geometry(n_total), the double-buffered 256-body LDS tiles of (x, y, z, G m), two j-bodies per staged group read
-// by broadcast, one or two rows per lane, d2 = fma(dx, dx, fma(dy, dy, dz * dz)) never softened, contraction off.
+// A row scan (scan_tile64.h) over tiles of (x, y, z, G m) with the pair census's d2 = fma(dx, dx, fma(dy, dy, dz * dz)), never softened,
+// contraction off (the NEAREST form of kernels_census64.hip).
 // Where the nearest form keeps one (best, index) per row, a lane keeps K of them, sorted ascending, in registers (every index into the
 // list is a compile-time constant: no scratch), and a candidate enters by compare and select in ASCENDING j under strict <: it goes
 // behind every entry it does not beat, so equal d2 stay in index order and the list is the K smallest in lexicographic (d2, index).  A
@@ -32,9 +29,7 @@
 // device.  A chunk's partial row is K x (d2, index as a double: exact) — K float4.  No scratch, no atomics.
 #include "kernels.h"
 
-#include <algorithm>
-
-#include "jerk_tile64.h"
+#include "scan_tile64.h"
 
 #pragma clang fp contract(off)
 
@@ -42,7 +37,6 @@ namespace nbody {
 
 namespace {
 
-constexpr int kNeighbours64Ipt = 2;    // bodies per lane of the per-body form, as the census
 constexpr int kNeighbours64Queue = 4;  // candidates a lane holds back per row before the wave takes them into the lists
 
 // (dc, jc) into the ascending list (d, j) behind every entry it does not beat under strict <; the last entry drops out.  The list is
@@ -342,25 +336,20 @@ __global__ __launch_bounds__(kBlock) void core_radius_fold_kernel(const double *
 template <int K>
 void launch_width(const Neighbours64Launch &L, hipStream_t s) {
   const bool self = L.ppos == nullptr;
-  const int ipt = self ? kNeighbours64Ipt : hermite_block_lanes(L.m, L.lanes);
-  int j_split, j_chunk;
-  probe_geometry(L.n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(L.n_total, K);
   const double4 *posm = (const double4 *)L.posm;
-  for (size_t first = 0; first < (size_t)L.m; first += slab) {
-    const int m = (int)std::min(slab, (size_t)L.m - first);
-    const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
+  for_row_slabs64(L.n_total, L.m, K, self, L.lanes, [&](const RowSlab64 &b) {
     if (self) {
-      hipLaunchKernelGGL((neighbours_tile_f64_kernel<K, kNeighbours64Ipt, true>), grid, dim3(kBlock), 0, s, posm, posm, (double *)L.part,
-                         L.n_total, m, (int)first, j_chunk, L.G);
+      hipLaunchKernelGGL((neighbours_tile_f64_kernel<K, kScan64Ipt, true>), b.grid, dim3(kBlock), 0, s, posm, posm, (double *)L.part, L.n_total,
+                         b.m, (int)b.first, b.j_chunk, L.G);
     } else {
-      const auto kernel = ipt == 2 ? neighbours_tile_f64_kernel<K, 2, false> : neighbours_tile_f64_kernel<K, 1, false>;
-      hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, posm, (const double4 *)L.ppos + first, (double *)L.part, L.n_total, m, 0, j_chunk, L.G);
+      const auto kernel = b.ipt == 2 ? neighbours_tile_f64_kernel<K, 2, false> : neighbours_tile_f64_kernel<K, 1, false>;
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, posm, (const double4 *)L.ppos + b.first, (double *)L.part, L.n_total, b.m, 0,
+                         b.j_chunk, L.G);
     }
-    hipLaunchKernelGGL(neighbours_fold_f64_kernel<K>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, posm, m,
-                       j_split, L.k, L.index ? L.index + first * L.k : nullptr, L.d2 ? L.d2 + first * L.k : nullptr,
-                       L.rho ? L.rho + first : nullptr, L.rk2 ? L.rk2 + first : nullptr);
-  }
+    hipLaunchKernelGGL(neighbours_fold_f64_kernel<K>, b.fold, dim3(kBlock), 0, s, (const double *)L.part, posm, b.m, b.j_split, L.k,
+                       L.index ? L.index + b.first * L.k : nullptr, L.d2 ? L.d2 + b.first * L.k : nullptr, L.rho ? L.rho + b.first : nullptr,
+                       L.rk2 ? L.rk2 + b.first : nullptr);
+  });
 }
 
 }  // namespace

@@ -7,12 +7,8 @@
 //   <., ., ., SELF = false>              <- the rows are caller points (ipos[il]); NO pair is dropped by index
 //   pot_fold_f64_kernel                  <- the chunks' rows added from 0.0 in chunk order, phi = -P
 //   tidal_fold_f64_kernel                <- the same for the seven sums, then T_aa = S_aa - Q: xx, yy, zz, xy, xz, yz
-// A SIBLING of the jerk's tile loop, not a further form of it: jerk_tile64.h, snap_tile64.h and kernels_points64.hip stay as they are,
-// and so does every kernel built from them (profiles/pot_tidal_f64_isa_compare.txt).  What it shares with jerk_tile_f64_kernel is
-// written out again here, operation for operation in the same order: the chunks of probe_geometry(n_total), the double-buffered
-// 256-body LDS tiles of (x, y, z, G m) — no velocity tile: half the jerk's LDS, 16 KiB a workgroup —, two j-bodies per staged group,
-// one or two rows per lane, s2 = fma(dx, dx, fma(dy, dy, dz * dz [+ eps^2])) and rsq_dev.  Per pair, contraction off and every bracket
-// one fp64 operation:
+// A row scan (scan_tile64.h) over tiles of (x, y, z, G m) — no velocity tile: 16 KiB of LDS a workgroup —, with the jerk's
+// s2 = fma(dx, dx, fma(dy, dy, dz * dz [+ eps^2])) and rsq_dev.  Per pair, contraction off and every bracket one fp64 operation:
 //     t = (s2 > 0 [&& j != self]) ? rsq_dev(s2) : 0;  t2 = t * t;  q = (gm * t) * t2           (the jerk's q)
 //     potential:  P = fma(gm, t, P)
 //     tidal:      h = (3.0 * q) * t2;  hx = h * dx;  hy = h * dy;  hz = h * dz
@@ -28,18 +24,13 @@
 // Sxy, Sxz, Syz, Q and a pad nobody reads: four float4, probe_slab_points(n_total, 4)).  No scratch, no atomics.
 #include "kernels.h"
 
-#include <algorithm>
-
-#include "jerk_tile64.h"
+#include "scan_tile64.h"
 
 #pragma clang fp contract(off)
 
 namespace nbody {
 
 namespace {
-
-constexpr int kPot64Ipt = 2;    // bodies per lane of the per-body forms, as the jerk pass
-constexpr int kPotRowWidth = 1, kTidalRowWidth = 4;   // the float4 of a partial row: one double (half a float4), eight doubles
 
 // local row il = blockIdx.x * (kBlock * IPT) + t + k * kBlock — the lanes past m repeat row m - 1 and write nothing — is
 // SELF: body i_first + il of ipos (== posm);  else: point il of ipos — against the bodies of chunk blockIdx.y
@@ -178,35 +169,27 @@ __global__ __launch_bounds__(kBlock) void tidal_fold_f64_kernel(const double *__
 // bodies, or the staging area does not hold a slab's partial rows
 template <bool TIDAL>
 hipError_t launch(const Pot64Launch &L, hipStream_t s) {
-  constexpr int W = TIDAL ? kTidalRowWidth : kPotRowWidth;
+  constexpr int W = TIDAL ? kTidal64Width : kPot64Width;
   const bool self = L.ppos == nullptr;
   if (L.m <= 0 || L.n_total <= 0 || !L.posm || !L.part || !L.out || (self && L.m != L.n_total)) return hipErrorInvalidValue;
   if (L.part_elems < probe_part_elems(L.n_total, L.m, W)) return hipErrorInvalidValue;
   const bool soft = L.eps2 > 0.0;                              // eps == 0: the exact d == 0 rule, as the jerk pass
-  const int ipt = self ? kPot64Ipt : hermite_block_lanes(L.m, L.lanes);
-  int j_split, j_chunk;
-  probe_geometry(L.n_total, &j_split, &j_chunk);
-  const size_t slab = probe_slab_points(L.n_total, W);
-  for (size_t first = 0; first < (size_t)L.m; first += slab) {
-    const int m = (int)std::min(slab, (size_t)L.m - first);
-    const dim3 grid((m + kBlock * ipt - 1) / (kBlock * ipt), j_split);
+  for_row_slabs64(L.n_total, L.m, W, self, L.lanes, [&](const RowSlab64 &b) {
     if (self) {
-      const auto kernel = soft ? pot_tile_f64_kernel<true, kPot64Ipt, TIDAL, true> : pot_tile_f64_kernel<false, kPot64Ipt, TIDAL, true>;
-      hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.posm, (double *)L.part, L.n_total, m,
-                         (int)first, j_chunk, L.G, L.eps2);
+      const auto kernel = soft ? pot_tile_f64_kernel<true, kScan64Ipt, TIDAL, true> : pot_tile_f64_kernel<false, kScan64Ipt, TIDAL, true>;
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.posm, (double *)L.part, L.n_total,
+                         b.m, (int)b.first, b.j_chunk, L.G, L.eps2);
     } else {
-      const auto kernel = ipt == 2 ? (soft ? pot_tile_f64_kernel<true, 2, TIDAL, false> : pot_tile_f64_kernel<false, 2, TIDAL, false>)
-                                   : (soft ? pot_tile_f64_kernel<true, 1, TIDAL, false> : pot_tile_f64_kernel<false, 1, TIDAL, false>);
-      hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.ppos + first, (double *)L.part,
-                         L.n_total, m, 0, j_chunk, L.G, L.eps2);
+      const auto kernel = b.ipt == 2 ? (soft ? pot_tile_f64_kernel<true, 2, TIDAL, false> : pot_tile_f64_kernel<false, 2, TIDAL, false>)
+                                     : (soft ? pot_tile_f64_kernel<true, 1, TIDAL, false> : pot_tile_f64_kernel<false, 1, TIDAL, false>);
+      hipLaunchKernelGGL(kernel, b.grid, dim3(kBlock), 0, s, (const double4 *)L.posm, (const double4 *)L.ppos + b.first, (double *)L.part,
+                         L.n_total, b.m, 0, b.j_chunk, L.G, L.eps2);
     }
     if (TIDAL)
-      hipLaunchKernelGGL(tidal_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
-                         L.out + 6 * first);
+      hipLaunchKernelGGL(tidal_fold_f64_kernel, b.fold, dim3(kBlock), 0, s, (const double *)L.part, b.m, b.j_split, L.out + 6 * b.first);
     else
-      hipLaunchKernelGGL(pot_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
-                         L.out + first);
-  }
+      hipLaunchKernelGGL(pot_fold_f64_kernel, b.fold, dim3(kBlock), 0, s, (const double *)L.part, b.m, b.j_split, L.out + b.first);
+  });
   return hipGetLastError();
 }
 

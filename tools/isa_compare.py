@@ -12,6 +12,9 @@ A kernel whose template arguments changed otherwise is paired by hand: --pair 'n
 names as this tool prints them).
 
     python3 tools/isa_compare.py OLD.o NEW.o [--only SUBSTRING] [--pair OLD=NEW ...]   # exit code 1 if a pair differs or a kernel has no partner
+
+--mask-registers: a pair whose streams differ, but are equal once every register number — scalar, vector or accumulator, single or a
+range — is replaced by a placeholder, is printed as `same instructions, registers differ` and does not count as differing.
 """
 import argparse
 import os
@@ -45,6 +48,11 @@ def kernels(obj, workdir):
     return out
 
 
+def masked(ins):
+    """the instruction lines with register numbers replaced: v14 -> vN, s[10:11] -> s[N]"""
+    return [re.sub(r"\b([vsa])(?:\d+|\[\d+:\d+\])", lambda m: m.group(1) + ("N" if m.group(0)[1] != "[" else "[N]"), ln) for ln in ins]
+
+
 def base(name):
     """(name without return type and parameters, template arguments or None)"""
     name = name.replace("(anonymous namespace)::", "").split("(")[0]   # (nbody::(anonymous namespace)::k<..>(..) is nbody::k<..>)
@@ -73,6 +81,7 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--only", default="", help="compare the kernels whose name holds this")
     ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW", help="the NEW kernel of this name is the OLD kernel of that name")
+    ap.add_argument("--mask-registers", action="store_true", help="a pair that differs in register numbers alone does not count as differing")
     a = ap.parse_args()
     renamed = {new: old for old, new in (p.split("=", 1) for p in a.pair)}
     with tempfile.TemporaryDirectory() as t_old, tempfile.TemporaryDirectory() as t_new:
@@ -93,9 +102,11 @@ def main():
             print(f"{k}: only in the {'old' if k in old else 'new'} object")
             bad += 1
             continue
-        same = old[k] == new[k]
-        print(f"{k}: {len(old[k])} / {len(new[k])} instructions, {'identical' if same else 'DIFFERENT'}")
-        bad += not same
+        verdict = "identical" if old[k] == new[k] else "DIFFERENT"
+        if verdict == "DIFFERENT" and a.mask_registers and masked(old[k]) == masked(new[k]):
+            verdict = "same instructions, registers differ"
+        print(f"{k}: {len(old[k])} / {len(new[k])} instructions, {verdict}")
+        bad += verdict == "DIFFERENT"
     return 1 if bad else 0
 
 
