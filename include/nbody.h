@@ -175,6 +175,10 @@ NBODY_AMD_API int nbody_device_count(void);
 
 /* ---- state in ----------------------------------------------------------------------------- */
 
+/* Every call of this section is ordered behind whatever the context still has in flight on its stream (nbody_step returns before its
+ * steps have run): the upload lands after the last queued update, whichever type the caller's arrays have, and the call returns once
+ * the new state is on the device — the caller's arrays are its own again. */
+
 /* TArray<FParticle> contents (OctreeSearch.h:8-18,118): all n_total records, `stride` bytes apart (>= 40). */
 NBODY_AMD_API int nbody_set_particles(nbody_ctx *ctx, const void *aos, size_t stride, int32_t n);
 

@@ -286,7 +286,9 @@ int note_masses(nbody_ctx *c, const T *posm4) {
   return NBODY_OK;
 }
 
-// Upload host SoA state given as T (float or double); converts to the context's precision.
+// Upload host SoA state given as T (float or double); converts to the context's precision.  Every copy goes through the context's
+// stream, behind whatever steps are still in flight on it: a copy on the null stream would not wait for them (the stream is
+// non-blocking), and their updates would land on top of the new state.
 // keep_history: the records of a running simulation edited by the host (nbody_push_particles) — the step count and the
 // Barnes-Hut root centre (the previous tree's CoM) stay what they are.
 template <typename T>
@@ -295,22 +297,25 @@ int upload_soa(nbody_ctx *c, const T *posm4, const T *vel4, bool keep_history = 
   const int n = c->p.n_total, ib = c->p.i_begin, ic = c->p.i_count;
   const bool ctx64 = c->p.precision == NBODY_PREC_F64;
   const bool same = ctx64 == (sizeof(T) == 8);
+  // both copies, then ONE wait whatever they returned: a copy that may still be reading its source never outlives it
+  auto send = [&](const void *p, size_t p_bytes, const void *v, size_t v_bytes) -> hipError_t {
+    const hipError_t e1 = hipMemcpyAsync(c->posm, p, p_bytes, hipMemcpyHostToDevice, c->stream);
+    const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(c->vel, v, v_bytes, hipMemcpyHostToDevice, c->stream) : e1;
+    const hipError_t e3 = hipStreamSynchronize(c->stream);
+    return e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3);
+  };
   if (same) {
-    HIP_TRY(c, hipMemcpyAsync(c->posm, posm4, (size_t)n * c->elem, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->vel, vel4 + 4 * (size_t)ib, (size_t)ic * c->elem, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, send(posm4, (size_t)n * c->elem, vel4 + 4 * (size_t)ib, (size_t)ic * c->elem));
   } else if (ctx64) {
     std::vector<double> tp((size_t)n * 4), tv((size_t)ic * 4);
     convert4(posm4, tp.data(), (size_t)n, false);
     convert4(vel4 + 4 * (size_t)ib, tv.data(), (size_t)ic, true);
-    HIP_TRY(c, hipMemcpy(c->posm, tp.data(), tp.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->vel, tv.data(), tv.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, send(tp.data(), tp.size() * 8, tv.data(), tv.size() * 8));
   } else {
     std::vector<float> tp((size_t)n * 4), tv((size_t)ic * 4);
     convert4(posm4, tp.data(), (size_t)n, false);
     convert4(vel4 + 4 * (size_t)ib, tv.data(), (size_t)ic, true);
-    HIP_TRY(c, hipMemcpy(c->posm, tp.data(), tp.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->vel, tv.data(), tv.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, send(tp.data(), tp.size() * 4, tv.data(), tv.size() * 4));
   }
   HIP_TRY(c, hipMemsetAsync(c->acc, 0, (size_t)ic * c->elem, c->stream));
   { const int rc = note_masses(c, posm4); if (rc) return rc; }
@@ -736,6 +741,7 @@ int set_particles(nbody_ctx *c, const void *aos, size_t stride, int32_t n, bool 
     acc[4 * (size_t)i + 0] = q.Acceleration[0]; acc[4 * (size_t)i + 1] = q.Acceleration[1];
     acc[4 * (size_t)i + 2] = q.Acceleration[2]; acc[4 * (size_t)i + 3] = 0.f;
   }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));                     // (upload_soa's clearing of c->acc runs on the stream)
   if (c->p.precision == NBODY_PREC_F64) {
     std::vector<double> a64(acc.begin(), acc.end());
     HIP_TRY(c, hipMemcpy(c->acc, a64.data(), a64.size() * 8, hipMemcpyHostToDevice));

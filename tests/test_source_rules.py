@@ -72,6 +72,71 @@ def test_memsets_on_the_null_stream_are_waited_for_before_the_function_returns()
     assert checked >= 2          # nbody_create and bh_create_state at least
 
 
+# functions whose blocking hipMemcpy( needs no wait in front of it: by name, each with its reason
+BLOCKING_COPY_EXEMPT = {
+    "nbody_create": "creation: the lists of the plan and the clock word go into buffers allocated in this function, before the context's "
+                    "stream has carried any work",
+}
+# what queues work between a wait and a copy: a kernel launch (a launcher of kernels.h, a launch written out, this library's own queue_* /
+# run_* / timed_launch helpers) or any ...Async( call
+QUEUES_WORK = re.compile(r"\w*Async\(|<<<|hipLaunchKernelGGL|\blaunch_\w+\(|\bqueue_\w+\(|\brun_\w+\(|\btimed_launch\(")
+
+
+def blocking_copy_faults(text, where):
+    """Every blocking hipMemcpy( of `text` that has no hipStreamSynchronize( earlier in its function, or has work queued between the
+    last one and itself: (messages, copies looked at, names of the exempt functions in which a blocking copy was passed over)."""
+    text = re.sub(r"//[^\n]*", "", text)
+    faults, checked, exempt_used = [], 0, set()
+    for a, b in _functions(text):
+        body = text[a:b]
+        head = body[:body.index("(")] if "(" in body else body
+        fn = head.split()[-1].lstrip("*&") if head.split() else ""
+        for m in re.finditer(r"\bhipMemcpy\(", body):
+            if fn in BLOCKING_COPY_EXEMPT:
+                exempt_used.add(fn)
+                continue
+            checked += 1
+            line = body[:m.start()].count("\n")
+            # the last wait whose block is still open at the copy: one in a branch that has closed since (an `if` arm beside the
+            # copy's own) is not on the copy's path
+            wait = body.rfind("hipStreamSynchronize(", 0, m.start())
+            while wait >= 0:
+                depth, low = 0, 0
+                for ch in body[wait:m.start()]:
+                    depth += (ch == "{") - (ch == "}")
+                    low = min(low, depth)
+                if low == 0:
+                    break
+                wait = body.rfind("hipStreamSynchronize(", 0, wait)
+            if wait < 0:
+                faults.append(f"{where}: {fn}: blocking hipMemcpy( (line {line} of the function) with no hipStreamSynchronize( before it in "
+                              "the function: it runs on the null stream, which the context's non-blocking stream does not wait for")
+                continue
+            between = QUEUES_WORK.search(body, wait + len("hipStreamSynchronize("), m.start())
+            if between:
+                faults.append(f"{where}: {fn}: '{between.group(0)}' queues work between the last hipStreamSynchronize( and the blocking "
+                              f"hipMemcpy( (line {line} of the function)")
+    return faults, checked, exempt_used
+
+
+def test_blocking_copies_wait_for_the_stream_first():
+    # hipMemcpy( runs on the NULL stream and the contexts' streams are non-blocking: a copy into or out of a buffer that queued work
+    # still writes races with it unless the function has waited for the stream and queued nothing since.  upload_soa's converting
+    # branches did not (an fp64 context given floats, an fp32 one given doubles): steps in flight wrote their update on top of the
+    # uploaded state.  The rule is per function: a wait somewhere up the call chain does not count (set_particles relied on
+    # upload_soa's).
+    faults, checked, exempt_used = [], 0, set()
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp"))):
+        f, k, used = blocking_copy_faults(open(path).read(), os.path.basename(path))
+        faults += f
+        checked += k
+        exempt_used |= used
+    assert not faults, "\n".join(faults)
+    assert checked >= 10, checked      # (the rule cannot pass on nothing)
+    # every exemption is still needed: a function of that name, in a .hip or .cpp file, with a blocking copy the rule passed over
+    assert exempt_used == set(BLOCKING_COPY_EXEMPT), sorted(set(BLOCKING_COPY_EXEMPT) - exempt_used)
+
+
 def test_no_stream_is_created_blocking_by_accident():
     # (the rule above rests on it: the streams are non-blocking on purpose — a blocking stream would serialise with torch's
     # null-stream work in the host process)
