@@ -1,6 +1,6 @@
 // The Hermite calls of the C-ABI (include/nbody.h) on fp64 contexts: fourth- and sixth-order shared steps, their block sessions and their
 // fp64 tracers, beside the snap and the jerk and snap at fp64 points they are built on (the other fp64 queries: capi_query64.hip).  Host
-// C++ like capi.hip, whose helpers it shares (capi_common.h).  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
+// C++ like capi.hip; what it shares with the other host units: capi_common.h.  One driver, written once as function templates over an order's traits (Order4, Order6: what truly differs between
 // the two schemes, each rule with its comment — DESIGN.md has the table); the extern "C" functions pick the instantiation.
 #include <algorithm>
 #include <cmath>
@@ -12,7 +12,7 @@
 
 namespace {
 
-using nbody::check_ready; using nbody::ensure_jerk64; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::fail; using nbody::gather_double4; using nbody::points64_part_holds; using nbody::points64_ready; using nbody::stage_points64; using nbody::stage_to_host; using nbody::Staged64; using nbody::hermite_invalidate; using nbody::hermite_invalidate_order; using nbody::HermiteBlockSession; using nbody::HermiteCache; using nbody::kSnapRowWidth; using nbody::multi_unsupported; using nbody::queue_body_jerk; using nbody::read_energy; using nbody::scatter_records; using nbody::timed_launch;
+using nbody::check_ready; using nbody::ensure_rows64; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::fail; using nbody::gather4; using nbody::points64_part_holds; using nbody::points64_ready; using nbody::stage_points64; using nbody::stage_to_host; using nbody::Staged64; using nbody::hermite_invalidate; using nbody::hermite_invalidate_order; using nbody::HermiteBlockSession; using nbody::HermiteCache; using nbody::kSnapRowWidth; using nbody::multi_unsupported; using nbody::queue_body_jerk; using nbody::read_energy; using nbody::scatter_records; using nbody::timed_launch;
 
 // where the stepping exists — fp64 state, one device, all bodies (such contexts are at theta == 0) — and when: a state set, no step half done
 int hermite_ready(nbody_ctx *c, const char *who) {
@@ -875,7 +875,7 @@ int nbody_get_snap_f64(nbody_ctx *c, const double *acc_in, size_t acc_in_stride,
     for (size_t i = 0; i < n; ++i) { memcpy(h + 4 * i, (const char *)acc_in + i * acc_in_stride, 24); h[4 * i + 3] = 0.0; }
     HIP_TRY(c, hipMemcpyAsync(ain, h, n * 32, hipMemcpyHostToDevice, c->stream));
   } else {                                                         // the live state's own accelerations, unrounded: the fp64 jerk pass first
-    if ((rc = ensure_jerk64(c))) return rc;
+    if ((rc = ensure_rows64(c, &c->jerk64, 6))) return rc;
     if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
     ain = (double *)c->jerk64; ain_stride = 6;
   }
@@ -902,7 +902,7 @@ int nbody_jerk_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   if ((rc = stage_points64(c, pos, pos_stride, vel, vel_stride, true, m, m * 48, &s))) return rc;
   double *d = s.d, *h = s.h + s.skip;
   if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
-  if ((rc = stage_to_host(c, s.skip, m * 48))) return rc;
+  if ((rc = stage_to_host(c, s.skip * 8, m * 48))) return rc;
   if (acc) scatter_records(acc, acc_stride, h, 24, m, 48);
   if (jerk) scatter_records(jerk, jerk_stride, h + 3, 24, m, 48);
   return NBODY_OK;
@@ -920,7 +920,7 @@ int nbody_snap_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   const size_t m = (size_t)n;
   if ((rc = ensure_probe_part(c, n, 3))) return rc;
   if ((rc = ensure_probe_part(c, n, kSnapRowWidth))) return rc;
-  if ((rc = ensure_jerk64(c))) return rc;
+  if ((rc = ensure_rows64(c, &c->jerk64, 6))) return rc;
   Staged64 s;                                                      // the points and their velocities, behind them six doubles (a, j), nine (a, j, s)
   if ((rc = stage_points64(c, pos, pos_stride, vel, vel_stride, true, m, m * 120, &s))) return rc;
   double *d = s.d, *h = s.h + 14 * m;
@@ -928,7 +928,7 @@ int nbody_snap_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, const 
   if ((rc = queue_body_jerk(c, (double *)c->jerk64, nullptr))) return rc;
   if ((rc = points64_jerk(c, c->posm, c->vel, d, d + 4 * m, n, d + 8 * m))) return rc;
   if ((rc = points64_snap(c, c->posm, c->vel, (const double *)c->jerk64, 6, d, d + 4 * m, d + 8 * m, 6, n, d + 14 * m))) return rc;
-  if ((rc = stage_to_host(c, 14 * m, m * 72))) return rc;
+  if ((rc = stage_to_host(c, 14 * m * 8, m * 72))) return rc;
   if (acc) scatter_records(acc, acc_stride, h, 24, m, 72);
   if (jerk) scatter_records(jerk, jerk_stride, h + 3, 24, m, 72);
   if (snap) scatter_records(snap, snap_stride, h + 6, 24, m, 72);
@@ -960,8 +960,8 @@ int nbody_set_tracers_f64(nbody_ctx *c, const double *pos, size_t pos_stride, co
   if ((rc = ensure_stage(c, m * 64))) return rc;
   HIP_TRY(c, hipMalloc(&c->tr64, 24 * m * sizeof(double)));
   double *h = (double *)c->h_stage;
-  gather_double4(h, pos, pos_stride, m);
-  gather_double4(h + 4 * m, vel, vel_stride, m);
+  gather4(h, pos, pos_stride, m);
+  gather4(h + 4 * m, vel, vel_stride, m);
   HIP_TRY(c, hipMemsetAsync(c->tr64, 0, 24 * m * sizeof(double), c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->tr64, h, m * 64, hipMemcpyHostToDevice, c->stream));   // pos and vel lie side by side
   HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,6 +1,6 @@
 // The fp64 queries of the C-ABI (include/nbody.h) on fp64 contexts that are not Hermite stepping: the potential and tidal tensor
 // (kernels_pot64.hip), the pair census (kernels_census64.hip), the neighbour census (kernels_neighbours64.hip), the radial census
-// (kernels_radial64.hip) and the group census (kernels_groups64.hip).  Host C++ like capi.hip, whose helpers it shares (capi_common.h).
+// (kernels_radial64.hip) and the group census (kernels_groups64.hip).  Host C++ like capi.hip; what it shares with the other host units: capi_common.h.
 // Written once here: the row pass (row_pass64) every N^2 query is queued through, and the staged points (Staged64) of every *_at_f64 call.
 #include <cmath>
 #include <cstdio>
@@ -26,28 +26,19 @@ int points64_ready(nbody_ctx *c, const char *who) {
   return NBODY_OK;
 }
 
-// n records of three doubles, `stride` bytes apart (NULL: zeros), as double4 rows with a fourth component of 0
-void gather_double4(double *dst, const double *src, size_t stride, size_t n) {
-  for (size_t k = 0; k < n; ++k) {
-    if (src) memcpy(dst + 4 * k, (const char *)src + k * stride, 24);
-    else     dst[4 * k] = dst[4 * k + 1] = dst[4 * k + 2] = 0.0;
-    dst[4 * k + 3] = 0.0;
-  }
-}
-
 int stage_points64(nbody_ctx *c, const double *pos, size_t pos_stride, const double *vel, size_t vel_stride, bool with_vel, size_t m,
                    size_t result_bytes, Staged64 *s) {
   s->m = m; s->skip = (with_vel ? 8 : 4) * m;
   if (int rc = ensure_stage(c, s->skip * sizeof(double) + result_bytes)) return rc;
   s->h = (double *)c->h_stage; s->d = (double *)c->d_stage;
-  gather_double4(s->h, pos, pos_stride, m);
-  if (with_vel) gather_double4(s->h + 4 * m, vel, vel_stride, m);
+  gather4(s->h, pos, pos_stride, m);
+  if (with_vel) gather4(s->h + 4 * m, vel, vel_stride, m);
   HIP_TRY(c, hipMemcpyAsync(s->d, s->h, s->skip * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return NBODY_OK;
 }
 
 int stage_to_host(nbody_ctx *c, size_t first, size_t bytes) {
-  HIP_TRY(c, hipMemcpyAsync((double *)c->h_stage + first, (double *)c->d_stage + first, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync((char *)c->h_stage + first, (const char *)c->d_stage + first, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return NBODY_OK;
 }
@@ -62,7 +53,7 @@ int points64_part_holds(nbody_ctx *c, int m, int width, const char *what) {
 
 namespace {
 
-using nbody::check_ready; using nbody::ensure_probe_part; using nbody::ensure_stage; using nbody::fail; using nbody::gather_double4; using nbody::points64_part_holds; using nbody::points64_ready; using nbody::read_energy; using nbody::scatter_records; using nbody::stage_points64; using nbody::stage_to_host; using nbody::Staged64; using nbody::timed_launch;
+using nbody::check_ready; using nbody::ensure_probe_part; using nbody::ensure_rows64; using nbody::tidal_time_out; using nbody::ensure_stage; using nbody::fail; using nbody::points64_part_holds; using nbody::points64_ready; using nbody::read_energy; using nbody::scatter_records; using nbody::stage_points64; using nbody::stage_to_host; using nbody::Staged64; using nbody::timed_launch;
 
 // ---- the row pass: every N^2 query of this unit (kernels.h: RowScan64Launch) ----
 // rows — m points (ppos: double4 each, device) or, ppos == nullptr, the bodies themselves with each left out by index — against the LIVE
@@ -100,7 +91,7 @@ int pot64_at(nbody_ctx *c, const char *who, bool tidal, const double *pos, size_
   Staged64 s;
   if ((rc = stage_points64(c, pos, pos_stride, nullptr, 0, false, (size_t)n, (size_t)n * doubles * 8, &s))) return rc;
   if ((rc = pot64_pass(c, tidal, s.d, n, s.d + s.skip))) return rc;
-  if ((rc = stage_to_host(c, s.skip, s.m * doubles * 8))) return rc;
+  if ((rc = stage_to_host(c, s.skip * 8, s.m * doubles * 8))) return rc;
   scatter_records(out, out_stride, s.h + s.skip, doubles * 8, s.m);
   return NBODY_OK;
 }
@@ -139,7 +130,7 @@ constexpr size_t kCensusRowBytes = 20;   // of the staging pair, per row
 
 // rows m of the staging pair to the caller's arrays: value and d2 are the nearest form's one array (d2), the partner form's two
 int census64_out(nbody_ctx *c, bool bound, size_t skip, size_t m, int32_t *index, double *energy, double *d2) {
-  if (int rc = stage_to_host(c, skip, m * kCensusRowBytes)) return rc;
+  if (int rc = stage_to_host(c, skip * 8, m * kCensusRowBytes)) return rc;
   const CensusRows h = census_rows(c->h_stage, skip, m);
   if (index) memcpy(index, h.index, m * 4);
   if (bound) {
@@ -210,7 +201,7 @@ int neighbours64_lists(nbody_ctx *c, int k, const void *ppos, size_t skip, size_
   double *dd2 = (double *)c->d_stage + skip;
   int *dindex = (int *)(dd2 + m * k);
   if (int rc = neighbours64_pass(c, k, ppos, (int)m, dindex, dd2, nullptr, nullptr)) return rc;
-  if (int rc = stage_to_host(c, skip, m * k * 12)) return rc;
+  if (int rc = stage_to_host(c, skip * 8, m * k * 12)) return rc;
   const double *hd2 = (const double *)c->h_stage + skip;
   if (d2) memcpy(d2, hd2, m * k * 8);
   if (index) memcpy(index, hd2 + m * k, m * k * 4);
@@ -302,16 +293,9 @@ int nbody_tidal_time_f64(nbody_ctx *c, double *t_min, int32_t *body) {
   int rc = points64_ready(c, who);
   if (rc) return rc;
   if (!t_min && !body) return fail(c, NBODY_ERR_INVALID, "%s: both outputs are null", who);
-  const int n = c->p.n_total;
-  if (!c->tidal64) HIP_TRY(c, hipMalloc(&c->tidal64, (6 * (size_t)n + 2 * (size_t)nbody::energy_fast_slots(n)) * sizeof(double)));
-  double *t64 = (double *)c->tidal64, *partials = t64 + 6 * (size_t)n;
-  if ((rc = pot64_pass(c, true, nullptr, n, t64))) return rc;
-  HIP_TRY(c, nbody::launch_tidal_time(t64, n, partials, (double *)c->scratch, c->stream));
-  double n2 = 0.0, at = 0.0;
-  if ((rc = read_energy(c, &n2, &at))) return rc;              // (the scratch's two doubles: the largest n2, its body)
-  if (t_min) *t_min = n2 == 0.0 ? HUGE_VAL : (std::isfinite(n2) ? 1.0 / std::sqrt(std::sqrt(n2)) : 0.0);   // nbody_tidal_time's rule
-  if (body) *body = (int32_t)at;
-  return NBODY_OK;
+  if ((rc = ensure_rows64(c, &c->tidal64, 6))) return rc;
+  if ((rc = pot64_pass(c, true, nullptr, c->p.n_total, (double *)c->tidal64))) return rc;
+  return tidal_time_out(c, t_min, body);
 }
 
 int nbody_get_nearest_f64(nbody_ctx *c, int32_t *index, double *d2) { return census64_get(c, "nbody_get_nearest_f64", false, index, nullptr, d2); }
@@ -510,7 +494,7 @@ int nbody_radius_counts_at_f64(nbody_ctx *c, const double *pos, size_t pos_strid
   Staged64 s;
   if ((rc = stage_points64(c, pos, pos_stride, nullptr, 0, false, (size_t)n, (size_t)n * 4, &s))) return rc;
   if ((rc = groups64_pass(c, r2, s.d, n, nullptr, false, nullptr, (int *)(s.d + s.skip)))) return rc;
-  if ((rc = stage_to_host(c, s.skip, s.m * 4))) return rc;
+  if ((rc = stage_to_host(c, s.skip * 8, s.m * 4))) return rc;
   memcpy(count, s.h + s.skip, s.m * 4);
   return NBODY_OK;
 }

@@ -1,5 +1,6 @@
-// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (capi.hip, capi_hermite.hip, capi_query64.hip, bh_driver.hip) share: error
-// texts, the device made current, the kernel timers.
+// The context behind the C-ABI's opaque nbody_ctx and what the host files that work on one (the C-ABI's units capi.hip, capi_state.hip,
+// capi_step.hip, capi_query.hip, capi_query64.hip, capi_hermite.hip — capi_common.h says which holds what — and bh_driver.hip) share:
+// error texts, the device made current, the kernel timers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,7 +74,9 @@ struct nbody_ctx {
   void *posm = nullptr, *vel = nullptr, *acc = nullptr, *accp = nullptr;
   void *posm_alt = nullptr;    // small systems: second position buffer of the one-launch step (swapped with posm)
   bool own_posm = false, own_vel = false, own_acc = false;
-  void *d_stage = nullptr, *h_stage = nullptr;   // renderer hand-off staging (device repack target, pinned mirror)
+  // the one staging pair (ensure_stage): the frame's FParticle records, the per-body getters' rows, every point query's points and results —
+  // on the device, and its pinned mirror.  Only calls that wait for their own work before they return use it.
+  void *d_stage = nullptr, *h_stage = nullptr;
   size_t stage_bytes = 0;
   void *scratch = nullptr;     // 64 B device scratch (bounds bits, energy sums)
   void *h_scratch = nullptr;   // pinned mirror
@@ -122,13 +125,11 @@ struct nbody_ctx {
   void *bh_acc = nullptr;      // [i_count] float4: the walk's output, summed (j_split = 1) by update_kernel
   struct { int queued = 0; bool whole = false; } bh_batch;   // what bh_queue_frame queued since the last bh_collect_frames (whole: frames, not a force-only pass)
   // massless points in the bodies' field (kernels_probe.hip; theta > 0: bh_probe_walk): the tracers the steps carry along
-  // (nbody_set_tracers) and the staging of nbody_field_at, grown on demand
+  // (nbody_set_tracers)
   int tr_n = 0;
   void *tr_pos = nullptr, *tr_vel = nullptr, *tr_acc = nullptr;   // [tr_n] float4 each
   void *probe_part = nullptr;  // the j chunks' partial rows of one slab of points (theta == 0), shared by tracers and queries
   size_t probe_part_elems = 0;
-  void *probe_dev = nullptr, *probe_host = nullptr;   // the point queries: probe_cap units of 32 bytes — the points as float4, behind them their results — on the device, and its pinned mirror
-  size_t probe_cap = 0;
   void *tidal64 = nullptr;     // nbody_tidal_time / nbody_tidal_time_f64: [n_total][6] double, the bodies' unrounded tidal tensors, then the reduction's workgroup pairs
   void *jerk64 = nullptr;      // nbody_get_jerk_f64 / nbody_jerk_time: [n_total][6] double, the bodies' unrounded (a, j), then the reduction's workgroup pairs
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
@@ -239,9 +240,14 @@ int timed_launch(nbody_ctx *c, int which, Launch &&launch, bool counts = true, b
   }
   EventPair ev = t.pool.back();
   t.pool.pop_back();
-  HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-  if (int rc = launch()) return rc;
-  HIP_TRY(c, hipEventRecord(ev.b, c->stream));
+  // a pass that fails to queue, or whose second stamp does, is not counted: its pair goes back to the pool (which nbody_destroy empties)
+  const int rc = [&]() -> int {
+    HIP_TRY(c, hipEventRecord(ev.a, c->stream));
+    if (int launch_rc = launch()) return launch_rc;
+    HIP_TRY(c, hipEventRecord(ev.b, c->stream));
+    return NBODY_OK;
+  }();
+  if (rc) { t.pool.push_back(ev); return rc; }
   ev.counts = counts;
   t.pending.push_back(ev);
   return may_drain ? timer_drain_at_cap(c, which) : NBODY_OK;

@@ -181,6 +181,53 @@ def test_after_a_step_the_last_tree_is_that_of_the_positions_before_its_update(n
     assert got.tobytes() == ref.tobytes()
 
 
+# ---- the frame's records and the queries share one staging pair ------------------------------------------------------------------
+
+@pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
+@pytest.mark.parametrize("theta", [0.0, 1.0])
+def test_queries_between_frames_disturb_neither(nb, theta, pinned):
+    """nbody_tick's FParticle records (theta = 0: the one-launch step's mirror; theta = 1: written by the walk through a mapped pointer)
+    and the point queries go through the same staging pair.  Twin A asks between its frames — 8 points first, then 8192, whose
+    8192 x 56 bytes (jerk_at) outgrow the 80 KB the records need, so the pair is reallocated between two frames —, twin B only after
+    them: every frame's records and Size are the same bytes, and each of A's answers is that of a fresh context stepped to the same
+    state with step() alone."""
+    n, dt = 2000, 0.01
+    posm, vel = bodies(nb, n)
+    few, many = probes_for(posm[:, :3], 8), probes_for(posm[:, :3], 8192)
+    pvel = np.random.default_rng(11).uniform(-50, 50, many.shape).astype(np.float32)
+    queries = [lambda e: [e.potential_at(few)], lambda e: list(e.jerk_at(many, pvel)), lambda e: [e.field_at(many)]]
+
+    def run(ask_between):
+        frames, answers = [], []
+        with nb.NBodyEngine(n, theta=theta) as e:
+            e.set_state(posm, vel)
+            out = np.zeros(n, nb.PARTICLE_DTYPE)
+            if pinned:
+                e.pin(out)
+            for q in queries:
+                size, rec = e.tick(dt, out=out)
+                assert rec is out
+                frames.append((np.float32(size).tobytes(), out.tobytes()))
+                if ask_between:
+                    answers.append([a.tobytes() for a in q(e)])
+            if not ask_between:
+                answers = [[a.tobytes() for a in q(e)] for q in queries]
+        return frames, answers
+
+    frames_a, answers_a = run(True)
+    frames_b, answers_b = run(False)
+    for k, (fa, fb) in enumerate(zip(frames_a, frames_b)):
+        assert fa[0] == fb[0], f"frame {k}: Size differs between the twins"
+        assert fa[1] == fb[1], f"frame {k}: the records differ between the twins"
+    assert answers_a[2] == answers_b[2]                            # (the one query both twins ask at the same state)
+    for k, q in enumerate(queries):
+        with nb.NBodyEngine(n, theta=theta) as e:
+            e.set_state(posm, vel)
+            for _ in range(k + 1):
+                e.step(dt, 1)
+            assert [a.tobytes() for a in q(e)] == answers_a[k], f"query {k}: not what a fresh context at the same state answers"
+
+
 # ---- errors ----------------------------------------------------------------------------------------------------------------------
 
 def test_errors(nb):

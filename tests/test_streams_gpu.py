@@ -451,10 +451,10 @@ def test_bind_device_state_behind_a_load(rigs, key):
 
 @pytest.mark.parametrize("variant", ["f32", "f32-tracers", "f64"])
 def test_staging_that_grows_behind_a_load(rigs, variant):
-    """A query behind the load that needs larger partial rows (ensure_probe_part), a larger point staging (ensure_probe_staging) and a
-    larger staging pair (ensure_stage) than any call before it — also with fp32 tracers, whose pass in the load reads the partial rows.
-    By the code every one of these either waits for the stream before it frees (the first two) or is only used by calls that wait for
-    their own work before they return (the staging pair); this confirms the order, on contexts that have made only small calls."""
+    """A query behind the load that needs larger partial rows (ensure_probe_part) and a larger staging pair (ensure_stage: the points
+    and results of every point query, the records of particles()) than any call before it — also with fp32 tracers, whose pass in the
+    load reads the partial rows.  By the code both wait for the stream before they free, and the staging pair is moreover only used by
+    calls that wait for their own work before they return; this confirms the order, on contexts that have made only small calls."""
     rig = rigs("f64-2000" if variant == "f64" else "f32-2000")
     twins = [rig.fresh(), rig.fresh()]
     small, big = rig.points[:8], rig.points

@@ -7,9 +7,11 @@ N = 65536 (reference box, distinct masses, eps = 0), theta = 0:
 1  fp32 state, M = N: jerk_at against potential_at and tidal_at, jerk() against potentials() and tidal(), on one context, three
    alternating rounds
 2  fp64 state: jerk(np.float64), three rounds
-Device times are nbody_kernel_time's (HIP events around the queued unit); every row is warmed up."""
+Device times are nbody_kernel_time's (HIP events around the queued unit), `call` the median on the host clock round the whole call
+(staging, copies and the wait included); every row is warmed up."""
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -23,14 +25,17 @@ def points(m):
 
 
 def timed(e, call, reps=20, warm=3):
-    """device ms per call"""
+    """(device ms per call, median wall ms per call)"""
     for _ in range(warm):
         call()
     e.kernel_time_reset()
+    walls = []
     for _ in range(reps):
+        t0 = time.perf_counter()
         call()
+        walls.append(time.perf_counter() - t0)
     ms, _ = e.kernel_time()
-    return ms / reps
+    return ms / reps, 1e3 * float(np.median(walls))
 
 
 def main():
@@ -47,8 +52,8 @@ def main():
             row = {}
             for name, call in (("potential_at", lambda: e.potential_at(pts)), ("tidal_at", lambda: e.tidal_at(pts)),
                                ("jerk_at", lambda: e.jerk_at(pts, pv)), ("potentials", e.potentials), ("tidal", e.tidal), ("jerk", e.jerk)):
-                row[name] = timed(e, call)
-                print(f"round {rnd}  {name:<13s} {row[name]:8.4f} ms  {float(n) * n / (row[name] * 1e-3):.3e} /s")
+                row[name], wall = timed(e, call)
+                print(f"round {rnd}  {name:<13s} {row[name]:8.4f} ms  {float(n) * n / (row[name] * 1e-3):.3e} /s  call {wall:7.3f} ms")
             print(f"round {rnd}  jerk_at / potential_at {row['jerk_at'] / row['potential_at']:.3f}   jerk_at / tidal_at "
                   f"{row['jerk_at'] / row['tidal_at']:.3f}   jerk / potentials {row['jerk'] / row['potentials']:.3f}   jerk / tidal "
                   f"{row['jerk'] / row['tidal']:.3f}")
@@ -56,8 +61,8 @@ def main():
     with nb.NBodyEngine(n, precision="f64", time_kernels=True) as e:
         e.set_state(posm.astype(np.float64), vel.astype(np.float64))
         for rnd in range(3):
-            ms = timed(e, lambda: e.jerk(np.float64), reps=5, warm=1)
-            print(f"round {rnd}  jerk f64      {ms:8.4f} ms  {float(n) * n / (ms * 1e-3):.3e} /s")
+            ms, wall = timed(e, lambda: e.jerk(np.float64), reps=5, warm=1)
+            print(f"round {rnd}  jerk f64      {ms:8.4f} ms  {float(n) * n / (ms * 1e-3):.3e} /s  call {wall:7.3f} ms")
 
 
 if __name__ == "__main__":
