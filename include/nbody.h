@@ -1112,6 +1112,43 @@ NBODY_AMD_API int nbody_radius_counts_at_f64(nbody_ctx *ctx, const double *pos, 
 NBODY_AMD_API int nbody_get_groups_f64(nbody_ctx *ctx, double radius, int32_t *label, int32_t *members, int32_t *degree,
                                        nbody_groups *summary);
 
+/* The fp64 minimum spanning tree (build-defined: the reference has none): the Euclidean minimum spanning tree of the bodies — what the
+ * mass-segregation ratio, the Q parameter and the single-linkage dendrogram are read from; cutting it at a length gives the
+ * friends-of-friends groups at THAT length, at every length from one call.  On the contexts that answer nbody_get_groups_f64 (fp64
+ * state, one device, all bodies, no open step); every other kind refuses with that call's refusals.  theta and eps play no part.  The
+ * call reads the live positions.  Every line below is reproducible in numpy, bit for bit; nothing but `rounds` depends on how it was
+ * computed.
+ *
+ * Weight.  dx = x_j - x_i (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz, contraction off: the group census's expression, symmetric in
+ *   every bit, so that the edges with d2 <= radius * radius connect exactly nbody_get_groups_f64(radius)'s groups.
+ * Edges.  The unordered pairs i < j whose d2 is finite.  A NaN or +inf d2 — a coordinate that is not finite, or an overflow between two
+ *   finite bodies — is no edge: such bodies end in components of their own, and the result is a minimum spanning FOREST.  A zero-mass
+ *   body is a vertex like any other; coincident bodies are joined by edges of d2 = 0.
+ * Order.  Edges compare by the key (d2, i, j), i < j, lexicographically: a strict total order, so the forest is UNIQUE — a function of
+ *   the positions alone, the same bytes every run.
+ * Output.  edges = n_total - components records (i, j, d2), ascending by that key, in i, j, d2: [n_total - 1] each; the entries from
+ *   `edges` on read (-1, -1, +inf).  component[n_total] = the lowest index among the bodies of each body's component (the groups' label
+ *   convention).
+ * Summary.  length = sum of sqrt(d2) over the edges in output order, added left to right from 0.0;  longest_d2 = the last edge's d2, 0.0
+ *   with no edge;  rounds = the N^2 passes the device took: Boruvka rounds — every body finds its nearest body in ANOTHER component,
+ *   every component keeps the least such edge by the key, the components are merged along them.  The components that still have an
+ *   edge at least halve every round: rounds <= ceil(log2 n_total) + 1, NBODY_ERR_INTERNAL beyond.  No pass is made once one component
+ *   remains (n_total == 1: 0 rounds); where several remain, one last pass that finds no edge ends the call and is counted.
+ *
+ * Any output may be NULL, not all five: NBODY_ERR_INVALID.  No particles set: NBODY_ERR_STATE.  The call synchronises, changes nothing
+ * a getter shows, and leaves both Hermite caches, the fp64 tracers and any block session of either order alone; nothing is kept per
+ * context between calls.  Each pass counts once under NBODY_KERNEL_FORCES, nothing under NBODY_KERNEL_UPDATE.
+ */
+typedef struct nbody_mst {   /* 32 bytes */
+  int32_t edges;            /* n_total - components */
+  int32_t components;       /* trees of the forest, singles included */
+  int32_t rounds;           /* N^2 passes taken */
+  int32_t reserved;         /* 0 */
+  double length;            /* sum of sqrt(d2) in output order */
+  double longest_d2;        /* d2 of the last edge; 0.0 with no edge */
+} nbody_mst;
+NBODY_AMD_API int nbody_get_mst_f64(nbody_ctx *ctx, int32_t *i, int32_t *j, double *d2, int32_t *component, nbody_mst *summary);
+
 /* ComputeCubeSize (OctreeSearch.cpp:47-56): max over owned bodies of max(|x|,|y|,|z|). */
 NBODY_AMD_API int nbody_get_bounds(nbody_ctx *ctx, float *size);
 

@@ -13,6 +13,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --core-every 5 --core-k 6       # density centre and core radius
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --lagrange-every 5 --lagrange-fractions 0.1,0.5,0.9   # Lagrangian radii
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --groups-every 5 --linking-length 0.02   # friends-of-friends groups
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --mst-every 5       # minimum spanning tree: length, mean and longest edge
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -95,6 +96,10 @@ def main(argv=None):
                          "device, one per round of the group finder)")
     ap.add_argument("--linking-length", type=float, default=None,
                     help="--groups-every: bodies closer than this are linked, finite and >= 0")
+    ap.add_argument("--mst-every", type=int, default=0,
+                    help="print the Euclidean minimum spanning tree every K frames: its edges, components, total length, mean and longest "
+                         "edge, and the rounds taken (--precision f64 only: a few passes over all pairs on the device, one per Boruvka "
+                         "round)")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -140,6 +145,10 @@ def main(argv=None):
         ap.error("--linking-length belongs to --groups-every")
     if a.linking_length is not None and not (0.0 <= a.linking_length < float("inf")):
         ap.error("--linking-length must be finite and >= 0")
+    if a.mst_every < 0:
+        ap.error("--mst-every must be >= 0")
+    if a.mst_every > 0 and a.precision != "f64":
+        ap.error("--mst-every needs --precision f64: the minimum spanning tree runs on fp64 contexts only")
     fractions = LAGRANGE_FRACTIONS
     if a.lagrange_fractions is not None:
         try:
@@ -217,7 +226,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.groups_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.groups_every, a.mst_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -252,6 +261,11 @@ def main(argv=None):
                 print(json.dumps({"frame": frame, "groups": {"linking_length": a.linking_length, "groups": g.groups,
                                                              "multiples": g.multiples, "largest": g.largest,
                                                              "largest_members": g.largest_members, "links": g.links}}), flush=True)
+            if a.mst_every > 0 and frame % a.mst_every == 0:
+                t = e.mst_f64().summary
+                print(json.dumps({"frame": frame, "mst": {"edges": t.edges, "components": t.components, "length": t.length,
+                                                          "mean_edge": t.length / t.edges if t.edges else 0.0,
+                                                          "longest_edge": float(np.sqrt(t.longest_d2)), "rounds": t.rounds}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

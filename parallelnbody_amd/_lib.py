@@ -152,7 +152,19 @@ class Groups(ctypes.Structure):
     ]
 
 
-MASS_WITHIN_MAX = 64      # radii one nbody_mass_within call answers
+class Mst(ctypes.Structure):
+    """struct nbody_mst (include/nbody.h): the summary of nbody_get_mst_f64, 32 bytes."""
+    _fields_ = [
+        ("edges", ctypes.c_int32),
+        ("components", ctypes.c_int32),
+        ("rounds", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("length", ctypes.c_double),
+        ("longest_d2", ctypes.c_double),
+    ]
+
+
+MASS_WITHIN_MAX = 64     # radii one nbody_mass_within call answers
 NEIGHBOURS_MAX = 8        # NBODY_NEIGHBOURS_MAX: the longest list nbody_get_neighbours_f64 answers
 LAGRANGE_MAX = 64         # NBODY_LAGRANGE_MAX: fractions one nbody_lagrange_radii_f64 call answers
 
@@ -271,6 +283,7 @@ def lib():
     sig("nbody_get_radius_counts_f64", c_int, vp, c_d, vp)
     sig("nbody_radius_counts_at_f64", c_int, vp, vp, sz, c_i32, c_d, vp)
     sig("nbody_get_groups_f64", c_int, vp, c_d, vp, vp, vp, ctypes.POINTER(Groups))
+    sig("nbody_get_mst_f64", c_int, vp, vp, vp, vp, vp, ctypes.POINTER(Mst))
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)
     sig("nbody_tracer_count_f64", c_int, vp, ctypes.POINTER(c_i32))

@@ -1,11 +1,14 @@
 // The fp64 queries of the C-ABI (include/nbody.h) on fp64 contexts that are not Hermite stepping: the potential and tidal tensor
 // (kernels_pot64.hip), the pair census (kernels_census64.hip), the neighbour census (kernels_neighbours64.hip), the radial census
-// (kernels_radial64.hip) and the group census (kernels_groups64.hip).  Host C++ like capi.hip; what it shares with the other host units: capi_common.h.
+// (kernels_radial64.hip), the group census (kernels_groups64.hip) and the minimum spanning forest (kernels_mst64.hip).  Host C++ like capi.hip; what it shares with the other host units: capi_common.h.
 // Written once here: the row pass (row_pass64) every N^2 query is queued through, and the staged points (Staged64) of every *_at_f64 call.
+#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "capi_common.h"
 #include "ctx.h"
@@ -274,6 +277,38 @@ int groups64_pass(nbody_ctx *c, double r2, const void *ppos, int m, const int *p
                     });
 }
 
+// ---- the fp64 minimum spanning forest (kernels_mst64.hip) ----
+static_assert(sizeof(nbody_mst) == 32, "include/nbody.h: 32 bytes");
+
+// every body's nearest body under another label: one pass
+int mst64_pass(nbody_ctx *c, int n, const nbody::Mst64Work &W) {
+  nbody::Mst64Launch L;
+  L.label = W.label; L.index = W.near_j; L.d2 = W.near_d2;
+  return row_pass64(c, nbody::kMst64Width, "the fp64 spanning-tree pass", nullptr, n, L,
+                    [&](const nbody::Mst64Launch &P) { return nbody::launch_mst_pass_f64(P, c->stream); });
+}
+
+// the work area of n bodies, mst64_bytes(n) of them, carved from `base` (the staging pair's device or host side): the 8-byte arrays first.
+// *out_first, *out_bytes: edge_d2, edge_i, edge_j and component, adjacent
+size_t mst64_bytes(size_t n) { return 4 * n * 8 + (7 * n + 1) * 4; }
+nbody::Mst64Work mst64_work(void *base, size_t n, size_t *out_first, size_t *out_bytes) {
+  nbody::Mst64Work W;
+  double *d = (double *)base;
+  W.near_d2 = d; W.best = (unsigned long long *)(d + n); W.pair = W.best + n; W.edge_d2 = d + 3 * n;
+  int *q = (int *)(d + 4 * n);
+  W.edge_i = q; W.edge_j = q + n; W.component = q + 2 * n; W.label = q + 3 * n; W.near_j = q + 4 * n; W.succ = q + 5 * n; W.lowest = q + 6 * n;
+  W.cursor = q + 7 * n;
+  *out_first = 3 * n * 8; *out_bytes = n * 8 + 3 * n * 4;
+  return W;
+}
+
+// ceil(log2 n) + 1: the components with an edge at least halve every round, and one last pass may find none
+int mst64_round_bound(size_t n) {
+  int bits = 0;
+  while (((size_t)1 << bits) < n) ++bits;
+  return bits + 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -539,6 +574,71 @@ int nbody_get_groups_f64(nbody_ctx *c, double radius, int32_t *label, int32_t *m
     summary->largest = (int32_t)(0x7fffffffull - (s[3] & 0xffffffffull)); summary->largest_members = (int32_t)(s[3] >> 32);
     summary->rounds = (int32_t)rounds; summary->reserved = 0;
     summary->links = (int64_t)(s[2] / 2);
+  }
+  return NBODY_OK;
+}
+
+// The Boruvka rounds are driven from here: clear, pass and fold, pick, hook, compress, then a 4-byte read-back of the edges so far.  No
+// pass is made once n - 1 edges are there; a round that appends none is the last and is counted.  NBODY_MST_PHASES=1 (read at every call;
+// tools/mst_f64_measure.py): the host clock round the rounds, the read-back and the sort, printed to stderr.
+int nbody_get_mst_f64(nbody_ctx *c, int32_t *i, int32_t *j, double *d2, int32_t *component, nbody_mst *summary) {
+  const char *who = "nbody_get_mst_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  if (!i && !j && !d2 && !component && !summary) return fail(c, NBODY_ERR_INVALID, "%s: every output is null", who);
+  const size_t n = (size_t)c->p.n_total;
+  size_t out_first, out_bytes;
+  if ((rc = ensure_stage(c, mst64_bytes(n)))) return rc;
+  const nbody::Mst64Work W = mst64_work(c->d_stage, n, &out_first, &out_bytes);
+  const nbody::Mst64Work H = mst64_work(c->h_stage, n, &out_first, &out_bytes);
+  const auto clock = [] { return std::chrono::steady_clock::now(); };
+  const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+  };
+  const auto t0 = clock();
+  HIP_TRY(c, nbody::launch_mst_begin(W, (int)n, c->stream));
+  const int bound = mst64_round_bound(n);
+  int rounds = 0;
+  size_t edges = 0;
+  while (edges + 1 < n) {
+    if (rounds == bound) return fail(c, NBODY_ERR_INTERNAL, "%s: %zu components of %zu bodies left after %d rounds", who, n - edges, n, rounds);
+    HIP_TRY(c, nbody::launch_mst_clear(W, (int)n, c->stream));
+    if ((rc = mst64_pass(c, (int)n, W))) return rc;
+    ++rounds;
+    HIP_TRY(c, nbody::launch_mst_merge(W, (int)n, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(H.cursor, W.cursor, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t now = (size_t)*H.cursor;
+    if (now >= n) return fail(c, NBODY_ERR_INTERNAL, "%s: %zu edges among %zu bodies", who, now, n);
+    if (now == edges) break;
+    edges = now;
+  }
+  const auto t1 = clock();
+  HIP_TRY(c, nbody::launch_mst_components(W, (int)n, c->stream));
+  if ((rc = stage_to_host(c, out_first, out_bytes))) return rc;
+  const auto t2 = clock();
+  struct Edge { double d2; int32_t lo, hi; };
+  std::vector<Edge> e(edges);
+  for (size_t k = 0; k < edges; ++k) e[k] = Edge{H.edge_d2[k], H.edge_i[k], H.edge_j[k]};
+  std::sort(e.begin(), e.end(), [](const Edge &a, const Edge &b) {
+    return a.d2 != b.d2 ? a.d2 < b.d2 : a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi;
+  });
+  const auto t3 = clock();
+  const char *env = getenv("NBODY_MST_PHASES");
+  if (env && env[0] == '1')
+    fprintf(stderr, "mst_f64 phases: n %zu rounds %d loop %.4f readback %.4f sort %.4f ms\n", n, rounds, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+  double length = 0.0;
+  for (size_t k = 0; k + 1 < n; ++k) {
+    const bool edge = k < edges;
+    if (i) i[k] = edge ? e[k].lo : -1;
+    if (j) j[k] = edge ? e[k].hi : -1;
+    if (d2) d2[k] = edge ? e[k].d2 : HUGE_VAL;
+    if (edge) length += std::sqrt(e[k].d2);
+  }
+  if (component) memcpy(component, H.component, n * 4);
+  if (summary) {
+    summary->edges = (int32_t)edges; summary->components = (int32_t)(n - edges); summary->rounds = rounds; summary->reserved = 0;
+    summary->length = length; summary->longest_d2 = edges ? e[edges - 1].d2 : 0.0;
   }
   return NBODY_OK;
 }

@@ -473,6 +473,43 @@ hipError_t launch_groups_merge(int *parent, const int *mn, int *hooked, int n, i
 // max over the groups of (size << 32 | 0x7fffffff - label) — integer atomics on cleared words, the same values whatever the order
 hipError_t launch_groups_members(const int *label, const int *degree, int n, int *size, int *members, unsigned long long *sum, hipStream_t s);
 
+// The minimum spanning forest of an fp64 state in Boruvka rounds — kernels_mst64.hip: launch_nearest_f64's argmin pass with the group
+// census's d2 and its label in the tile's fourth component.  Edges are the pairs i < j with a finite d2 = (dx*dx + dy*dy) + dz*dz
+// (contraction off), ordered by the key (d2, i, j): a strict total order, so the forest is unique.
+//   launch_mst_pass_f64:  the bodies only (m == n_total, ppos == nullptr): per row the body j of ANOTHER label with the smallest d2 under
+//                         strict < in ascending j — for a fixed row the smallest key —; none: (-1, +inf).  A d2 that is NaN or +inf is
+//                         never taken; the padding is kept out by index, the row's own component (itself included) by label.  A
+//                         partial row is (d2, index), kNearest64Width, folded in chunk order under strict <.
+constexpr int kMst64Width = kNearest64Width;
+struct Mst64Launch : RowScan64Launch {
+  const int *label = nullptr;   // [n_total]: every body's component label (a body of that component, whose own label is itself)
+  int *index = nullptr;         // [m]
+  double *d2 = nullptr;         // [m]
+};
+hipError_t launch_mst_pass_f64(const Mst64Launch &L, hipStream_t s);
+// The O(N) kernels of a round, integer atomics only — every array comes out the same whatever the order.  W is carved from one work area:
+struct Mst64Work {
+  double *near_d2 = nullptr;               // [n] the pass's answer, with near_j
+  unsigned long long *best = nullptr;      // [n] per label: the smallest d2 of an edge that leaves the component, as its bit pattern
+  unsigned long long *pair = nullptr;      // [n] per label: the smallest (lo << 32 | hi) among the edges of that d2     (best, pair: adjacent)
+  double *edge_d2 = nullptr;               // [n] the edges in the order they were appended               (edge_d2, edge_i, edge_j, component:
+  int *edge_i = nullptr, *edge_j = nullptr;   // [n] each, i < j                                            adjacent, read back in one copy)
+  int *component = nullptr;                // [n] the lowest index of every body's component (launch_mst_components)
+  int *label = nullptr, *near_j = nullptr, *succ = nullptr, *lowest = nullptr;   // [n] each
+  int *cursor = nullptr;                   // the edges appended so far
+};
+// label[i] = lowest[i] = i, *cursor = 0
+hipError_t launch_mst_begin(const Mst64Work &W, int n, hipStream_t s);
+// best = pair = all ones, ahead of a round's pass
+hipError_t launch_mst_clear(const Mst64Work &W, int n, hipStream_t s);
+// behind the pass: pick (atomicMin of the d2 bits into best[label], then of the packed pair among the bodies that attain it), hook (a
+// label's successor is the label at the foreign end of its edge; where two labels chose the same edge the lower one stays a root; the
+// edge is appended once, at atomicAdd(cursor), by the label that is not the higher of such two), compress (label[i] = the root the
+// successors lead to from label[i]: succ is read-only meanwhile, a forest by the total order, and the chase is capped at n)
+hipError_t launch_mst_merge(const Mst64Work &W, int n, hipStream_t s);
+// component[i] = the lowest body index among those of label[i]
+hipError_t launch_mst_components(const Mst64Work &W, int n, hipStream_t s);
+
 // Symmetric (each unordered pair once) force pass — kernels_sym.hip (fp32), kernels_sym64.hip (fp64).  Who evaluates
 // which pairs, where the partial sums go and in which order they are added is the plan of sym_plan.h, uploaded once.
 struct SymLaunch {

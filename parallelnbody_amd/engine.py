@@ -131,6 +131,13 @@ GroupsSummary = collections.namedtuple("GroupsSummary", ("groups", "multiples", 
 # NBodyEngine.groups_f64(): per body label, members, degree (int32[n_total]), then the summary
 GroupsResult = collections.namedtuple("GroupsResult", ("label", "members", "degree", "summary"))
 
+# NBodyEngine.mst_f64(): the fields of struct nbody_mst
+MstSummary = collections.namedtuple("MstSummary", ("edges", "components", "rounds", "length", "longest_d2"))
+
+# NBodyEngine.mst_f64(): the edges i < j with their d2 in ascending (d2, i, j) order (int32, int32, float64: [summary.edges] each), per
+# body the lowest index of its component (int32[n_total]), then the summary
+MstResult = collections.namedtuple("MstResult", ("i", "j", "d2", "component", "summary"))
+
 # NBodyEngine.group_table_f64(): one row per group (group_table())
 GROUP_TABLE_DTYPE = np.dtype([("label", np.int32), ("count", np.int32), ("mass", np.float64), ("com", np.float64, 3),
                               ("velocity", np.float64, 3), ("r_rms", np.float64), ("sigma", np.float64)])
@@ -156,6 +163,34 @@ def group_table(label, posm, vel, min_members=2):
             sigma = np.sqrt((m * ((v - vm) ** 2).sum(1)).sum() / mass)
         row["label"], row["count"], row["mass"], row["com"], row["velocity"], row["r_rms"], row["sigma"] = l, k, mass, com, vm, r_rms, sigma
     return out
+
+
+def mst_groups(i, j, d2, n, radius):
+    """(label, members), int32[n] each: the connected components of n bodies under the edges (i, j) whose d2 <= radius * radius — a
+    union-find, the lower root winning, so a label is the lowest index of its group.  The edges are ascending in d2 (a spanning
+    forest's): those within the radius are a prefix."""
+    r2 = np.float64(radius) * np.float64(radius)
+    if not (np.isfinite(radius) and radius >= 0.0 and np.isfinite(r2)):
+        raise ValueError("mst_groups: the radius must be finite and >= 0 and its square finite")
+    keep = int(np.searchsorted(np.asarray(d2, np.float64), r2, "right"))
+    parent = list(range(n))
+
+    def find(a):
+        r = a
+        while parent[r] != r:
+            r = parent[r]
+        while parent[a] != r:
+            parent[a], a = r, parent[a]
+        return r
+    for a, b in zip(np.asarray(i)[:keep].tolist(), np.asarray(j)[:keep].tolist()):
+        ra, rb = find(a), find(b)
+        if ra < rb:
+            parent[rb] = ra
+        elif rb < ra:
+            parent[ra] = rb
+    label = np.array([find(a) for a in range(n)], np.int32).reshape(n)
+    members = np.bincount(label, minlength=n)[label].astype(np.int32)
+    return label, members
 
 
 LAGRANGE_FRACTIONS = (0.01,0.02, 0.05, 0.1, 0.2, 0.3, 0.5, 0.7, 0.9)
@@ -1034,6 +1069,32 @@ class NBodyEngine:
         label = self.groups_f64(radius).label
         posm, vel, _ = self.state(np.float64)
         return group_table(label, posm, vel, min_members)
+
+    # -- the fp64 minimum spanning tree (fp64 contexts) --
+    def mst_f64(self):
+        """The Euclidean minimum spanning tree of the bodies (nbody_get_mst_f64): an MstResult (i, j, d2, component, summary).  The
+        weight of the pair i < j is d2 = (dx*dx + dy*dy) + dz*dz without contraction — groups_f64()'s expression —, an edge only
+        where it is finite: bodies with a NaN or infinite coordinate end in components of their own, and the result is a forest.  Edges
+        compare by (d2, i, j), a strict total order, so the forest is unique and the same bytes every run.  i, j, d2: the
+        summary.edges = n_total - summary.components edges in ascending order of that key; component[n_total]: the lowest index of
+        each body's component.  summary: edges, components, rounds (the pair passes the device took, at most ceil(log2 n_total) + 1),
+        length (= np.cumsum(np.sqrt(d2))[-1], 0.0 with no edge) and longest_d2 (the last edge's, 0.0 with none).  Contexts and side
+        effects (none) as radius_counts_f64()."""
+        n = self.n_total
+        i, j = (np.empty(max(n - 1, 0), np.int32) for _ in range(2))
+        d2 = np.empty(max(n - 1, 0), np.float64)
+        component = np.empty(n, np.int32)
+        s = _lib.Mst()
+        self._check(self._L.nbody_get_mst_f64(self._h, i.ctypes.data, j.ctypes.data, d2.ctypes.data, component.ctypes.data, ctypes.byref(s)))
+        summary = MstSummary(int(s.edges), int(s.components), int(s.rounds), float(s.length), float(s.longest_d2))
+        return MstResult(i[:summary.edges].copy(), j[:summary.edges].copy(), d2[:summary.edges].copy(), component, summary)
+
+    @staticmethod
+    def mst_groups_f64(mst, radius):
+        """(label, members) of the friends-of-friends groups at linking length `radius` from an MstResult, in numpy: a union-find over
+        the edges with d2 <= radius * radius, the lower root winning.  label[i] = the lowest index of i's group, members[i] = its
+        size (int32[n_total] each): byte for byte groups_f64(radius)'s, for any number of radii from one mst_f64() call."""
+        return mst_groups(mst.i, mst.j, mst.d2, len(mst.component), radius)
 
     def set_tracers_f64(self, pos, vel=None):
         """Massless fp64 tracers that hermite_step(), hermite_advance(), hermite6_step() and hermite6_advance() carry beside the bodies
