@@ -1112,6 +1112,44 @@ NBODY_AMD_API int nbody_radius_counts_at_f64(nbody_ctx *ctx, const double *pos, 
 NBODY_AMD_API int nbody_get_groups_f64(nbody_ctx *ctx, double radius, int32_t *label, int32_t *members, int32_t *degree,
                                        nbody_groups *summary);
 
+/* The fp64 separation census (build-defined: the reference has none): HOW MANY PAIRS LIE WITHIN r, AS A FUNCTION OF r — the pair-count
+ * function C(r), from which the pair-separation histogram, the DD / DR / RR counts of the two-point correlation function, the correlation
+ * dimension d log C / d log r and the radial distribution function are read — at up to NBODY_PAIR_RADII_MAX radii from ONE call, where
+ * nbody_get_radius_counts_f64 takes one N^2 pass per radius and leaves the sum to the host.  The pair form of nbody_mass_within.  On the
+ * contexts that answer nbody_get_radius_counts_f64 (fp64 state, one device, all bodies, no open step); every other kind refuses with
+ * that call's refusals.  theta and eps play no part: nothing is softened.  The calls read the live positions.  Every count is an exact
+ * integer, reproducible in numpy; nothing depends on how it was computed.
+ *
+ * Distance.  dx = x_j - x_i (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz, contraction off: the group census's expression in every
+ *   operation, symmetric in every bit.
+ * Threshold.  r2 = radii[q] * radii[q], one fp64 multiply.
+ * Link.  A pair counts at radius q iff d2 <= r2.  A NaN d2 never counts; a +inf d2 never passes a finite r2.  A zero-mass body counts
+ *   like any other.
+ * Radii.  1 <= k <= NBODY_PAIR_RADII_MAX; each radius finite and >= 0 with a finite square.  The radii may come in ANY ORDER and WITH
+ *   REPEATS; each is answered on its own (equal radii get equal answers), as in nbody_mass_within.
+ *
+ * nbody_get_pair_counts_f64: count[q] = the number of UNORDERED pairs {i, j}, i != j BY INDEX, with d2 <= r2_q.  Coincident distinct
+ *   bodies count at radius 0.  (d2_ij == d2_ji in every bit, so the ordered count is even; this is half of it.)
+ * nbody_pair_counts_at_f64: count[q] = the number of (point, body) pairs within radii[q], over n points of three doubles, pos_stride
+ *   (>= 24) bytes apart, and all bodies.  NO body is dropped by index: a point on a body counts that body.  n == 0: NBODY_OK, zeros
+ *   written.
+ * Identities, all exact:  nbody_get_pair_counts_f64's count[q] == nbody_groups.links of nbody_get_groups_f64(radii[q]) == the sum of
+ *   nbody_get_radius_counts_f64(radii[q])'s degrees / 2;  nbody_pair_counts_at_f64's count[q] == the sum of
+ *   nbody_radius_counts_at_f64(radii[q])'s counts;  with one point c it equals the count of nbody_mass_within(c, radii[q]).
+ *
+ * NULL radii, count or points, k outside 1 .. NBODY_PAIR_RADII_MAX, a radius that is NaN, negative, infinite or whose square overflows,
+ * n < 0, a stride < 24: NBODY_ERR_INVALID.  No particles set: NBODY_ERR_STATE.  Every check runs before anything is written: a refused
+ * call leaves count[] untouched.  The calls synchronise, change nothing a getter shows, and leave both Hermite caches, the fp64 tracers
+ * and any block session of either order alone; nothing is kept per context between calls.  The distinct r2 among the k radii are
+ * answered NBODY_PAIR_RADII_PER_PASS to an N^2 pass: a call takes ceil(k_distinct / NBODY_PAIR_RADII_PER_PASS) passes, each counted
+ * once under NBODY_KERNEL_FORCES, nothing under NBODY_KERNEL_UPDATE (nbody_pair_counts_at_f64 with n == 0: none).
+ */
+#define NBODY_PAIR_RADII_MAX 64
+#define NBODY_PAIR_RADII_PER_PASS 16
+NBODY_AMD_API int nbody_get_pair_counts_f64(nbody_ctx *ctx, const double *radii, int32_t k, int64_t *count);
+NBODY_AMD_API int nbody_pair_counts_at_f64(nbody_ctx *ctx, const double *pos, size_t pos_stride, int32_t n, const double *radii, int32_t k,
+                                           int64_t *count);
+
 /* The fp64 minimum spanning tree (build-defined: the reference has none): the Euclidean minimum spanning tree of the bodies — what the
  * mass-segregation ratio, the Q parameter and the single-linkage dendrogram are read from; cutting it at a length gives the
  * friends-of-friends groups at THAT length, at every length from one call.  On the contexts that answer nbody_get_groups_f64 (fp64

@@ -14,6 +14,7 @@
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --lagrange-every 5 --lagrange-fractions 0.1,0.5,0.9   # Lagrangian radii
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --groups-every 5 --linking-length 0.02   # friends-of-friends groups
     python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --mst-every 5       # minimum spanning tree: length, mean and longest edge
+    python -m parallelnbody_amd --plummer --n 4096 --precision f64 --steps 20 --pairs-every 5 --pair-radii 0.01,0.02,0.05,0.1   # pairs within each radius
 
 Trajectory file (nothing in the reference to mirror): header `NBDYTRJ1`, int32 n, int32 reserved, then per
 dumped frame int64 frame number + n x 3 float32 positions — `read_trajectory(path)` returns (frames, positions[k, n, 3]).
@@ -100,6 +101,11 @@ def main(argv=None):
                     help="print the Euclidean minimum spanning tree every K frames: its edges, components, total length, mean and longest "
                          "edge, and the rounds taken (--precision f64 only: a few passes over all pairs on the device, one per Boruvka "
                          "round)")
+    ap.add_argument("--pairs-every", type=int, default=0,
+                    help="print the pair counts at --pair-radii every K frames: the unordered pairs of bodies within each radius "
+                         "(--precision f64 only: one pass over all pairs on the device per 16 distinct radii)")
+    ap.add_argument("--pair-radii", default=None,
+                    help="--pairs-every: the radii, r,r,... each finite and >= 0, in any order, at most 64")
     ap.add_argument("--checkpoint", help="write the final state here")
     ap.add_argument("--resume", help="start from this checkpoint instead of fresh initial conditions")
     ap.add_argument("--dump-positions", help="write the final positions (n x 3 float32, .npy)")
@@ -149,6 +155,22 @@ def main(argv=None):
         ap.error("--mst-every must be >= 0")
     if a.mst_every > 0 and a.precision != "f64":
         ap.error("--mst-every needs --precision f64: the minimum spanning tree runs on fp64 contexts only")
+    if a.pairs_every < 0:
+        ap.error("--pairs-every must be >= 0")
+    if a.pairs_every > 0 and a.precision != "f64":
+        ap.error("--pairs-every needs --precision f64: the separation census runs on fp64 contexts only")
+    if a.pairs_every > 0 and a.pair_radii is None:
+        ap.error("--pairs-every needs --pair-radii")
+    if a.pair_radii is not None and a.pairs_every == 0:
+        ap.error("--pair-radii belongs to --pairs-every")
+    pair_radii = ()
+    if a.pair_radii is not None:
+        try:
+            pair_radii = tuple(float(r) for r in a.pair_radii.split(","))
+        except ValueError:
+            pair_radii = ()
+        if not 1 <= len(pair_radii) <= 64 or not all(0.0 <= r < float("inf") for r in pair_radii):
+            ap.error("--pair-radii must be 1 .. 64 comma-separated radii, each finite and >= 0")
     fractions = LAGRANGE_FRACTIONS
     if a.lagrange_fractions is not None:
         try:
@@ -226,7 +248,7 @@ def main(argv=None):
             frame_buf = np.empty((a.n, 3), np.float32)
             e.pin(frame_buf)                                     # frames land in it by one DMA
         # advance in chunks that end on every frame somebody wants to see
-        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.groups_every, a.mst_every, a.trajectory_every if trj else 0) if m > 0]
+        marks = [m for m in (a.energy_every, a.moments_every, a.core_every, a.lagrange_every, a.groups_every, a.mst_every, a.pairs_every, a.trajectory_every if trj else 0) if m > 0]
         if a.energy_every > 0 and a.sync_energy and not a.resume:
             print(json.dumps({"frame": start, **energies()}), flush=True)
         t0 = time.perf_counter()
@@ -266,6 +288,9 @@ def main(argv=None):
                 print(json.dumps({"frame": frame, "mst": {"edges": t.edges, "components": t.components, "length": t.length,
                                                           "mean_edge": t.length / t.edges if t.edges else 0.0,
                                                           "longest_edge": float(np.sqrt(t.longest_d2)), "rounds": t.rounds}}), flush=True)
+            if a.pairs_every > 0 and frame % a.pairs_every == 0:
+                counts = e.pair_counts_f64(pair_radii)
+                print(json.dumps({"frame": frame, "pairs": {"radii": list(pair_radii), "counts": [int(c) for c in counts]}}), flush=True)
             if trj and frame % a.trajectory_every == 0:
                 e.positions(out=frame_buf)
                 trj.write(np.int64(frame).tobytes() + frame_buf.tobytes())

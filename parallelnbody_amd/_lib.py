@@ -167,6 +167,8 @@ class Mst(ctypes.Structure):
 MASS_WITHIN_MAX = 64     # radii one nbody_mass_within call answers
 NEIGHBOURS_MAX = 8        # NBODY_NEIGHBOURS_MAX: the longest list nbody_get_neighbours_f64 answers
 LAGRANGE_MAX = 64         # NBODY_LAGRANGE_MAX: fractions one nbody_lagrange_radii_f64 call answers
+PAIR_RADII_MAX = 64       # NBODY_PAIR_RADII_MAX: radii one nbody_get_pair_counts_f64 call answers
+PAIR_RADII_PER_PASS = 16  # NBODY_PAIR_RADII_PER_PASS: distinct radii one N^2 pass of it answers
 
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 DRAW_POINT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_float)
@@ -283,6 +285,8 @@ def lib():
     sig("nbody_get_radius_counts_f64", c_int, vp, c_d, vp)
     sig("nbody_radius_counts_at_f64", c_int, vp, vp, sz, c_i32, c_d, vp)
     sig("nbody_get_groups_f64", c_int, vp, c_d, vp, vp, vp, ctypes.POINTER(Groups))
+    sig("nbody_get_pair_counts_f64", c_int, vp, dp, c_i32, ctypes.POINTER(c_i64))
+    sig("nbody_pair_counts_at_f64", c_int, vp, vp, sz, c_i32, dp, c_i32, ctypes.POINTER(c_i64))
     sig("nbody_get_mst_f64", c_int, vp, vp, vp, vp, vp, ctypes.POINTER(Mst))
     sig("nbody_set_tracers_f64", c_int, vp, vp, sz, vp, sz, c_i32)
     sig("nbody_get_tracers_f64", c_int, vp, vp, sz, vp, sz)

@@ -1,6 +1,6 @@
 // The fp64 queries of the C-ABI (include/nbody.h) on fp64 contexts that are not Hermite stepping: the potential and tidal tensor
 // (kernels_pot64.hip), the pair census (kernels_census64.hip), the neighbour census (kernels_neighbours64.hip), the radial census
-// (kernels_radial64.hip), the group census (kernels_groups64.hip) and the minimum spanning forest (kernels_mst64.hip).  Host C++ like capi.hip; what it shares with the other host units: capi_common.h.
+// (kernels_radial64.hip), the group census (kernels_groups64.hip), the separation census (kernels_pairs64.hip) and the minimum spanning forest (kernels_mst64.hip).  Host C++ like capi.hip; what it shares with the other host units: capi_common.h.
 // Written once here: the row pass (row_pass64) every N^2 query is queued through, and the staged points (Staged64) of every *_at_f64 call.
 #include <algorithm>
 #include <chrono>
@@ -275,6 +275,70 @@ int groups64_pass(nbody_ctx *c, double r2, const void *ppos, int m, const int *p
                     [&](const nbody::Groups64Launch &P) {
                       return parent ? nbody::launch_groups_pass_f64(P, first_round, c->stream) : nbody::launch_radius_counts_f64(P, c->stream);
                     });
+}
+
+// ---- the fp64 separation census (kernels_pairs64.hip) ----
+static_assert(nbody::kPairs64Group == NBODY_PAIR_RADII_PER_PASS && NBODY_PAIR_RADII_MAX % NBODY_PAIR_RADII_PER_PASS == 0,
+              "include/nbody.h states the thresholds of a pass");
+
+// The k radii of a call as the passes take them: r2 the `distinct` DISTINCT squares ascending, kPairs64Group to a pass, and slot[q] =
+// where radius q's square stands in r2.  Plain host code, no context: false where a radius is not finite and >= 0 or its square not
+// finite (`*bad_q`: which).
+struct PairRadii {
+  double r2[NBODY_PAIR_RADII_MAX];
+  int slot[NBODY_PAIR_RADII_MAX];
+  int distinct = 0;
+};
+bool pair_radii_plan(const double *radii, int k, PairRadii *P, int *bad_q) {
+  double sq[NBODY_PAIR_RADII_MAX];
+  for (int q = 0; q < k; ++q) {
+    sq[q] = radii[q] * radii[q];
+    if (!(std::isfinite(radii[q]) && radii[q] >= 0.0 && std::isfinite(sq[q]))) { *bad_q = q; return false; }
+    P->r2[q] = sq[q];
+  }
+  std::sort(P->r2, P->r2 + k);
+  P->distinct = (int)(std::unique(P->r2, P->r2 + k) - P->r2);
+  for (int q = 0; q < k; ++q) P->slot[q] = (int)(std::lower_bound(P->r2, P->r2 + P->distinct, sq[q]) - P->r2);
+  return true;
+}
+
+// what both calls check of their radii and output before anything is written; the plan into *P
+int pairs64_plan(nbody_ctx *c, const char *who, const double *radii, int32_t k, const int64_t *count, PairRadii *P) {
+  if (!radii || !count) return fail(c, NBODY_ERR_INVALID, "%s: null radii or output", who);
+  if (k < 1 || k > NBODY_PAIR_RADII_MAX) return fail(c, NBODY_ERR_INVALID, "%s: k = %d outside 1 .. %d", who, (int)k, NBODY_PAIR_RADII_MAX);
+  int bad_q = 0;
+  if (!pair_radii_plan(radii, k, P, &bad_q))
+    return fail(c, NBODY_ERR_INVALID, "%s: radius %d must be finite and >= 0 and its square finite", who, bad_q);
+  return NBODY_OK;
+}
+
+// the bytes of the staging pair behind `first` a call needs: the P.distinct totals, then the workgroups' slots of a pass
+int pairs64_lanes() { return nbody::env_int("NBODY_PAIRS64_LANES", 0); }   // tests: 1 or 2 points per lane, read at every call; it enters no count
+size_t pairs64_bytes(nbody_ctx *c, const PairRadii &P, bool self, int m) {
+  return ((size_t)P.distinct + nbody::pairs64_partial_words(c->p.n_total, m, self, pairs64_lanes())) * 8;
+}
+
+// ceil(P.distinct / kPairs64Group) passes — over m points (ppos: double4 each, device) or, ppos == nullptr, over the ordered pairs of
+// the bodies — add into the P.distinct words at `dcount` (device, inside the staging pair at byte `first`), cleared here; then read
+// back in one copy and handed out in the caller's order, halved where the rows are the bodies
+int pairs64_run(nbody_ctx *c, const PairRadii &P, const void *ppos, int m, size_t first, int32_t k, int64_t *count) {
+  unsigned long long *dcount = (unsigned long long *)((char *)c->d_stage + first);
+  const int lanes = pairs64_lanes();
+  const size_t words = nbody::pairs64_partial_words(c->p.n_total, m, ppos == nullptr, lanes);
+  HIP_TRY(c, hipMemsetAsync(dcount, 0, (size_t)P.distinct * 8, c->stream));
+  for (int g = 0; g < P.distinct; g += nbody::kPairs64Group) {
+    nbody::Pairs64Launch L;
+    L.k = std::min(nbody::kPairs64Group, P.distinct - g); L.count = dcount + g;
+    for (int q = 0; q < L.k; ++q) L.r2[q] = P.r2[g + q];
+    L.lanes = lanes; L.partial = dcount + P.distinct; L.partial_words = words;
+    if (int rc = row_pass64(c, nbody::kPairs64Width, "the fp64 pair-count pass", ppos, m, L,
+                            [&](const nbody::Pairs64Launch &Q) { return nbody::launch_pair_counts_f64(Q, c->stream); }))
+      return rc;
+  }
+  if (int rc = stage_to_host(c, first, (size_t)P.distinct * 8)) return rc;
+  const unsigned long long *h = (const unsigned long long *)((const char *)c->h_stage + first);
+  for (int q = 0; q < k; ++q) count[q] = (int64_t)(ppos ? h[P.slot[q]] : h[P.slot[q]] / 2);
+  return NBODY_OK;
 }
 
 // ---- the fp64 minimum spanning forest (kernels_mst64.hip) ----
@@ -576,6 +640,32 @@ int nbody_get_groups_f64(nbody_ctx *c, double radius, int32_t *label, int32_t *m
     summary->links = (int64_t)(s[2] / 2);
   }
   return NBODY_OK;
+}
+
+int nbody_get_pair_counts_f64(nbody_ctx *c, const double *radii, int32_t k, int64_t *count) {
+  const char *who = "nbody_get_pair_counts_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  PairRadii P;
+  if ((rc = pairs64_plan(c, who, radii, k, count, &P))) return rc;
+  if ((rc = ensure_stage(c, pairs64_bytes(c, P, true, c->p.n_total)))) return rc;
+  return pairs64_run(c, P, nullptr, c->p.n_total, 0, k, count);
+}
+
+int nbody_pair_counts_at_f64(nbody_ctx *c, const double *pos, size_t pos_stride, int32_t n, const double *radii, int32_t k, int64_t *count) {
+  const char *who = "nbody_pair_counts_at_f64";
+  int rc = points64_ready(c, who);
+  if (rc) return rc;
+  PairRadii P;
+  if ((rc = pairs64_plan(c, who, radii, k, count, &P))) return rc;
+  if (n < 0 || !pos || pos_stride < 24) return fail(c, NBODY_ERR_INVALID, "%s: null points, n < 0, or a stride < 24", who);
+  if (n == 0) {
+    for (int q = 0; q < k; ++q) count[q] = 0;
+    return NBODY_OK;
+  }
+  Staged64 s;
+  if ((rc = stage_points64(c, pos, pos_stride, nullptr, 0, false, (size_t)n, pairs64_bytes(c, P, false, n), &s))) return rc;
+  return pairs64_run(c, P, s.d, n, s.skip * 8, k, count);
 }
 
 // The Boruvka rounds are driven from here: clear, pass and fold, pick, hook, compress, then a 4-byte read-back of the edges so far.  No

@@ -473,6 +473,30 @@ hipError_t launch_groups_merge(int *parent, const int *mn, int *hooked, int n, i
 // max over the groups of (size << 32 | 0x7fffffff - label) — integer atomics on cleared words, the same values whatever the order
 hipError_t launch_groups_members(const int *label, const int *degree, int n, int *size, int *members, unsigned long long *sum, hipStream_t s);
 
+// The separation census of an fp64 state, over the bodies or over m points that are not bodies — kernels_pairs64.hip: the group census's
+// pass (its grid, chunks, tiles, d2 and <=) with NO per-row result: how many (row, body) pairs have d2 <= t, for kPairs64Group thresholds
+// t at once.  ppos == nullptr: the rows are the bodies (m == n_total) and the pairs i != j BY INDEX are counted, ORDERED (each unordered
+// pair twice: d2 is symmetric in every bit); else no body is dropped by index.  A NaN d2 and a +inf d2 never count; the padding and the
+// repeated rows never count; a zero-mass body counts.  Every wave counts on its scalar pipe; a workgroup's kPairs64Group totals go to a
+// slot of its own in `partial`, and a fold adds the slots into count[] with integer atomicAdd: the same words whatever the order.
+// `part` is not used (there are no partial rows); the rows still go in the slabs of a width-1 pass, every slab through the same
+// `partial` (the stream orders them) into the same words.
+#ifndef NBODY_PAIRS64_GROUP
+#define NBODY_PAIRS64_GROUP 16   // A/B builds: 8, 16, 32 (profiles/pairs_f64_kernel_resources.txt)
+#endif
+constexpr int kPairs64Group = NBODY_PAIRS64_GROUP;   // thresholds per launch: two SGPRs each and one per counter
+constexpr int kPairs64Width = 1;                     // the slabs' width (no partial row is written)
+struct Pairs64Launch : RowScan64Launch {
+  double r2[kPairs64Group] = {};        // r2[0 .. k): ascending (repeats allowed), each finite and >= 0, or nothing is launched
+  int k = 0;                            // 1 .. kPairs64Group.  The kernel's unused thresholds sit BELOW r2[0] and hold no d2 (-1): the
+                                        // wave leaves the chain at the first of them, so a launch of few thresholds pays for few
+  unsigned long long *count = nullptr;  // [k], device, cleared by the caller: count[q] += the pairs with d2 <= r2[q]
+  unsigned long long *partial = nullptr;   // device work area, written before it is read
+  size_t partial_words = 0;             // the words `partial` holds: at least pairs64_partial_words(n_total, m, ...), or nothing is launched
+};
+size_t pairs64_partial_words(int n_total, int m, bool self, int lanes);   // kPairs64Group words per workgroup of the largest slab
+hipError_t launch_pair_counts_f64(const Pairs64Launch &L, hipStream_t s);
+
 // The minimum spanning forest of an fp64 state in Boruvka rounds — kernels_mst64.hip: launch_nearest_f64's argmin pass with the group
 // census's d2 and its label in the tile's fourth component.  Edges are the pairs i < j with a finite d2 = (dx*dx + dy*dy) + dz*dz
 // (contraction off), ordered by the key (d2, i, j): a strict total order, so the forest is unique.

@@ -1,11 +1,12 @@
-// What the fp64 row scans share (kernels_pot64.hip, kernels_census64.hip, kernels_neighbours64.hip, kernels_groups64.hip, kernels_mst64.hip): rows held in
+// What the fp64 row scans share (kernels_pot64.hip, kernels_census64.hip, kernels_neighbours64.hip, kernels_groups64.hip, kernels_mst64.hip, kernels_pairs64.hip): rows held in
 // registers — the bodies themselves or caller points, one or two per lane — against every body of one chunk, the bodies going through
-// LDS.  The shape of all five tile kernels is jerk_tile_f64_kernel's (jerk_tile64.h; DESIGN.md, "The fp64 row scans"):
+// LDS.  The shape of all six tile kernels is jerk_tile_f64_kernel's (jerk_tile64.h; DESIGN.md, "The fp64 row scans"):
 //   grid.x : blocks of kBlock * IPT rows (lane t holds rows ibase + t + k * kBlock: coalesced; the lanes past m repeat row m - 1 and
 //            write nothing)
 //   grid.y : the chunks of probe_geometry(n_total), [c * j_chunk, min((c + 1) * j_chunk, n_total)); each writes its own partial rows
 // in double-buffered tiles of kJerkTile bodies, tile t + 1 fetched before tile t is consumed, the last tile padded with zeros ON THE
-// ORIGIN (a kernel whose padding must not count keeps it out BY INDEX, j < j1), the bodies of a tile taken kJerk64Jb at a time by
+// ORIGIN (a kernel whose padding must not count keeps it out BY INDEX, j < j1; the separation census, which has no per-pair select to
+// put that in, pads with NaNs and writes totals per workgroup, not partial rows), the bodies of a tile taken kJerk64Jb at a time by
 // broadcast reads in ASCENDING j.
 // Here: the HOST side of that shape, written once — the rows' slabs and the launch grids.  The DEVICE loop stays written out in each of
 // the kernels.  It was tried as one function template with hooks (how body j is fetched, what is staged, what a group of bodies

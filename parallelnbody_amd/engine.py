@@ -193,6 +193,35 @@ def mst_groups(i, j, d2, n, radius):
     return label, members
 
 
+# NBodyEngine.correlation_f64(): the Landy-Szalay estimate per bin (float64, NaN where rr == 0) and the raw pair counts per bin (int64)
+CorrelationResult = collections.namedtuple("CorrelationResult", ("xi", "dd", "dr", "rr"))
+
+
+def pair_histogram(edges, cumulative):
+    """The pairs per bin (edges[b], edges[b + 1]] — the LOWER edge open, the upper closed — from the cumulative counts at the edges
+    (pairs with d2 <= edges[b]^2): int64[len(edges) - 1], the differences of consecutive counts.  The edges must ascend (equal
+    neighbours give an empty bin)."""
+    e = np.asarray(edges, np.float64).reshape(-1)
+    c = np.asarray(cumulative, np.int64).reshape(-1)
+    if e.shape[0] < 2 or c.shape != e.shape:
+        raise ValueError("pair_histogram: at least two edges, and one cumulative count per edge")
+    if not np.all(np.diff(e) >= 0.0):                             # (a NaN edge fails too)
+        raise ValueError("pair_histogram: the edges must ascend")
+    return np.diff(c)
+
+
+def landy_szalay(dd, dr, rr, n, n_random):
+    """xi = (DD - 2 DR + RR) / RR per bin, each term normalised by its number of pairs: DD = dd / (n (n - 1) / 2), DR = dr / (n n_random),
+    RR = rr / (n_random (n_random - 1) / 2), for unordered data-data and random-random counts and data-random (point, body) counts.
+    float64; NaN where rr == 0 (and everywhere where a normalisation is 0)."""
+    dd, dr, rr = (np.asarray(a, np.float64) for a in (dd, dr, rr))
+    n, n_random = float(n), float(n_random)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        DD, DR, RR = dd / (n * (n - 1.0) / 2.0), dr / (n * n_random), rr / (n_random * (n_random - 1.0) / 2.0)
+        xi = (DD - 2.0 * DR + RR) / RR
+    return np.where(rr == 0.0, np.nan, xi)
+
+
 LAGRANGE_FRACTIONS = (0.01,0.02, 0.05, 0.1, 0.2, 0.3, 0.5, 0.7, 0.9)
 
 
@@ -319,6 +348,7 @@ class NBodyEngine:
         self.i_count = i_count if i_count else n_total - i_begin
         self.f64 = p.precision == _lib.PREC_F64
         self._G = float(p.G)   # (binaries_f64's elements)
+        self._device = device  # (correlation_f64's temporary engine)
         self._keep = []   # externally bound tensors kept alive
 
     # -- plumbing --
@@ -1069,6 +1099,65 @@ class NBodyEngine:
         label = self.groups_f64(radius).label
         posm, vel, _ = self.state(np.float64)
         return group_table(label, posm, vel, min_members)
+
+    # -- the fp64 separation census: pair counts at many radii in one pass (fp64 contexts) --
+    def _pair_counts(self, radii, call):
+        r = np.ascontiguousarray(radii, np.float64)
+        flat = r.reshape(-1)
+        count = np.zeros(flat.shape[0], np.int64)
+        for lo in range(0, max(flat.shape[0], 1), _lib.PAIR_RADII_MAX):
+            part = np.ascontiguousarray(flat[lo:lo + _lib.PAIR_RADII_MAX])
+            c = np.zeros(part.shape[0], np.int64)
+            self._check(call(_dp(part), part.shape[0], c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            count[lo:lo + part.shape[0]] = c
+        return count.reshape(r.shape)
+
+    def pair_counts_f64(self, radii):
+        """count: the number of UNORDERED pairs of bodies {i, j}, i != j by index, within each of `radii` (nbody_get_pair_counts_f64):
+        an int64 array shaped like radii.  A pair counts iff d2 <= radius * radius with d2 as radius_counts_f64(); coincident bodies
+        count at radius 0; a NaN or +inf d2 never counts.  The radii may come in any order and with repeats, each finite and >= 0 with
+        a finite square (else ERR_INVALID); any number of them, 64 to a call, 16 distinct ones to an N^2 pass — where one
+        radius_counts_f64() pass answers one.  count == groups_f64(r).summary.links == radius_counts_f64(r).sum() // 2 exactly.
+        Contexts and side effects (none) as radius_counts_f64()."""
+        return self._pair_counts(radii, lambda r, k, c: self._L.nbody_get_pair_counts_f64(self._h, r, k, c))
+
+    def pair_counts_at_f64(self, points, radii):
+        """count: the number of (point, body) pairs within each of `radii`, over every row of `points` and every body
+        (nbody_pair_counts_at_f64): an int64 array shaped like radii.  No body is dropped by index: a point exactly on a body counts
+        that body.  count == radius_counts_at_f64(points, r).sum() exactly; no points: zeros.  Rules, contexts and side effects (none)
+        as pair_counts_f64()."""
+        p = self._rows64(points, "pair_counts_at_f64", "points")
+        return self._pair_counts(radii, lambda r, k, c: self._L.nbody_pair_counts_at_f64(self._h, p.ctypes.data, 24, p.shape[0], r, k, c))
+
+    def pair_histogram_f64(self, edges):
+        """The pair-separation histogram: the unordered pairs of bodies whose separation lies in (edges[b], edges[b + 1]] — the LOWER
+        edge is open, the upper closed; a pair at separation exactly edges[0] is in no bin — for ascending `edges`:
+        int64[len(edges) - 1], the differences of pair_counts_f64(edges) (pair_histogram()), in numpy."""
+        e = np.asarray(edges, np.float64).reshape(-1)
+        if e.shape[0] < 2 or not np.all(np.diff(e) >= 0.0):
+            raise ValueError("pair_histogram_f64: at least two edges, ascending")
+        return pair_histogram(e, self.pair_counts_f64(e))
+
+    def correlation_f64(self, edges, randoms):
+        """The two-point correlation function of the bodies in the bins of pair_histogram_f64(edges), by the Landy-Szalay estimator
+        against the rows of `randoms` ([n_random, >= 3]): a CorrelationResult (xi, dd, dr, rr).  dd: the bodies' pairs per bin
+        (pair_histogram_f64); dr: the (random, body) pairs per bin from pair_counts_at_f64(randoms, edges); rr: the randoms' own pairs
+        per bin, from a temporary fp64 engine on the same device that holds them.  xi = (DD - 2 DR + RR) / RR with DD = dd / (n (n - 1)
+        / 2), DR = dr / (n n_random), RR = rr / (n_random (n_random - 1) / 2) (landy_szalay()); NaN where rr == 0."""
+        e = np.asarray(edges, np.float64).reshape(-1)
+        if e.shape[0] < 2 or not np.all(np.diff(e) >= 0.0):
+            raise ValueError("correlation_f64: at least two edges, ascending")
+        r = self._rows64(randoms, "correlation_f64", "randoms")
+        if r.shape[0] < 2:
+            raise ValueError("correlation_f64: at least two randoms")
+        dd = pair_histogram(e, self.pair_counts_f64(e))
+        dr = pair_histogram(e, self.pair_counts_at_f64(r, e))
+        posm = np.ones((r.shape[0], 4), np.float64)
+        posm[:, :3] = r
+        with NBodyEngine(r.shape[0], device=self._device, precision="f64") as other:
+            other.set_state(posm, np.zeros_like(posm))
+            rr = pair_histogram(e, other.pair_counts_f64(e))
+        return CorrelationResult(landy_szalay(dd, dr, rr, self.n_total, r.shape[0]), dd, dr, rr)
 
     # -- the fp64 minimum spanning tree (fp64 contexts) --
     def mst_f64(self):
