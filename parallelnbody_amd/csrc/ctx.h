@@ -135,7 +135,7 @@ struct nbody_ctx {
   void *pot64 = nullptr;       // nbody_energy_fast: [n_total] double, the bodies' unrounded potentials, then the reduction's workgroup pairs
   int radial_resident = 0;     // nbody_radial_order_f64 / nbody_lagrange_radii_f64: workgroups of the radix pass the device holds at once (0: not asked yet)
   // Hermite stepping of fp64 contexts (capi_hermite.hip), every instance indexed by order: [0] fourth (nbody_hermite_*,
-  // kernels_hermite.hip, kernels_hermite_block.hip), [1] sixth (nbody_hermite6_*, kernels_snap.hip, kernels_hermite6_block.hip)
+  // kernels_hermite.hip, kernels_hermite_block.hip), [1] sixth (nbody_hermite6_*, kernels_snap.hip, kernels_hermite_block.hip)
   nbody::HermiteCache hm[2];          // the bodies' caches
   bool hm_external = false;           // a buffer was bound or a pointer handed out: somebody else may write the state, every call of either order evaluates anew
   nbody::HermiteBlockSession hb[2];   // the block sessions, each on its order's cache

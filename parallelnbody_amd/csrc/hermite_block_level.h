@@ -1,5 +1,5 @@
-// The level rules of the Hermite block time steps (nbody_hermite_block_*, kernels_hermite_block.hip; nbody_hermite6_block_*,
-// kernels_hermite6_block.hip), one function each for the device and the host: the correctors call them per active body,
+// The level rules of the Hermite block time steps (nbody_hermite_block_* and nbody_hermite6_block_*, both in
+// kernels_hermite_block.hip), one function each for the device and the host: the correctors call them per active body,
 // nbody_hermite_block_level and nbody_hermite6_block_level export them so that the CPU tests pin them without a device.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@ __host__ __device__ inline int hermite_block_level(double dt_c, double dt_max, i
   return levels;
 }
 
-// The sixth-order rule (nbody_hermite6_block_*, kernels_hermite6_block.hip).  kk is nbody_hermite6_timescale's per-body
+// The sixth-order rule (nbody_hermite6_block_*).  kk is nbody_hermite6_timescale's per-body
 // k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2), whose step is eta kk^(-1/6).  A cube root is not correctly rounded, so the device and
 // numpy could not agree on it in every bit; the rule therefore compares in the CUBED domain, where every operation is: r = sqrt(kk),
 // e3 = (eta eta) eta, and the level is the smallest k in 0 .. levels with ((h h) h) r <= e3, h = ldexp(dt_max, -k) — which is

@@ -141,6 +141,9 @@ hipError_t launch_tidal(const TidalLaunch &L, hipStream_t s);
 // as +inf), out[1] = the lowest index that attains it, as a double: per-workgroup pairs into `partials` (2 * energy_fast_slots(n) doubles),
 // then one workgroup folds them — a fixed order, no atomics.
 hipError_t launch_tidal_time(const double *t64, int n, double *partials, double *out, hipStream_t s);
+// that fold on its own, for every reduction that leaves (value, index as a double) pairs of this kind in `partials`: out[0] = the largest
+// value of partials[2 q], q < slots, out[1] = the lowest index partials[2 q + 1] that attains it — one workgroup, a fixed order
+hipError_t launch_max_fold(const double *partials, int slots, double *out, hipStream_t s);
 
 // The jerk j = da/dt beside the acceleration, a pair sum over all n_total bodies at every theta — kernels_jerk.hip: with d = x_j - x,
 // w = v_j - v, s^2 = |d|^2 + eps2:  a = sum_j G m_j d / s^3,  j = sum_j G m_j [w / s^3 - 3 (d . w) d / s^5].  With eps2 == 0 a pair at
@@ -197,12 +200,11 @@ hipError_t launch_hermite_time(const double *aj0, const void *a2, const void *a3
 //   launch_hermite_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp) = every body at T_next
 //   launch_hermite_block_evaluate:  the rows of list[first .. first + m) into part, m <= probe_slab_points(n, 3); lanes = bodies per lane
 //   launch_hermite_block_correct:   those bodies corrected from part (the rows of that launch), their T, level, cache and state stored
-struct HermiteBlockLaunch {
+// what both orders' sessions hold (HermiteBlockLaunch, Hermite6BlockLaunch): the state, the scheduler's arrays and the session's rule
+struct HermiteBlockBase {
   void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state
   void *xp = nullptr, *vp = nullptr;                      // [n] double4 each: the predicted state
-  double *aj0 = nullptr;                                  // [n][6]: every body's (a, j) at its own time
-  void *a2 = nullptr, *a3 = nullptr;                      // [n] double4 each
-  void *part = nullptr;                                   // [probe_part_elems(n, m, 3)] float4: the evaluation's partial rows
+  void *part = nullptr;                                   // the evaluation's partial rows: [probe_part_elems(n, m, row width)] float4
   long long *T = nullptr;                                 // [n] ticks
   int *level = nullptr, *list = nullptr;                  // [n] each
   long long *seg_min = nullptr;                           // [slots of hermite_block_segment]
@@ -211,7 +213,13 @@ struct HermiteBlockLaunch {
   unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
   int n = 0, levels = 0;
   int n_field = 0;   // the tracers' arrays: the bodies whose chunks (probe_geometry) the partial rows follow; 0: n
-  double tick = 0.0, dt_max = 0.0, root_eta = 0.0, G = 0.0, eps2 = 0.0;
+  double tick = 0.0, dt_max = 0.0, G = 0.0, eps2 = 0.0;
+};
+struct HermiteBlockLaunch : HermiteBlockBase {
+  static constexpr int kRow = 6;                          // the doubles of a cached row
+  double *aj0 = nullptr;                                  // [n][6]: every body's (a, j) at its own time
+  void *a2 = nullptr, *a3 = nullptr;                      // [n] double4 each
+  double root_eta = 0.0;
 };
 constexpr int kHermiteBlockOneLaneMax = 1024;   // listed bodies up to which the evaluation holds one body per lane (more workgroups)
 int hermite_block_segment(int n, int *slots);   // bodies per scheduler workgroup (a multiple of 256); *slots = the workgroups
@@ -268,28 +276,19 @@ hipError_t launch_hermite6_correct(const Hermite6Launch &L, hipStream_t s);
 hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *a4, const void *a5, int n, bool derivs, double *partials,
                                 double *out, hipStream_t s);
 
-// Sixth-order Hermite block time steps of an fp64 state — kernels_hermite6_block.hip: HermiteBlockLaunch's times, levels, segments and
+// Sixth-order Hermite block time steps of an fp64 state — kernels_hermite_block.hip: HermiteBlockLaunch's times, levels, segments and
 // scheduler around the ACTIVE-SET form of the snap pass (snap_tile64.h: nbody_get_snap_f64's chunks, pair operations and order) and the
 // sixth-order predictor and corrector with a dt per body; the level rule is hermite6_block_level (hermite_block_level.h).
 //   launch_hermite6_block_init:      T := 0; level := level_in (device, may be null: the level of eta_start |a0| / |j0| from ajs0)
 //   launch_hermite6_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp, ap) = every body at T_next
 //   launch_hermite6_block_evaluate:  the rows of list[first .. first + m) into part, m <= probe_slab_points(n, kSnapRowWidth)
 //   launch_hermite6_block_correct:   those bodies corrected from part (the rows of that launch), their T, level, cache and state stored
-struct Hermite6BlockLaunch {
-  void *posm = nullptr, *vel = nullptr, *acc = nullptr;   // [n] double4 each: the live state
-  void *xp = nullptr, *vp = nullptr, *ap = nullptr;       // [n] double4 each: the predicted state and its predicted accelerations
+struct Hermite6BlockLaunch : HermiteBlockBase {
+  static constexpr int kRow = 9;                          // the doubles of a cached row
+  void *ap = nullptr;                                     // [n] double4: the predicted accelerations
   double *ajs0 = nullptr;                                 // [n][9]: every body's (a, j, s) at its own time
   void *a3 = nullptr, *a4 = nullptr, *a5 = nullptr;       // [n] double4 each
-  void *part = nullptr;                                   // [probe_part_elems(n, n, kSnapRowWidth)] float4: the evaluation's partial rows
-  long long *T = nullptr;                                 // [n] ticks
-  int *level = nullptr, *list = nullptr;                  // [n] each
-  long long *seg_min = nullptr;                           // [slots of hermite_block_segment]
-  int *seg_cnt = nullptr;                                 // [slots]
-  long long *record = nullptr;                            // [2]: T_next, m
-  unsigned long long *floor_hits = nullptr;               // [1]: bodies clamped to the deepest level since the session began
-  int n = 0, levels = 0;
-  int n_field = 0;   // as HermiteBlockLaunch's
-  double tick = 0.0, dt_max = 0.0, eta = 0.0, G = 0.0, eps2 = 0.0;
+  double eta = 0.0;
 };
 hipError_t launch_hermite6_block_init(const Hermite6BlockLaunch &L, const int *level_in, double eta_start, hipStream_t s);
 hipError_t launch_hermite6_block_schedule(const Hermite6BlockLaunch &L, hipStream_t s);

@@ -183,13 +183,6 @@ __global__ __launch_bounds__(kBlock) void jerk_time_parts_kernel(const double *_
   const TidalMax r = tidal_max_workgroup(a, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
-__global__ __launch_bounds__(kBlock) void jerk_time_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax a{-1.0, 0x7fffffff};
-  for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(a, part[2 * q], (int)part[2 * q + 1]);
-  const TidalMax r = tidal_max_workgroup(a, red);
-  if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
-}
 
 }  // namespace
 
@@ -239,8 +232,7 @@ hipError_t launch_jerk_time(const double *aj64, int n, double *partials, double 
   if (n <= 0 || !aj64 || !partials || !out) return hipErrorInvalidValue;
   const int slots = energy_fast_slots(n);
   hipLaunchKernelGGL(jerk_time_parts_kernel, dim3(slots), dim3(kBlock), 0, s, aj64, n, partials);
-  hipLaunchKernelGGL(jerk_time_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)partials, slots, out);
-  return hipGetLastError();
+  return launch_max_fold(partials, slots, out, s);
 }
 
 }  // namespace nbody

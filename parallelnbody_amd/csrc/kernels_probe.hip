@@ -335,7 +335,8 @@ __global__ __launch_bounds__(kBlock) void tidal_time_parts_kernel(const double *
   const TidalMax r = tidal_max_workgroup(a, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
-__global__ __launch_bounds__(kBlock) void tidal_time_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
+// the one fold of every (value, body) maximum: the workgroups' pairs in a fixed order (launch_max_fold)
+__global__ __launch_bounds__(kBlock) void max_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
   __shared__ TidalMax red[kBlock / 64];
   TidalMax a{-1.0, 0x7fffffff};
   for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(a, part[2 * q], (int)part[2 * q + 1]);
@@ -420,7 +421,12 @@ hipError_t launch_tidal_time(const double *t64, int n, double *partials, double 
   if (n <= 0 || !t64 || !partials || !out) return hipErrorInvalidValue;
   const int slots = energy_fast_slots(n);
   hipLaunchKernelGGL(tidal_time_parts_kernel, dim3(slots), dim3(kBlock), 0, s, t64, n, partials);
-  hipLaunchKernelGGL(tidal_time_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)partials, slots, out);
+  return launch_max_fold(partials, slots, out, s);
+}
+
+hipError_t launch_max_fold(const double *partials, int slots, double *out, hipStream_t s) {
+  if (slots <= 0 || !partials || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(max_fold_kernel, dim3(1), dim3(kBlock), 0, s, partials, slots, out);
   return hipGetLastError();
 }
 

@@ -11,15 +11,17 @@
 //   hermite6_predict_kernel <- (xp, vp, ap) from (x, v, a0, j0, s0, a3): the Taylor series to fifth / fourth / third order
 //   hermite6_correct_kernel <- (x, v) from (a0, j0, s0) and the (a1, j1, s1) of the predicted state; the stored acceleration; a3, a4, a5
 //                              at the new time, from the quintic through both ends
-//   hermite6_time_*_kernel  <- k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2) per body — without derivatives |j0|^2 / |a0|^2 —, its
-//                              maximum and that body, folded in a fixed order (point_tile.h: tidal_max_*)
+//   hermite6_time_parts_kernel <- k = (|a3| |a5| + |a4|^2) / (|a0| |s0| + |j0|^2) per body — without derivatives |j0|^2 / |a0|^2 —, its
+//                              maximum and that body, folded in a fixed order by launch_max_fold (kernels_probe.hip)
+// The arithmetic of the stepping kernels is hermite_step64.h's, which the block kernels (kernels_hermite_block.hip) call too.
 // Contraction is off for the whole file: every fused multiply-add of the tile loop is written out as fma(), and EVERY operation of the
-// stepping kernels is one correctly rounded fp64 operation in the order the comments write it, so that numpy reproduces a step in
+// stepping kernels is one correctly rounded fp64 operation in the order that header writes it, so that numpy reproduces a step in
 // every bit from the (a, j, s) of nbody_get_snap_f64 (tests/hermite6_ref.py).  No scratch, no atomics, no grid-wide waits.
 #include "kernels.h"
 
 #include <algorithm>
 
+#include "hermite_step64.h"
 #include "point_tile.h"
 #include "snap_tile64.h"
 
@@ -52,79 +54,42 @@ __global__ __launch_bounds__(kBlock) void snap_fold_f64_kernel(const double *__r
 
 // ---- sixth-order Hermite stepping: one lane per body ----
 
-// a body's (a, j, s) in the snap fold's rows: nine doubles, 72 bytes apart
-struct Ajs { double a[3], j[3], s[3]; };
-__device__ __forceinline__ Ajs load_ajs(const double *__restrict__ ajs, int i) {
-  const double *r = ajs + 9 * (size_t)i;
-  return Ajs{{r[0], r[1], r[2]}, {r[3], r[4], r[5]}, {r[6], r[7], r[8]}};
-}
-
-// per component  xp = ((((x + dt v) + c2 a0) + c3 j0) + c4 s0) + c5 a3;  vp = (((v + dt a0) + c2 j0) + c3 s0) + c4 a3;
-// ap = ((a0 + dt j0) + c2 s0) + c3 a3;  xp.w = m, vp.w = 0, ap.w = 0
-struct Hermite6PredictConsts { double dt, c2, c3, c4, c5; };
+// (xp, vp, ap) := hermite6_predict of every body with the call's constants
 __global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(const double4 *__restrict__ posm, const double4 *__restrict__ vel,
                                                                   const double *__restrict__ ajs0, const double4 *__restrict__ a3,
                                                                   double4 *__restrict__ xp, double4 *__restrict__ vp,
-                                                                  double4 *__restrict__ ap, int n, Hermite6PredictConsts k) {
+                                                                  double4 *__restrict__ ap, int n, Hermite6Predict k) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  const double4 x = posm[i], v = vel[i], d3 = a3[i];
-  const Ajs s = load_ajs(ajs0, i);
-  auto px = [&](double xc, double vc, double a, double j, double sn, double c) {
-    return ((((xc + k.dt * vc) + k.c2 * a) + k.c3 * j) + k.c4 * sn) + k.c5 * c;
-  };
-  auto pv = [&](double vc, double a, double j, double sn, double c) { return (((vc + k.dt * a) + k.c2 * j) + k.c3 * sn) + k.c4 * c; };
-  auto pa = [&](double a, double j, double sn, double c) { return ((a + k.dt * j) + k.c2 * sn) + k.c3 * c; };
-  xp[i] = make_double4(px(x.x, v.x, s.a[0], s.j[0], s.s[0], d3.x), px(x.y, v.y, s.a[1], s.j[1], s.s[1], d3.y),
-                       px(x.z, v.z, s.a[2], s.j[2], s.s[2], d3.z), x.w);
-  vp[i] = make_double4(pv(v.x, s.a[0], s.j[0], s.s[0], d3.x), pv(v.y, s.a[1], s.j[1], s.s[1], d3.y), pv(v.z, s.a[2], s.j[2], s.s[2], d3.z), 0.0);
-  ap[i] = make_double4(pa(s.a[0], s.j[0], s.s[0], d3.x), pa(s.a[1], s.j[1], s.s[1], d3.y), pa(s.a[2], s.j[2], s.s[2], d3.z), 0.0);
+  hermite6_predict(k, posm, vel, ajs0, a3, xp, vp, ap, i);
 }
 
-// per component, with (a1, j1, s1) the snap pass's answer at (xp, vp) given ap:
-//   v1 = v + ((ch (a0 + a1) + c10 (j0 - j1)) + c120 (s0 + s1));   x1 = x + ((ch (v + v1) + c10 (a0 - a1)) + c120 (j0 + j1))
-//   R1 = ((a1 - a0) - dt j0) - c2 s0;   R2 = dt ((j1 - j0) - dt s0);   R3 = d2 (s1 - s0)
-//   X = ((60 R1) - (24 R2)) + (3 R3);   Y = ((168 R2) - (360 R1)) - (24 R3);   Z = ((720 R1) - (360 R2)) + (60 R3)
-//   a3 = ((X + Y) + 0.5 Z) / d3;   a4 = (Y + Z) / d4;   a5 = Z / d5
-// x := x1 (the mass stays), v := v1 (its fourth component stays), acc := (a1, 0), a3, a4, a5 := (those, 0)
-struct Hermite6Consts { double dt, ch, c2, c10, c120, d2, d3, d4, d5; };
+// hermite6_correct per component with (a1, j1, s1) the row of ajs1:  x := x1 (the mass stays), v := v1 (its fourth component stays), acc := (a1, 0),
+// a3, a4, a5 := (those, 0)
 __global__ __launch_bounds__(kBlock) void hermite6_correct_kernel(double4 *__restrict__ posm, double4 *__restrict__ vel,
                                                                   double4 *__restrict__ acc, const double *__restrict__ ajs0,
                                                                   const double *__restrict__ ajs1, double4 *__restrict__ a3,
                                                                   double4 *__restrict__ a4, double4 *__restrict__ a5, int n,
-                                                                  Hermite6Consts k) {
+                                                                  Hermite6Correct k) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const double4 x = posm[i], v = vel[i];
   const Ajs s0 = load_ajs(ajs0, i), s1 = load_ajs(ajs1, i);
   const double xc[3] = {x.x, x.y, x.z}, vc[3] = {v.x, v.y, v.z};
-  double x1[3], v1[3], q3[3], q4[3], q5[3];
+  Hermite6Comp r[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    v1[q] = vc[q] + ((k.ch * (s0.a[q] + s1.a[q]) + k.c10 * (s0.j[q] - s1.j[q])) + k.c120 * (s0.s[q] + s1.s[q]));
-    x1[q] = xc[q] + ((k.ch * (vc[q] + v1[q]) + k.c10 * (s0.a[q] - s1.a[q])) + k.c120 * (s0.j[q] + s1.j[q]));
-    const double R1 = ((s1.a[q] - s0.a[q]) - k.dt * s0.j[q]) - k.c2 * s0.s[q];
-    const double R2 = k.dt * ((s1.j[q] - s0.j[q]) - k.dt * s0.s[q]);
-    const double R3 = k.d2 * (s1.s[q] - s0.s[q]);
-    const double X = ((60.0 * R1) - (24.0 * R2)) + (3.0 * R3);
-    const double Y = ((168.0 * R2) - (360.0 * R1)) - (24.0 * R3);
-    const double Z = ((720.0 * R1) - (360.0 * R2)) + (60.0 * R3);
-    q3[q] = ((X + Y) + 0.5 * Z) / k.d3;
-    q4[q] = (Y + Z) / k.d4;
-    q5[q] = Z / k.d5;
-  }
-  posm[i] = make_double4(x1[0], x1[1], x1[2], x.w);
-  vel[i] = make_double4(v1[0], v1[1], v1[2], v.w);
+  for (int q = 0; q < 3; ++q) r[q] = hermite6_correct(k, xc[q], vc[q], s0.a[q], s0.j[q], s0.s[q], s1.a[q], s1.j[q], s1.s[q]);
+  posm[i] = make_double4(r[0].x, r[1].x, r[2].x, x.w);
+  vel[i] = make_double4(r[0].v, r[1].v, r[2].v, v.w);
   acc[i] = make_double4(s1.a[0], s1.a[1], s1.a[2], 0.0);
-  a3[i] = make_double4(q3[0], q3[1], q3[2], 0.0);
-  a4[i] = make_double4(q4[0], q4[1], q4[2], 0.0);
-  a5[i] = make_double4(q5[0], q5[1], q5[2], 0.0);
+  a3[i] = make_double4(r[0].a3, r[1].a3, r[2].a3, 0.0);
+  a4[i] = make_double4(r[0].a4, r[1].a4, r[2].a4, 0.0);
+  a5[i] = make_double4(r[0].a5, r[1].a5, r[2].a5, 0.0);
 }
 
-// nbody_hermite6_timescale's candidates (k, body), reduced as jerk_time_parts_kernel reduces its own.  derivs: norms
-// sqrt((x x + y y) + z z), k = (|a3| |a5| + |a4| |a4|) / (|a0| |s0| + |j0| |j0|); else nbody_jerk_time's k = |j0|^2 / |a0|^2 of the
-// squared norms.  0 / 0 = 0, x / 0 = +inf, and a value that is not finite counts as +inf.
-__device__ __forceinline__ double norm3_dev(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+// nbody_hermite6_timescale's candidates (k, body), reduced as jerk_time_parts_kernel reduces its own.  derivs: hermite6_ratio of the six
+// norms; else nbody_jerk_time's k = |j0|^2 / |a0|^2 of the squared norms.  0 / 0 = 0, x / 0 = +inf, and a value that is not finite
+// counts as +inf.
 __global__ __launch_bounds__(kBlock) void hermite6_time_parts_kernel(const double *__restrict__ ajs0, const double4 *__restrict__ a3,
                                                                      const double4 *__restrict__ a4, const double4 *__restrict__ a5,
                                                                      int n, int derivs, double *__restrict__ part) {
@@ -132,30 +97,17 @@ __global__ __launch_bounds__(kBlock) void hermite6_time_parts_kernel(const doubl
   TidalMax m{-1.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const Ajs s = load_ajs(ajs0, i);
-    double num, den;
+    Ratio r;
     if (derivs) {
       const double4 d3 = a3[i], d4 = a4[i], d5 = a5[i];
-      const double A0 = norm3_dev(s.a[0], s.a[1], s.a[2]), J0 = norm3_dev(s.j[0], s.j[1], s.j[2]), S0 = norm3_dev(s.s[0], s.s[1], s.s[2]);
-      const double A3 = norm3_dev(d3.x, d3.y, d3.z), A4 = norm3_dev(d4.x, d4.y, d4.z), A5 = norm3_dev(d5.x, d5.y, d5.z);
-      num = A3 * A5 + A4 * A4;
-      den = A0 * S0 + J0 * J0;
+      r = hermite6_ratio(norm3(s.a[0], s.a[1], s.a[2]), norm3(s.j[0], s.j[1], s.j[2]), norm3(s.s[0], s.s[1], s.s[2]), norm3(d3), norm3(d4), norm3(d5));
     } else {
-      num = (s.j[0] * s.j[0] + s.j[1] * s.j[1]) + s.j[2] * s.j[2];
-      den = (s.a[0] * s.a[0] + s.a[1] * s.a[1]) + s.a[2] * s.a[2];
+      r = Ratio{sqnorm3(s.j[0], s.j[1], s.j[2]), sqnorm3(s.a[0], s.a[1], s.a[2])};
     }
-    double k = (num == 0.0 && den == 0.0) ? 0.0 : num / den;
-    if (!(k <= 0x1.fffffffffffffp1023)) k = __builtin_inf();
-    tidal_max_take(m, k, i);
+    tidal_max_take(m, ratio_k<true>(r), i);
   }
   const TidalMax r = tidal_max_workgroup(m, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
-}
-__global__ __launch_bounds__(kBlock) void hermite6_time_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax m{-1.0, 0x7fffffff};
-  for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(m, part[2 * q], (int)part[2 * q + 1]);
-  const TidalMax r = tidal_max_workgroup(m, red);
-  if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
 }
 
 inline bool bad(const Hermite6Launch &L) {
@@ -192,19 +144,17 @@ hipError_t launch_snap_fold_f64(const void *part, int m, int j_split, double *aj
 // the constants are the host's own doubles — products and one quotient each, in the order written (nothing a host compiler could fuse)
 hipError_t launch_hermite6_predict(const Hermite6Launch &L, hipStream_t s) {
   if (bad(L) || !L.xp || !L.vp || !L.ap) return hipErrorInvalidValue;
-  const double dt = L.dt, d2 = dt * dt;
-  const Hermite6PredictConsts k{dt, d2 * 0.5, (d2 * dt) / 6.0, (d2 * d2) / 24.0, ((d2 * d2) * dt) / 120.0};
   hipLaunchKernelGGL(hermite6_predict_kernel, dim3((L.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double4 *)L.posm,
-                     (const double4 *)L.vel, L.ajs0, (const double4 *)L.a3, (double4 *)L.xp, (double4 *)L.vp, (double4 *)L.ap, L.n, k);
+                     (const double4 *)L.vel, L.ajs0, (const double4 *)L.a3, (double4 *)L.xp, (double4 *)L.vp, (double4 *)L.ap, L.n,
+                     hermite6_predict_consts(L.dt));
   return hipGetLastError();
 }
 
 hipError_t launch_hermite6_correct(const Hermite6Launch &L, hipStream_t s) {
   if (bad(L) || !L.acc || !L.ajs1 || !L.a4 || !L.a5) return hipErrorInvalidValue;
-  const double dt = L.dt, d2 = dt * dt, d4 = d2 * d2;
-  const Hermite6Consts k{dt, dt * 0.5, d2 * 0.5, d2 / 10.0, (d2 * dt) / 120.0, d2, d2 * dt, d4, d4 * dt};
   hipLaunchKernelGGL(hermite6_correct_kernel, dim3((L.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (double4 *)L.posm, (double4 *)L.vel,
-                     (double4 *)L.acc, L.ajs0, L.ajs1, (double4 *)L.a3, (double4 *)L.a4, (double4 *)L.a5, L.n, k);
+                     (double4 *)L.acc, L.ajs0, L.ajs1, (double4 *)L.a3, (double4 *)L.a4, (double4 *)L.a5, L.n,
+                     hermite6_correct_consts(L.dt));
   return hipGetLastError();
 }
 
@@ -214,8 +164,7 @@ hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *
   const int slots = energy_fast_slots(n);
   hipLaunchKernelGGL(hermite6_time_parts_kernel, dim3(slots), dim3(kBlock), 0, s, ajs0, (const double4 *)a3, (const double4 *)a4,
                      (const double4 *)a5, n, derivs ? 1 : 0, partials);
-  hipLaunchKernelGGL(hermite6_time_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)partials, slots, out);
-  return hipGetLastError();
+  return launch_max_fold(partials, slots, out, s);
 }
 
 }  // namespace nbody
