@@ -1,6 +1,7 @@
 // integration/ue4/OctreeSearch.cpp — see OctreeSearch.h next to it.  Every method keeps the reference's observable
 // behaviour (silent guards, what gets drawn and in which order); its body is a call into nbody::OctreeSearchActor.
-// NOT COMPILED IN THIS REPOSITORY (no Unreal Engine 4.9 here).
+// Compiled and run in this repository against stand-in engine headers (oracle/ue4_standin/), not against Unreal Engine 4.9: see
+// OctreeSearch.h next to this file.
 #include "NBody.h"
 #include "OctreeSearch.h"
 #include "DrawDebugHelpers.h"

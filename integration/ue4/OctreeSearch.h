@@ -5,8 +5,12 @@
 // (reference lines cited as OctreeSearch.h:N / OctreeSearch.cpp:N); the Octree class and the per-particle loops of the
 // reference are gone — their work happens on the GPU.
 //
-// NOT COMPILED IN THIS REPOSITORY: Unreal Engine 4.9 and UnrealBuildTool are not available here.  What the file
-// forwards to is compiled and tested (tests/cpp/actor_parity.cpp, tests/test_actor_gpu.py).
+// Unreal Engine 4.9 and UnrealBuildTool are not available in this repository, so the two files have never been built against the
+// engine.  They ARE compiled, linked with libnbody_amd.so and run against functional stand-ins for the engine names they use
+// (oracle/ue4_standin/: FVector, TArray, AActor, the UnrealHeaderTool macros), around the same driver that runs the reference's own
+// OctreeSearch.cpp (oracle/ref_driver.cpp): records, Size and the DrawDebugBox / DrawDebugPoint sequence of every frame equal the
+// reference's recorded ones byte for byte (tests/test_reference_parity_gpu.py).  What they forward to is tested on its own as well
+// (tests/cpp/actor_parity.cpp, tests/test_actor_gpu.py).
 // Module wiring, Source/NBody/NBody.Build.cs:
 //     PublicIncludePaths.Add(Path.Combine(ThirdPartyPath, "nbody_amd", "include"));
 //     PublicAdditionalLibraries.Add(Path.Combine(ThirdPartyPath, "nbody_amd", "lib", "libnbody_amd.so"));

@@ -4,12 +4,22 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this
  * library.  Nothing under parallelnbody_amd/ links, imports or calls it.
  *
- * PARITY UNPINNED.  The reference (Milias/ParallelNbody) ships no tests, golden vectors or
- * fixtures for this path, and its sources need Unreal Engine 4.9 headers plus
- * UnrealHeaderTool-generated code that this image does not have, so the reference cannot be
- * built here without writing stand-ins for them (not allowed).  This file is therefore a
- * restatement by reading, checked only against analytic known answers and against an
- * independent fp64 direct sum (tests/test_oracle.py).
+ * PARITY.  The reference (Milias/ParallelNbody) ships no tests, golden vectors or fixtures for
+ * this path.  This file is a restatement by reading — and it is held, byte for byte, to the
+ * reference's own Source/NBody/OctreeSearch.{h,cpp}, compiled unchanged by g++ against functional
+ * stand-ins for the Unreal Engine 4.9 names they use (oracle/ue4_standin/, oracle/ref_driver.cpp,
+ * `make reference` -> oracle/_ref/nbody_ref; tests/test_reference_build.py):
+ *   PINNED      the reference's source under g++ -std=c++11 -O2 -ffp-contract=off and glibc on
+ *               x86-64 SSE2: frames (records, Size, root centre of mass), forces at theta 0 .. 1.7
+ *               with zero and nonzero roots, the DrawOctreeBoxes sequence.  With pow_mode 0 and
+ *               div_mode 0 — the defaults — no byte differs on any of 363 fuzzed scenes of nine
+ *               families; with pow_mode 3 (what the device computes) none differs on the same 363
+ *               either.  div_mode 1, pow_mode 1 and pow_mode 2 each change more than half of the
+ *               shipped scene's accelerations after one Tick: the check can fail.
+ *   NOT PINNED  the engine's real FVector (the stand-in follows the 4.9 API as described below;
+ *               it is not engine code) and Visual Studio 2013's pow overload set (pow_mode 1, 2).
+ * Besides: analytic known answers, an independent fp64 direct sum and a second restatement in
+ * Python (tests/test_oracle.py).
  *
  * Every function cites the reference lines it restates (paths relative to
  * /root/reference/Source/NBody/).  Arithmetic is restated operation by operation in the
@@ -21,8 +31,8 @@
  * differences in X,Y,Z order; operator/=(float) multiplies by the fp32 reciprocal;
  * GetAbsMax = max(max(|X|,|Y|),|Z|)) and the C runtime's pow.  The .sln names Visual Studio
  * 2013, whose <cmath> may resolve pow(float,int) to a float overload rather than C++11's
- * double promotion; `pow_mode` selects the reading (0 = double pow, the C++11 rule and the
- * default; 1 = powf; 2 = float d*(d*d); 3 = the correctly rounded cube in double, (d*d)*d — d*d is
+ * double promotion; `pow_mode` selects the reading (0 = double pow, the C++11 rule, the
+ * default, and what the compiled reference equals; 1 = powf; 2 = float d*(d*d); 3 = the correctly rounded cube in double, (d*d)*d — d*d is
  * exact for a float d — which a correctly rounded pow would return and glibc's returns for all but a
  * few arguments in a thousand).  The readings differ by a few fp32 ulp per pair at most.
  */

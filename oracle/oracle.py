@@ -1,7 +1,10 @@
 """ctypes/numpy front end of the CPU oracle (oracle/nbody_oracle.c).  TEST INFRASTRUCTURE ONLY.
 
 Importers allowed: tests/, __graft_entry__.smoke(), bench.py's cpu_baseline leg.  The product
-package (parallelnbody_amd/) never imports this module.  PARITY UNPINNED — see nbody_oracle.c.
+package (parallelnbody_amd/) never imports this module.
+
+PARITY: pinned against the reference's own source compiled with g++ (oracle/_ref/nbody_ref, oracle/reference.py,
+tests/test_reference_build.py); what that pins and what it leaves open is in the header of nbody_oracle.c.
 """
 import ctypes
 import os
@@ -23,10 +26,13 @@ PARTICLE_DTYPE = np.dtype(
 
 
 def build(force=False):
-    """Compile the oracle with gcc (see oracle/Makefile)."""
+    """Compile the oracle with gcc and — where the reference's sources are present — the reference itself into oracle/_ref/
+    (see oracle/Makefile; without the sources oracle/_ref/ is left as it is)."""
     src = os.path.join(_HERE, "nbody_oracle.c")
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
         subprocess.check_call(["make", "-C", _HERE, "-B", "libnbody_oracle.so"], stdout=subprocess.DEVNULL)
+    from . import reference
+    reference.build()
     return _LIB_PATH
 
 

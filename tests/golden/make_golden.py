@@ -1,9 +1,9 @@
 """Regenerates tests/golden/*.npz.
 
 Inputs come from the product's seeded host-side generators (nbody_ic_plummer / nbody_ic_reference_box —
-no GPU involved); expected outputs come from the CPU oracle (oracle/nbody_oracle.c).  The reference
-itself cannot be built in this image (it needs Unreal Engine 4.9 headers), so these fixtures pin the
-ORACLE's outputs, not the reference's: parity stays "unpinned" (see DESIGN.md).
+no GPU involved); expected outputs come from the CPU oracle (oracle/nbody_oracle.c), so these fixtures pin the
+ORACLE's outputs.  What the compiled reference itself writes is recorded by make_reference_golden.py next to this file
+(reference_*.npz); tests/test_reference_build.py holds the oracle — `acc_tree0` of both files included — to it.
 
     python tests/golden/make_golden.py
 """

@@ -1,7 +1,7 @@
 """The CPU oracle against analytic answers, an independent fp64 sum, its own tree walk and the
-committed fixtures.  No GPU.  (The reference ships no tests or vectors for this path and cannot be
-built here: the oracle is 'parity unpinned' — these tests pin the restatement to physics and to
-itself, which is the most this image allows.)"""
+committed fixtures.  No GPU.  (The reference ships no tests or vectors for this path: these tests pin
+the restatement to physics and to itself.  tests/test_reference_build.py holds it to the reference's
+own compiled code.)"""
 import os
 
 import numpy as np
@@ -452,6 +452,21 @@ def test_simd_cpu_baseline_is_the_same_pair_law(oracle):
     soft = oracle.forces_simd_f32(pos, mass, eps=2.0, i0=100, i1=200, nthreads=2)
     ref = oracle.forces_direct_f64(pos.astype(np.float64), mass.astype(np.float64), eps=2.0, i0=100, i1=200)
     assert (np.linalg.norm(soft - ref, axis=1) / np.linalg.norm(ref, axis=1)).max() < 2e-5
+
+
+def test_loading_the_throughput_baseline_leaves_the_float_environment_alone(oracle):
+    # libnbody_cpubase.so is compiled with -ffast-math; were it LINKED with it, gcc's crtfastmath.o would switch the loading process to
+    # flush-to-zero / denormals-are-zero, and every oracle call after it would flush denormals the reference keeps (oracle/Makefile).
+    # In a fresh process, so that the order of the tests cannot hide it: an fp32 product that is a denormal, before and after the load.
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import numpy as np; from oracle import oracle as O; a = np.float32(1e-38); h = np.float32(0.5); "
+            "before = float(a * h); O.cpubase(); O.lib(); print(before, float(a * h))")
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    before, after = (float(w) for w in out.stdout.split())
+    assert 0 < before < 1.1754944e-38 and after == before, out.stdout      # (below FLT_MIN: a denormal, and still one)
 
 
 def test_child_centre_in_fp32_equals_the_reference_double_expression(tmp_path):

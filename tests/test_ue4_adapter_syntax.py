@@ -1,6 +1,7 @@
 """integration/ue4/OctreeSearch.{h,cpp} — the UE4 adapter, this repository's own code — through a compiler's parser once.
 
-Unreal Engine 4.9 and UnrealHeaderTool are not in the image, so the adapter cannot be BUILT here.  tests/cpp/ue4_syntax/ declares
+Unreal Engine 4.9 and UnrealHeaderTool are not in the image, so the adapter cannot be built against the engine (it is built and run
+against functional stand-ins by tests/test_reference_parity_gpu.py; this file is the parse alone, no GPU).  tests/cpp/ue4_syntax/ declares
 the minimum of the engine's names the two files use (AActor, TArray, FVector, FColor, DrawDebug*, the UHT macros as no-ops) and
 `g++ -fsyntax-only` reads the adapter against them and against the real include/nbody_actor.hpp.  It pins no arithmetic, is no
 oracle and no build of the reference (tests/cpp/ue4_syntax/README.md); it catches typos, missing members and signature drift.
