@@ -194,7 +194,7 @@ hipError_t launch_hermite_time(const double *aj0, const void *a2, const void *a3
 
 // Hermite block time steps of an fp64 state — kernels_hermite_block.hip: per-body times T (ticks of dt_max 2^-levels) and levels, a
 // scheduler that lists the bodies due next in ascending index and predicts EVERY body to that time, the fp64 jerk pass on the listed
-// bodies alone (jerk_tile64.h: nbody_get_jerk_f64's chunks, pair operations and order), and a corrector for the listed bodies that adds
+// bodies alone (deriv_tile64.h: nbody_get_jerk_f64's chunks, pair operations and order), and a corrector for the listed bodies that adds
 // the chunks' rows, steps the body by its own dt and chooses its next level (hermite_block_level.h).
 //   launch_hermite_block_init:      T := 0; level := level_in (device, may be null: the level of eta_start |a| / |j| from aj0)
 //   launch_hermite_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp) = every body at T_next
@@ -277,7 +277,7 @@ hipError_t launch_hermite6_time(const double *ajs0, const void *a3, const void *
                                 double *out, hipStream_t s);
 
 // Sixth-order Hermite block time steps of an fp64 state — kernels_hermite_block.hip: HermiteBlockLaunch's times, levels, segments and
-// scheduler around the ACTIVE-SET form of the snap pass (snap_tile64.h: nbody_get_snap_f64's chunks, pair operations and order) and the
+// scheduler around the ACTIVE-SET form of the snap pass (deriv_tile64.h: nbody_get_snap_f64's chunks, pair operations and order) and the
 // sixth-order predictor and corrector with a dt per body; the level rule is hermite6_block_level (hermite_block_level.h).
 //   launch_hermite6_block_init:      T := 0; level := level_in (device, may be null: the level of eta_start |a0| / |j0| from ajs0)
 //   launch_hermite6_block_schedule:  record[0] = T_next, record[1] = m, list[0 .. m) ascending, (xp, vp, ap) = every body at T_next

@@ -23,15 +23,6 @@ template <typename T> struct V4;
 template <> struct V4<float> { using type = float4; };
 template <> struct V4<double> { using type = double4; };
 
-// 1/sqrt(x): v_rsq_f64 seed (~2^-26 relative) and one third-order step, y (1 + e/2 + 3/8 e^2) with e = 1 - x y^2
-// (error ~e^3, far below 2^-53; five ops where two Newton steps take seven) — as in kernels_sym64.hip
-__device__ __forceinline__ double rsq_dev(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = fma(-(x * y), y, 1.0);
-  const double q = e * fma(e, 0.375, 0.5);
-  return fma(y, q, y);
-}
-
 // Plain or Kahan-compensated 3-vector accumulator.
 template <typename T, bool KAHAN> struct Acc3;
 template <typename T> struct Acc3<T, false> {
@@ -325,14 +316,6 @@ __global__ __launch_bounds__(kBlock) void forces_tile_pk_kernel(const float4 *__
     if (il1 < i_count) accp[(size_t)c * i_count + il1] = make_float4(sx.y, sy.y, sz.y, 0.f);
   }
   clock_end(clk, stamp);
-}
-
-// HIP's __fmul_rn/__fadd_rn are plain * and + and get contracted into FMAs under the default
-// -ffp-contract=fast; the pragma keeps the two roundings of the reference's operators (FVector's * and +).
-template <typename T> __device__ __forceinline__ T mul_add_sep(T a, T b, T c) {
-#pragma clang fp contract(off)
-  const T p = a * b;
-  return c + p;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -2,15 +2,10 @@
 // — see bh_common.h.
 #include "bh_common.h"
 #include "bh_force_term.h"
+#include "pk_common.h"   // mul_add_sep
 
 namespace nbody {
 namespace bh {
-
-template <typename T> __device__ __forceinline__ T mul_add_sep(T a, T b, T c) {
-#pragma clang fp contract(off)
-  const T p = a * b;
-  return c + p;
-}
 
 // own[]: a count per block of kB sorted positions, then every block adds up the counts before it and ranks its own bodies (two
 // launches of a few microseconds; the list has exactly `count` entries whatever the order is)

@@ -236,8 +236,8 @@ __global__ __launch_bounds__(kBlock) void forces_block_pk_kernel(const float4 *_
   if (finisher) acc_out[il] = make_float4(ax, ay, az, 0.f);
   if (!integrate) return;
   const float4 x0 = x;
-  vv.x = mul_add_sep2(dt, ax, vv.x); vv.y = mul_add_sep2(dt, ay, vv.y); vv.z = mul_add_sep2(dt, az, vv.z);
-  x.x = mul_add_sep2(dt, vv.x, x.x); x.y = mul_add_sep2(dt, vv.y, x.y); x.z = mul_add_sep2(dt, vv.z, x.z);
+  vv.x = mul_add_sep(dt, ax, vv.x); vv.y = mul_add_sep(dt, ay, vv.y); vv.z = mul_add_sep(dt, az, vv.z);
+  x.x = mul_add_sep(dt, vv.x, x.x); x.y = mul_add_sep(dt, vv.y, x.y); x.z = mul_add_sep(dt, vv.z, x.z);
   if (finisher) {
     vel[il] = vv;
     posm_out[i_begin + il] = x;

@@ -176,40 +176,22 @@ __global__ __launch_bounds__(kBlock) void census_fold_f64_kernel(const double *_
 }
 
 // The pair reductions, shaped like launch_tidal_time's (kernels_probe.hip): two launches, no atomics, the same bits and the same row every
-// run.  A candidate is (value, row); the smallest value wins, the lowest row among equals.
-struct CensusMin { double v; int i; };
-__device__ __forceinline__ void census_min_take(CensusMin &a, double v, int i) {
-  if (v < a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
-}
-__device__ __forceinline__ CensusMin census_min_workgroup(CensusMin a, CensusMin (&red)[kBlock / 64]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double v = __shfl_xor(a.v, off, 64);
-    const int i = __shfl_xor(a.i, off, 64);
-    census_min_take(a, v, i);
-  }
-  if ((t & 63) == 0) red[t >> 6] = a;
-  __syncthreads();
-  CensusMin r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) census_min_take(r, red[w].v, red[w].i);
-  return r;
-}
+// run.  A candidate is (value, row); the smallest value wins, the lowest row among equals: value_at_workgroup<false> (pk_common.h).
 __global__ __launch_bounds__(kBlock) void census_pair_parts_kernel(const double *__restrict__ value, int n, double *__restrict__ part) {
-  __shared__ CensusMin red[kBlock / 64];
-  CensusMin a{__builtin_inf(), 0x7fffffff};
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) census_min_take(a, value[i], i);
-  const CensusMin r = census_min_workgroup(a, red);
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt a{__builtin_inf(), 0x7fffffff};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) value_at_take<false>(a, value[i], i);
+  const ValueAt r = value_at_workgroup<false>(a, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
 // out[0] = the smallest value, out[1] = its row i, out[2] = index[i], out[3] = aux[i] (aux == nullptr: the value again);
 // no row below +inf: (+inf, -1, -1, +inf)
 __global__ __launch_bounds__(kBlock) void census_pair_fold_kernel(const double *__restrict__ part, int slots, const int *__restrict__ index,
                                                                   const double *__restrict__ aux, double *__restrict__ out) {
-  __shared__ CensusMin red[kBlock / 64];
-  CensusMin a{__builtin_inf(), 0x7fffffff};
-  for (int q = threadIdx.x; q < slots; q += kBlock) census_min_take(a, part[2 * q], (int)part[2 * q + 1]);
-  const CensusMin r = census_min_workgroup(a, red);
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt a{__builtin_inf(), 0x7fffffff};
+  for (int q = threadIdx.x; q < slots; q += kBlock) value_at_take<false>(a, part[2 * q], (int)part[2 * q + 1]);
+  const ValueAt r = value_at_workgroup<false>(a, red);
   if (threadIdx.x == 0) {
     const bool some = r.v < __builtin_inf();
     out[0] = some ? r.v : __builtin_inf();

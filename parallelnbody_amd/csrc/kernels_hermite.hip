@@ -53,14 +53,14 @@ __global__ __launch_bounds__(kBlock) void hermite_correct_kernel(double4 *__rest
 // +inf; the candidates (k, body) reduced as jerk_time_parts_kernel reduces its own.
 __global__ __launch_bounds__(kBlock) void hermite_time_parts_kernel(const double *__restrict__ aj0, const double4 *__restrict__ a2,
                                                                     const double4 *__restrict__ a3, int n, double *__restrict__ part) {
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax m{-1.0, 0x7fffffff};
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt m{-1.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const Aj s = load_aj(aj0, i);
     const double4 d2 = a2[i], d3 = a3[i];
-    tidal_max_take(m, ratio_k<true>(hermite4_ratio(norm3(s.a[0], s.a[1], s.a[2]), norm3(s.j[0], s.j[1], s.j[2]), norm3(d2), norm3(d3))), i);
+    value_at_take<true>(m, ratio_k<true>(hermite4_ratio(norm3(s.a[0], s.a[1], s.a[2]), norm3(s.j[0], s.j[1], s.j[2]), norm3(d2), norm3(d3))), i);
   }
-  const TidalMax r = tidal_max_workgroup(m, red);
+  const ValueAt r = value_at_workgroup<true>(m, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
 

@@ -6,7 +6,7 @@
 //   hermite[6]_block_list_kernel  <- hermite_block_list (hermite_block_sched.h): T_next = the smallest of those, the bodies that attain it
 //                                    as a list in ascending body index; EVERY body predicted to T_next with its own dt by the order's
 //                                    predictor (hermite_step64.h): (xp, vp), sixth order (xp, vp, ap)
-//   jerk_tile_f64_kernel<., ., true> (jerk_tile64.h) / snap_tile_f64_kernel<., ., true> (snap_tile64.h)  <- the rows of the listed bodies
+//   deriv_tile_f64_kernel<., ., true, false, SNAP> (deriv_tile64.h: the jerk pass's / the snap pass's kernel)  <- the rows of the listed bodies
 //                                    against all predicted bodies: one partial row per listed body and chunk, the chunks, the pair
 //                                    operations and their order those of nbody_get_jerk_f64 / nbody_get_snap_f64
 //   hermite[6]_block_correct_kernel <- the listed bodies: the chunks' rows added in chunk order (the fold kernels' sums), the order's
@@ -17,13 +17,13 @@
 // What is written once and what per order: DESIGN 4.16b.  EVERY operation outside the pair sums is one correctly rounded fp64 operation
 // in the order written: contraction is off for the whole file, so that numpy (tests/hermite_block_ref.py, tests/hermite6_block_ref.py)
 // reproduces a block step in every bit.  No scratch, no grid-wide waits; the one atomic is an integer count of floor hits.
-#include "jerk_tile64.h"
 #include "kernels.h"
+
+#include "deriv_tile64.h"
 
 #include "hermite_block_level.h"
 #include "hermite_block_sched.h"
 #include "hermite_step64.h"
-#include "snap_tile64.h"
 
 #pragma clang fp contract(off)
 
@@ -293,10 +293,9 @@ hipError_t launch_hermite_block_evaluate(const HermiteBlockLaunch &L, int first,
   if ((size_t)m > probe_slab_points(L.n, 3)) return hipErrorInvalidValue;
   const bool soft = L.eps2 > 0.0;
   const dim3 grid((m + kBlock * lanes - 1) / (kBlock * lanes), j_split);
-  const auto kernel = lanes == 1 ? (soft ? jerk_tile_f64_kernel<true, 1, true> : jerk_tile_f64_kernel<false, 1, true>)
-                                 : (soft ? jerk_tile_f64_kernel<true, 2, true> : jerk_tile_f64_kernel<false, 2, true>);
-  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.xp, (const double4 *)L.vp, (double *)L.part, L.n, m, 0, j_chunk,
-                     L.G, L.eps2, (const int *)L.list + first);
+  hipLaunchKernelGGL((deriv_tile_f64_form<true, false, false>(lanes, soft)), grid, dim3(kBlock), 0, s,
+                     DerivArgs<false, false>{(const double4 *)L.xp, (const double4 *)L.vp, L.n, m, 0, j_chunk, L.G, L.eps2, (const int *)L.list + first},
+                     (double *)L.part);
   return hipGetLastError();
 }
 
@@ -307,10 +306,10 @@ hipError_t launch_hermite6_block_evaluate(const Hermite6BlockLaunch &L, int firs
   if ((size_t)m > probe_slab_points(L.n, kSnapRowWidth)) return hipErrorInvalidValue;
   const bool soft = L.eps2 > 0.0;
   const dim3 grid((m + kBlock * lanes - 1) / (kBlock * lanes), j_split);
-  const auto kernel = lanes == 1 ? (soft ? snap_tile_f64_kernel<true, 1, true> : snap_tile_f64_kernel<false, 1, true>)
-                                 : (soft ? snap_tile_f64_kernel<true, 2, true> : snap_tile_f64_kernel<false, 2, true>);
-  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, (const double4 *)L.xp, (const double4 *)L.vp, (const double *)L.ap, 4,
-                     (double *)L.part, L.n, m, 0, j_chunk, L.G, L.eps2, (const int *)L.list + first);
+  hipLaunchKernelGGL((deriv_tile_f64_form<true, false, true>(lanes, soft)), grid, dim3(kBlock), 0, s,
+                     DerivArgs<false, true>{(const double4 *)L.xp, (const double4 *)L.vp, (const double *)L.ap, 4, L.n, m, 0, j_chunk, L.G, L.eps2,
+                                            (const int *)L.list + first},
+                     (double *)L.part);
   return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@
 //   probe_jerk_pk_kernel   <- fp32 state: the tile loop of point_tile.h with the bodies' velocities in a second pair of LDS tiles, the
 //                             potential's distance term, six accumulators, no s^-5; SELF: the points are the bodies, j == i dropped by index
 //   jerk_fold_kernel       <- the chunks' rows added in chunk order in fp64, rounded once
-//   jerk_tile_f64_kernel   <- fp64 state, the bodies only: scalar, shaped like forces_tile_kernel<double> (kernels.hip): the <SOFT, 2, false> form of jerk_tile64.h's template
+//   deriv_tile_f64_kernel  <- fp64 state, the bodies only: scalar, shaped like forces_tile_kernel<double> (kernels.hip): the <SOFT, 2, false, false, false> form of deriv_tile64.h's template
 //   jerk_fold_f64_kernel   <- its chunks' rows added in chunk order
 //   jerk_time_*_kernel     <- the largest |j_i|^2 / |a_i|^2 of the unrounded vectors and its body, reduced in a fixed order
 #include "kernels.h"
@@ -13,7 +13,7 @@
 #include <algorithm>
 
 #include "../../include/nbody.h"
-#include "jerk_tile64.h"
+#include "deriv_tile64.h"
 #include "point_tile.h"
 
 namespace nbody {
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void jerk_fold_kernel(const float4 *__restr
 
 constexpr int kJerk64Ipt = 2;   // bodies per lane
 
-// (jerk_tile_f64_kernel<SOFT, IPT, LIST>: jerk_tile64.h, shared with the active-set evaluation of kernels_hermite_block.hip)
+// (the pair kernel: deriv_tile64.h, shared with the snap, the active-set evaluations of kernels_hermite_block.hip and the points of kernels_points64.hip)
 
 __global__ __launch_bounds__(kBlock) void jerk_fold_f64_kernel(const double *__restrict__ part, int m, int j_split, double *__restrict__ aj64,
                                                                float *__restrict__ ajf) {
@@ -170,17 +170,17 @@ __global__ __launch_bounds__(kBlock) void jerk_fold_f64_kernel(const double *__r
 // 0 / 0 = 0, x / 0 = +inf for x > 0, and a value that is not finite counting as +inf.
 __global__ __launch_bounds__(kBlock) void jerk_time_parts_kernel(const double *__restrict__ aj64, int n, double *__restrict__ part) {
 #pragma clang fp contract(off)
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax a{-1.0, 0x7fffffff};
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt a{-1.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const double *v = aj64 + (size_t)i * 6;
     const double ax = v[0], ay = v[1], az = v[2], jx = v[3], jy = v[4], jz = v[5];
     const double a2 = (ax * ax + ay * ay) + az * az, j2 = (jx * jx + jy * jy) + jz * jz;
     double k = (j2 == 0.0 && a2 == 0.0) ? 0.0 : j2 / a2;
     if (!(k <= 0x1.fffffffffffffp1023)) k = __builtin_inf();
-    tidal_max_take(a, k, i);
+    value_at_take<true>(a, k, i);
   }
-  const TidalMax r = tidal_max_workgroup(a, red);
+  const ValueAt r = value_at_workgroup<true>(a, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
 
@@ -199,9 +199,10 @@ hipError_t launch_jerk(const JerkLaunch &L, hipStream_t s) {
     for (size_t first = 0; first < (size_t)L.m; first += slab) {
       const int m = (int)std::min(slab, (size_t)L.m - first);
       const dim3 grid((m + kBlock * kJerk64Ipt - 1) / (kBlock * kJerk64Ipt), j_split);
-      hipLaunchKernelGGL((soft ? jerk_tile_f64_kernel<true, kJerk64Ipt, false> : jerk_tile_f64_kernel<false, kJerk64Ipt, false>), grid, dim3(kBlock), 0, s,
-                         (const double4 *)L.posm, (const double4 *)L.vel, (double *)L.part, L.n_total, m, (int)first, j_chunk, L.G, L.eps2,
-                         (const int *)nullptr);
+      hipLaunchKernelGGL((soft ? deriv_tile_f64_kernel<true, kJerk64Ipt, false, false, false> : deriv_tile_f64_kernel<false, kJerk64Ipt, false, false, false>),
+                         grid, dim3(kBlock), 0, s,
+                         DerivArgs<false, false>{(const double4 *)L.posm, (const double4 *)L.vel, L.n_total, m, (int)first, j_chunk, L.G, L.eps2, nullptr},
+                         (double *)L.part);
       hipLaunchKernelGGL(jerk_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
                          L.aj64 ? L.aj64 + 6 * first : nullptr, L.ajf ? L.ajf + 6 * first : nullptr);
     }

@@ -236,43 +236,25 @@ __device__ __forceinline__ void core_sum_workgroup(double (&a)[S], double (&red)
     a[s] = v;
   }
 }
-// the largest weight and the lowest body that attains it
-struct CoreMax { double v; int i; };
-__device__ __forceinline__ void core_max_take(CoreMax &a, double v, int i) {
-  if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
-}
-__device__ __forceinline__ CoreMax core_max_workgroup(CoreMax a, CoreMax (&red)[kBlock / 64]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double v = __shfl_xor(a.v, off, 64);
-    const int i = __shfl_xor(a.i, off, 64);
-    core_max_take(a, v, i);
-  }
-  if ((t & 63) == 0) red[t >> 6] = a;
-  __syncthreads();
-  CoreMax r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) core_max_take(r, red[w].v, red[w].i);
-  return r;
-}
+// (the largest weight and the lowest body that attains it: value_at_workgroup<true>, pk_common.h)
 
 constexpr int kCoreCentreRow = 8;   // doubles of a workgroup's row of pass A: S0, Sx, Sy, Sz, used, rho_max, densest, pad
 // pass A: S0 = sum w, S = sum w x, used = the bodies with w > 0, the largest w and the lowest body with it
 __global__ __launch_bounds__(kBlock) void core_centre_parts_kernel(const double4 *__restrict__ posm, const double *__restrict__ rho, int n,
                                                                    double *__restrict__ part) {
   __shared__ double red[5][kBlock / 64];
-  __shared__ CoreMax redm[kBlock / 64];
+  __shared__ ValueAt redm[kBlock / 64];
   double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  CoreMax best{0.0, 0x7fffffff};
+  ValueAt best{0.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const double w = core_weight(rho[i]);
     const double4 p = posm[i];
     a[0] += w; a[1] += w * p.x; a[2] += w * p.y; a[3] += w * p.z;
     a[4] += w > 0.0 ? 1.0 : 0.0;
-    if (w > 0.0) core_max_take(best, w, i);
+    if (w > 0.0) value_at_take<true>(best, w, i);
   }
   core_sum_workgroup<5>(a, red);
-  const CoreMax r = core_max_workgroup(best, redm);
+  const ValueAt r = value_at_workgroup<true>(best, redm);
   if (threadIdx.x == 0) {
     double *row = part + (size_t)kCoreCentreRow * blockIdx.x;
     row[0] = a[0]; row[1] = a[1]; row[2] = a[2]; row[3] = a[3]; row[4] = a[4]; row[5] = r.v; row[6] = (double)r.i;
@@ -281,17 +263,17 @@ __global__ __launch_bounds__(kBlock) void core_centre_parts_kernel(const double4
 // out[0] = S0, out[1 .. 3] = centre = S / S0, out[4] = used, out[5] = rho_max, out[6] = densest; used == 0: centre NaN, densest -1, rho_max 0
 __global__ __launch_bounds__(kBlock) void core_centre_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
   __shared__ double red[5][kBlock / 64];
-  __shared__ CoreMax redm[kBlock / 64];
+  __shared__ ValueAt redm[kBlock / 64];
   double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  CoreMax best{0.0, 0x7fffffff};
+  ValueAt best{0.0, 0x7fffffff};
   for (int q = threadIdx.x; q < slots; q += kBlock) {
     const double *row = part + (size_t)kCoreCentreRow * q;
 #pragma unroll
     for (int s = 0; s < 5; ++s) a[s] += row[s];
-    if (row[5] > 0.0) core_max_take(best, row[5], (int)row[6]);
+    if (row[5] > 0.0) value_at_take<true>(best, row[5], (int)row[6]);
   }
   core_sum_workgroup<5>(a, red);
-  const CoreMax r = core_max_workgroup(best, redm);
+  const ValueAt r = value_at_workgroup<true>(best, redm);
   if (threadIdx.x == 0) {
     const bool some = a[4] > 0.0;
     const double nan = __builtin_nan("");

@@ -320,27 +320,27 @@ __global__ __launch_bounds__(kBlock) void tidal_fold_kernel(const float4 *__rest
 }
 
 // nbody_tidal_time's reduction, shaped like energy_fast_*_kernel: two launches, no atomics, the same bits and the same body every run.
-// A candidate is (n2, body) (point_tile.h: tidal_max_*); a value that is not finite counts as +inf.
+// A candidate is (n2, body) (pk_common.h: value_at_*); a value that is not finite counts as +inf.
 __global__ __launch_bounds__(kBlock) void tidal_time_parts_kernel(const double *__restrict__ t64, int n, double *__restrict__ part) {
 #pragma clang fp contract(off)
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax a{-1.0, 0x7fffffff};
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt a{-1.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const double *t = t64 + (size_t)i * 6;
     const double xx = t[0], yy = t[1], zz = t[2], xy = t[3], xz = t[4], yz = t[5];
     double n2 = (xx * xx + yy * yy) + zz * zz + 2.0 * ((xy * xy + xz * xz) + yz * yz);
     if (!(n2 <= 0x1.fffffffffffffp1023)) n2 = __builtin_inf();
-    tidal_max_take(a, n2, i);
+    value_at_take<true>(a, n2, i);
   }
-  const TidalMax r = tidal_max_workgroup(a, red);
+  const ValueAt r = value_at_workgroup<true>(a, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
 // the one fold of every (value, body) maximum: the workgroups' pairs in a fixed order (launch_max_fold)
 __global__ __launch_bounds__(kBlock) void max_fold_kernel(const double *__restrict__ part, int slots, double *__restrict__ out) {
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax a{-1.0, 0x7fffffff};
-  for (int q = threadIdx.x; q < slots; q += kBlock) tidal_max_take(a, part[2 * q], (int)part[2 * q + 1]);
-  const TidalMax r = tidal_max_workgroup(a, red);
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt a{-1.0, 0x7fffffff};
+  for (int q = threadIdx.x; q < slots; q += kBlock) value_at_take<true>(a, part[2 * q], (int)part[2 * q + 1]);
+  const ValueAt r = value_at_workgroup<true>(a, red);
   if (threadIdx.x == 0) { out[0] = r.v; out[1] = (double)r.i; }
 }
 

@@ -3,10 +3,9 @@
 // fp64 state, the bodies only.  With d = x_j - x_i, w = v_j - v_i, b = acc_j - acc_i (acc: a per-body INPUT array), s^2 = |d|^2 + eps^2,
 // t = 1 / s, al = (d . w) t^2, be = (w . w + d . b) t^2 + al^2:
 //     A_ij = G m_j d t^3      J_ij = G m_j w t^3 - 3 al A_ij      S_ij = G m_j b t^3 - 6 al J_ij - 3 be A_ij
-//   snap_tile_f64_kernel    <- (snap_tile64.h) shaped like jerk_tile_f64_kernel (jerk_tile64.h, which this file neither includes nor
-//                              changes): its chunks, its tiles, its rsq, its zero rule and, up to A and J, its operations in its order — so
-//                              the A and J of a snap pass are nbody_get_jerk_f64's in every bit; a third pair of LDS tiles holds the
-//                              input accelerations
+//   deriv_tile_f64_kernel   <- (deriv_tile64.h) the <SOFT, kSnapIpt, false, false, true> form of the jerk pass's own kernel template: the g and S
+//                              chains beside its A and J chains — so the A and J of a snap pass are nbody_get_jerk_f64's in every bit —; a
+//                              third pair of LDS tiles holds the input accelerations
 //   snap_fold_f64_kernel    <- the chunks' rows, nine doubles per body, added in chunk order
 //   hermite6_predict_kernel <- (xp, vp, ap) from (x, v, a0, j0, s0, a3): the Taylor series to fifth / fourth / third order
 //   hermite6_correct_kernel <- (x, v) from (a0, j0, s0) and the (a1, j1, s1) of the predicted state; the stored acceleration; a3, a4, a5
@@ -21,9 +20,9 @@
 
 #include <algorithm>
 
+#include "deriv_tile64.h"
 #include "hermite_step64.h"
 #include "point_tile.h"
-#include "snap_tile64.h"
 
 #pragma clang fp contract(off)
 
@@ -93,8 +92,8 @@ __global__ __launch_bounds__(kBlock) void hermite6_correct_kernel(double4 *__res
 __global__ __launch_bounds__(kBlock) void hermite6_time_parts_kernel(const double *__restrict__ ajs0, const double4 *__restrict__ a3,
                                                                      const double4 *__restrict__ a4, const double4 *__restrict__ a5,
                                                                      int n, int derivs, double *__restrict__ part) {
-  __shared__ TidalMax red[kBlock / 64];
-  TidalMax m{-1.0, 0x7fffffff};
+  __shared__ ValueAt red[kBlock / 64];
+  ValueAt m{-1.0, 0x7fffffff};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const Ajs s = load_ajs(ajs0, i);
     Ratio r;
@@ -104,9 +103,9 @@ __global__ __launch_bounds__(kBlock) void hermite6_time_parts_kernel(const doubl
     } else {
       r = Ratio{sqnorm3(s.j[0], s.j[1], s.j[2]), sqnorm3(s.a[0], s.a[1], s.a[2])};
     }
-    tidal_max_take(m, ratio_k<true>(r), i);
+    value_at_take<true>(m, ratio_k<true>(r), i);
   }
-  const TidalMax r = tidal_max_workgroup(m, red);
+  const ValueAt r = value_at_workgroup<true>(m, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = r.v; part[2 * blockIdx.x + 1] = (double)r.i; }
 }
 
@@ -125,9 +124,11 @@ hipError_t launch_snap(const SnapLaunch &L, hipStream_t s) {
   for (size_t first = 0; first < (size_t)L.n_total; first += slab) {
     const int m = (int)std::min(slab, (size_t)L.n_total - first);
     const dim3 grid((m + kBlock * kSnapIpt - 1) / (kBlock * kSnapIpt), j_split);
-    hipLaunchKernelGGL((soft ? snap_tile_f64_kernel<true, kSnapIpt, false> : snap_tile_f64_kernel<false, kSnapIpt, false>), grid, dim3(kBlock), 0, s,
-                       (const double4 *)L.posm, (const double4 *)L.vel, L.ain, L.ain_stride, (double *)L.part, L.n_total, m, (int)first,
-                       j_chunk, L.G, L.eps2, (const int *)nullptr);
+    hipLaunchKernelGGL((soft ? deriv_tile_f64_kernel<true, kSnapIpt, false, false, true> : deriv_tile_f64_kernel<false, kSnapIpt, false, false, true>),
+                       grid, dim3(kBlock), 0, s,
+                       DerivArgs<false, true>{(const double4 *)L.posm, (const double4 *)L.vel, L.ain, L.ain_stride, L.n_total, m, (int)first, j_chunk, L.G,
+                                              L.eps2, nullptr},
+                       (double *)L.part);
     hipLaunchKernelGGL(snap_fold_f64_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const double *)L.part, m, j_split,
                        L.ajs64 + 9 * first);
   }

@@ -2,7 +2,7 @@
 // (work items = an i-set in registers against a strip of 64-body subtiles, 256-body j tiles in LDS, the running j-side
 // sum moving from lane to lane with its body, item-private partial-sum segments), with double state and plain v_*_f64 arithmetic:
 // there is no packed fp64, a lane simply carries two i-bodies.  Pair law OctreeSearch.h:101-104 in double (build-
-// defined: the reference is fp32); rsq = v_rsq_f64 + two Newton steps.
+// defined: the reference is fp32); rsq = rsq_dev(double) of pk_common.h.
 //
 // One pair evaluation = 22 fp64 ops (3 sub, 3 for r^2, 6 for rsq, 4 scale factors, 6 accumulate FMAs; 20 in the
 // equal-mass form, which has no mass factors) and serves two interactions; the one-sided fp64 kernel spends ~24 per interaction.  The running sums cost six v_mov_b32_dpp per step
@@ -15,16 +15,6 @@
 namespace nbody {
 
 namespace {
-
-
-// 1/sqrt(x): v_rsq_f64 seed (~2^-26 relative) and ONE third-order step, y (1 + e/2 + 3/8 e^2) with e = 1 - x y^2:
-// the error goes to ~e^3/3 — far below 2^-53 — in five ops where two Newton steps take seven.
-__device__ __forceinline__ double rsq64(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = fma(-(x * y), y, 1.0);
-  const double q = e * fma(e, 0.375, 0.5);
-  return fma(y, q, y);
-}
 
 // One 64-body subtile against the lane's bodies K0 .. IPT-1 (see sym_subtile in kernels_sym.hip): ONE = false, K0 = 0 is
 // a symmetric strip; ONE = true is a subtile of the i-set's OWN block that lies in the lanes' slot K0 — the slots above meet
@@ -45,7 +35,7 @@ __device__ __forceinline__ void sym_subtile64(const double (&xi)[IPT], const dou
       const bool own = ONE && q == K0;
       const double dx = pxy.x - xi[q], dy = pxy.y - yi[q], dz = pzw.x - zi[q];
       const double r2 = SOFT ? fma(dx, dx, fma(dy, dy, fma(dz, dz, eps2))) : fma(dx, dx, fma(dy, dy, dz * dz));
-      double rinv = rsq64(r2);
+      double rinv = rsq_dev(r2);
       if (!SOFT && (!BARE || own)) rinv = (r2 > 0.0) ? rinv : 0.0;
       const double u3 = (rinv * rinv) * rinv;
       const double s_i = UNI ? u3 : u3 * pzw.y;

@@ -1,4 +1,5 @@
-// Shared device helpers of the packed-fp32 force kernels (kernels.hip, kernels_sym.hip).
+// Shared device helpers: the packed-fp32 force kernels' (kernels.hip, kernels_sym.hip) and what every kernel file writes the same way —
+// kBlock, the reciprocal square roots, the reference's two-rounding multiply-add, the (value, index) workgroup reduction.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,46 @@ constexpr int kBlock = 256;   // 4 waves of 64 lanes: one per SIMD of a CU
 enum { Z_SOFT = 0, Z_CLAMP = 1, Z_SELECT = 2, Z_BARE = 3 };
 
 __device__ __forceinline__ float rsq_dev(float x) { return __builtin_amdgcn_rsqf(x); }   // v_rsq_f32, 1 ulp
+
+// 1 / sqrt(x) of every fp64 pair kernel: the v_rsq_f64 seed (~2^-26 relative) and ONE third-order step, y (1 + e/2 + 3/8 e^2) with
+// e = 1 - x y^2: the error goes to ~e^3 / 3, far below 2^-53, in five operations where two Newton steps take seven.  0 and +inf give NaN
+// (x * y is 0 * inf): a caller keeps both out itself.
+__device__ __forceinline__ double rsq_dev(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double e = fma(-(x * y), y, 1.0);
+  const double q = e * fma(e, 0.375, 0.5);
+  return fma(y, q, y);
+}
+
+// c + a * b in TWO roundings, the reference's update (FVector's operator* and operator+, OctreeSearch.cpp:29-30).  HIP's __fmul_rn /
+// __fadd_rn are plain * and + and get contracted into one FMA under the default -ffp-contract=fast; the pragma keeps them apart.
+template <typename T> __device__ __forceinline__ T mul_add_sep(T a, T b, T c) {
+#pragma clang fp contract(off)
+  const T p = a * b;
+  return c + p;
+}
+
+// The (value, index) reduction of the time-scale and census passes: a candidate is (value, index); MAX: the larger value wins, else the
+// smaller; among equal values the lower index.  Lanes first, then the fixed shuffle tree, then the four waves in order: no atomics,
+// the same bits and the same index every run.
+struct ValueAt { double v; int i; };
+template <bool MAX> __device__ __forceinline__ void value_at_take(ValueAt &a, double v, int i) {
+  if ((MAX ? v > a.v : v < a.v) || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
+}
+template <bool MAX> __device__ __forceinline__ ValueAt value_at_workgroup(ValueAt a, ValueAt (&red)[kBlock / 64]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double v = __shfl_xor(a.v, off, 64);
+    const int i = __shfl_xor(a.i, off, 64);
+    value_at_take<MAX>(a, v, i);
+  }
+  if ((t & 63) == 0) red[t >> 6] = a;
+  __syncthreads();
+  ValueAt r = red[0];
+  for (int w = 1; w < kBlock / 64; ++w) value_at_take<MAX>(r, red[w].v, red[w].i);
+  return r;
+}
 
 // Which clock did the kernel run at?  The force loops are power-limited: the clock a box holds under them differs by several
 // per cent from box to box (2.13 - 2.33 GHz seen), so a time alone cannot tell a slower box from slower code.  A wave can read two

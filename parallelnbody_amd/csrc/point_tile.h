@@ -5,7 +5,7 @@
 //   grid.y : j chunks [c * j_chunk, min((c + 1) * j_chunk, n_total)); each writes its own partial row part[c][m]
 // What a pair adds and what a chunk's row holds is the kernel's: a per-tile functor and a write-out.  VEL (the jerk): the bodies'
 // velocities go through a second pair of LDS tiles beside their positions, and the points carry theirs in register pairs.
-// Also here, shared by the two files: the points' slabs (for_point_slabs) and the fixed-order maximum of the time scales (tidal_max_*).
+// Also here, shared by the two files: the points' slabs (for_point_slabs).
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -170,27 +170,6 @@ void for_point_slabs(int n_total, int m_all, int width, Run run) {
     if (wgs2 < 1024) run(std::integral_constant<int, 1>{}, first, m, dim3((m + 2 * kBlock - 1) / (2 * kBlock), j_split), j_split, j_chunk);
     else             run(std::integral_constant<int, 2>{}, first, m, dim3((m + 4 * kBlock - 1) / (4 * kBlock), j_split), j_split, j_chunk);
   }
-}
-
-// The reduction of nbody_tidal_time and nbody_jerk_time: a candidate is (value, body); the larger value wins, equal ones the lower
-// index.  Lanes first, then the fixed shuffle tree, then the four waves in order: no atomics, the same bits and the same body every run.
-struct TidalMax { double v; int i; };
-__device__ __forceinline__ void tidal_max_take(TidalMax &a, double v, int i) {
-  if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; }
-}
-__device__ __forceinline__ TidalMax tidal_max_workgroup(TidalMax a, TidalMax (&red)[kBlock / 64]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double v = __shfl_xor(a.v, off, 64);
-    const int i = __shfl_xor(a.i, off, 64);
-    tidal_max_take(a, v, i);
-  }
-  if ((t & 63) == 0) red[t >> 6] = a;
-  __syncthreads();
-  TidalMax r = red[0];
-  for (int w = 1; w < kBlock / 64; ++w) tidal_max_take(r, red[w].v, red[w].i);
-  return r;
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // What the fp64 row scans share (kernels_pot64.hip, kernels_census64.hip, kernels_neighbours64.hip, kernels_groups64.hip, kernels_mst64.hip, kernels_pairs64.hip): rows held in
 // registers — the bodies themselves or caller points, one or two per lane — against every body of one chunk, the bodies going through
-// LDS.  The shape of all six tile kernels is jerk_tile_f64_kernel's (jerk_tile64.h; DESIGN.md, "The fp64 row scans"):
+// LDS.  The shape of all six tile kernels is deriv_tile_f64_kernel's (deriv_tile64.h; DESIGN.md, "The fp64 row scans"):
 //   grid.x : blocks of kBlock * IPT rows (lane t holds rows ibase + t + k * kBlock: coalesced; the lanes past m repeat row m - 1 and
 //            write nothing)
 //   grid.y : the chunks of probe_geometry(n_total), [c * j_chunk, min((c + 1) * j_chunk, n_total)); each writes its own partial rows
@@ -18,7 +18,7 @@
 #pragma once
 #include <algorithm>
 
-#include "jerk_tile64.h"
+#include "deriv_tile64.h"   // kJerkTile, kJerk64Jb
 
 namespace nbody {
 namespace {

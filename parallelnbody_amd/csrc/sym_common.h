@@ -23,7 +23,7 @@ constexpr int kJT = 256;    // j tile (bodies), 4 subtiles of 64
 // exactly 0 and so is the term — whatever it is multiplied with (G m_j = 0 in the general kernels, nothing at all in the
 // equal-mass kernels, which have no per-body factor to hide a pad behind).  The only float within reach of the pad
 // point is the pad point itself (ulp(1e30) = 7.6e22); a body exactly there selects the guarded kernel (dup_detect).
-// fp64: 1e120 — the squared distance stays finite (the Newton step of rsq64 would turn inf into NaN) and |d|^-3 =
+// fp64: 1e120 — the squared distance stays finite (the refinement step of rsq_dev would turn inf into NaN) and |d|^-3 =
 // 1e-361 underflows to exactly 0.  Doubles within ~6e107 of that point exist (ulp = 1.5e104); mass_check_kernel sends
 // a scene with a body out there (all three coordinates > 9e119) to the general kernels, where the pad's zero mass does it.
 constexpr float kPadFar = 1.0e30f;
@@ -218,12 +218,6 @@ __global__ __launch_bounds__(kBlock) void reduce_j_kernel(const typename SymVec<
   send[b] = o;
 }
 
-template <typename T> __device__ __forceinline__ T mul_add_sep2(T a, T b, T c) {
-#pragma clang fp contract(off)
-  const T p = a * b;
-  return c + p;
-}
-
 // Own body bl: acc = its i-side segments + the rows received from every rank (rank order), times the common G m if
 // the equal-mass kernels ran (`general` non-null and clear); then optionally the reference's update
 // (OctreeSearch.cpp:29-30), multiply and add kept apart.  One workgroup per own granule.
@@ -258,8 +252,8 @@ __global__ __launch_bounds__(kBlock) void update_sym_kernel(typename SymVec<R>::
   acc[bl] = ao;
   if (integrate) {
     V v = vel[bl], x = posm[i_begin + bl];
-    v.x = mul_add_sep2(dt, ax, v.x); v.y = mul_add_sep2(dt, ay, v.y); v.z = mul_add_sep2(dt, az, v.z);
-    x.x = mul_add_sep2(dt, v.x, x.x); x.y = mul_add_sep2(dt, v.y, x.y); x.z = mul_add_sep2(dt, v.z, x.z);
+    v.x = mul_add_sep(dt, ax, v.x); v.y = mul_add_sep(dt, ay, v.y); v.z = mul_add_sep(dt, az, v.z);
+    x.x = mul_add_sep(dt, v.x, x.x); x.y = mul_add_sep(dt, v.y, x.y); x.z = mul_add_sep(dt, v.z, x.z);
     vel[bl] = v;
     posm[i_begin + bl] = x;
   }
@@ -320,8 +314,8 @@ __global__ __launch_bounds__(2 * kBlock) void update_sym_fused_kernel(float4 *__
   float4 x = posm[bl];
   if (integrate) {
     float4 v = vel[bl];
-    v.x = mul_add_sep2(dt, ax, v.x); v.y = mul_add_sep2(dt, ay, v.y); v.z = mul_add_sep2(dt, az, v.z);
-    x.x = mul_add_sep2(dt, v.x, x.x); x.y = mul_add_sep2(dt, v.y, x.y); x.z = mul_add_sep2(dt, v.z, x.z);
+    v.x = mul_add_sep(dt, ax, v.x); v.y = mul_add_sep(dt, ay, v.y); v.z = mul_add_sep(dt, az, v.z);
+    x.x = mul_add_sep(dt, v.x, x.x); x.y = mul_add_sep(dt, v.y, x.y); x.z = mul_add_sep(dt, v.z, x.z);
     vel[bl] = v;
     posm[bl] = x;
   }

@@ -51,7 +51,7 @@ def direct_snap(posm, vel, acc_in=None, eps=0.0, dtype=np.float64, g=G, rows=Non
 
 
 def emulate_snap_f64(posm, vel, acc_in, eps=0.0, g=G):
-    """snap_tile_f64_kernel's sums in the kernel's order: fp64 per pair, the kernel's own sequence of operations, one chain per chunk of
+    """the fp64 snap kernel's sums (deriv_tile64.h) in the kernel's order: fp64 per pair, the kernel's own sequence of operations, one chain per chunk of
     probe_geometry in body order, the chunks added in chunk order.  Multiplies and adds are numpy's own (no fused multiply-add, a
     correctly rounded root): the ORDER is the kernel's, not its last bit."""
     f64 = np.float64

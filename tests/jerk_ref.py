@@ -116,7 +116,7 @@ def emulate_jerk_f32(pos, mass, vel, pts, pvel=None, eps=0.0, skip_self=False, g
 
 
 def emulate_jerk_f64(pos, mass, vel, eps=0.0, g=G):
-    """jerk_tile_f64_kernel's sums in the kernel's order, for the bodies themselves: fp64 per pair, one chain per chunk of
+    """the fp64 jerk kernel's sums (deriv_tile64.h) in the kernel's order, for the bodies themselves: fp64 per pair, one chain per chunk of
     probe_geometry in body order, the chunks added in chunk order.  Multiplies and adds are numpy's own (no fused multiply-add, a
     correctly rounded root): the order of the sums is the kernel's, not its last bit."""
     f64 = np.float64
